@@ -2,7 +2,7 @@
 """Headline benchmark: rendered views/sec of the batch-render hot path
 (Manager::step) on N MI355X, one process per GPU.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N \
          --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
@@ -58,6 +58,9 @@ SETTLE_S = float(os.environ.get("MRX_BENCH_SETTLE_S", "0.25"))
 # profiles/r03_k20.txt)
 SETTLE_BATCH = int(os.environ.get("MRX_BENCH_SETTLE_BATCH", "2000"))
 STRONG_WORLDS = 16384    # BASELINE.json configs[3]
+# --dump-outputs: bytes written in all (every rank's share together), and the seed of the view sample
+DUMP_BYTES = 60 << 20
+DUMP_SEED = 20261015
 
 
 def parse(argv=None):
@@ -94,7 +97,16 @@ def parse(argv=None):
                     help="total worlds of the strong-scaling measurement (configs[3]: 16384)")
     ap.add_argument("--cpu-views", type=int, default=4096)
     ap.add_argument("--cpu-threads", type=int, default=16)
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the headline renderer's outputs of its last step to "
+                         "DIR/<name>.npy (float32 / float64; a fixed, seeded sample of the views when they "
+                         "exceed %d MiB)" % (DUMP_BYTES >> 20))
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs and dump_bytes_per_view(a) > DUMP_BYTES // max(1, a.gpus):
+        ap.error("--dump-outputs: one %dx%d view does not fit in %d MiB" % (a.width, a.height, DUMP_BYTES >> 20))
+    return a
 
 
 # --------------------------------------------------------------------------
@@ -180,6 +192,53 @@ def timed_steps(r, steps, barrier):
     t1 = time.perf_counter()
     barrier()
     return t1 - t0, r.elapsed_ms()
+
+
+def ids_output(a):
+    """The per-pixel id buffer a caller of the renderer gets: visibility ids when
+    MADRONA_MI355_VISIBILITY is set, else the segmask of Raytracer mode, else none."""
+    try:
+        if int(os.environ.get("MADRONA_MI355_VISIBILITY", "0") or "0") != 0:
+            return "visibility"
+    except ValueError:
+        pass
+    return "segmask" if a.mode == "Raytracer" else None
+
+
+def dump_bytes_per_view(a):
+    """Bytes one view takes in the dump: rgb and depth as float32, ids as float64."""
+    pixels = a.width * (a.width if a.mode == "Raytracer" else a.height)   # Raytracer views are square
+    return pixels * (4 * 4 + 4 + (8 if ids_output(a) else 0))
+
+
+def dump_outputs(r, a, out_dir, rank, n_gpus):
+    """Write what the renderer's last step produced -- rgb, depth and the id buffer
+    (ids_output) in the renderer's own layout -- as float32 / float64 .npy files under
+    out_dir.  When all views exceed this rank's share of DUMP_BYTES, a seeded sample of
+    views is written; view_index.npy names the views either way.  The scene is
+    deterministic, so the same arguments give the same files on every run."""
+    import numpy as np
+    import torch
+    torch.cuda.synchronize()
+    names = [("rgb", r.rgb_tensor(), np.float32), ("depth", r.depth_tensor(), np.float32)]
+    ids = ids_output(a)
+    if ids == "visibility":
+        names.append((ids, r.visibility_tensor(), np.float64))
+    elif ids == "segmask":
+        names.append((ids, r.segmask_tensor(), np.float64))
+    views = int(names[0][1].to_torch().shape[0])
+    n = min(views, (DUMP_BYTES // n_gpus) // dump_bytes_per_view(a))
+    if n < views:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).choice(views, n, replace=False))
+    else:
+        idx = np.arange(views)
+    sel = torch.from_numpy(idx).to(names[0][1].to_torch().device)
+    prefix = "rank%d_" % rank if n_gpus > 1 else ""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t, dtype in names:
+        arr = t.to_torch().index_select(0, sel).cpu().numpy().astype(dtype)
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), arr)
+    np.save(os.path.join(out_dir, prefix + "view_index.npy"), idx.astype(np.float64))
 
 
 def workload_tag(a, n_gpus):
@@ -415,6 +474,8 @@ def run_rank(a):
         r.step()
     barrier()                                   # (first use sets the communicator up)
     wall, dev_ms = timed_steps(r, a.steps, barrier)
+    if a.dump_outputs:
+        dump_outputs(r, a, a.dump_outputs, rank, n_gpus)
     wall = max_over_ranks(wall)
     total_views = views * n_gpus
     value = total_views * a.steps / wall
@@ -513,7 +574,7 @@ def run_rank(a):
             side = torch.cuda.Stream()
             r.set_stream(side.cuda_stream)
             graph = torch.cuda.CUDAGraph()
-            per_graph = 20
+            per_graph = min(20, k5)
             with torch.cuda.stream(side):
                 r.step()
                 side.synchronize()
@@ -596,7 +657,7 @@ def run_rank(a):
                 rc = scenes.make_renderer(scenes.synthetic_scene(4096, **kw), gpu_id=local)
             finally:
                 os.environ.pop("MADRONA_MI355_KERNEL", None)
-            k = min(k, max(a.steps, 20))
+            k = min(k, a.steps)
             settle(rc, 0.1)
             wc, msc = timed_steps(rc, k, lambda: None)
             bc = int(rc.bytes_per_step())

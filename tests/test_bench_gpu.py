@@ -4,7 +4,10 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
+
+from madrona_renderer_amd import scenes
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -190,3 +193,49 @@ def test_bvh_workload_with_committed_sq_counters_reports_its_own_roofline(native
     assert r["bound"] == "valu-issue" and r["unit"] == "G wave-instr/s" and abs(r["peak"] - 1228.8) < 1e-6
     assert 0.1 < r["frac"] < 1.0 and r["valu_per_wave"] > 300
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
+
+
+def _bench_dump(out_dir, *args):
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--warmup", "2", "--no-cpu-baseline",
+                        "--no-extra", "--no-strong", "--dump-outputs", str(out_dir)] + list(args),
+                       capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    files = {f[:-4]: np.load(os.path.join(out_dir, f)) for f in sorted(os.listdir(out_dir))}
+    for name, arr in files.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+    return out, files
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("mode", ["Rasterizer", "Raytracer"])
+def test_bench_dump_outputs_are_what_the_oracle_renders(native, oracle_mod, tmp_path, mode):
+    # --dump-outputs writes the headline renderer's outputs of its last timed step; 48 views fit whole
+    out, got = _bench_dump(tmp_path, "--steps", "3", "--worlds", "48", "--mode", mode)
+    assert out["steps"] == 3
+    ids = "segmask" if mode == "Raytracer" else None
+    assert sorted(got) == sorted(["rgb", "depth", "view_index"] + ([ids] if ids else []))
+    assert np.array_equal(got["view_index"], np.arange(48))
+    ref = oracle_mod.FlatScene(scenes.synthetic_scene(48, render_mode=mode)).render()
+    assert np.array_equal(got["rgb"], ref["rgb"].astype(np.float32))
+    np.testing.assert_allclose(got["depth"].reshape(ref["depth"].shape), ref["depth"], rtol=1e-4, atol=0)
+    if ids:
+        assert np.array_equal(got[ids], ref[ids].astype(np.float64))
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_of_the_headline_are_a_fixed_sample_under_64_mb(native, oracle_mod, tmp_path):
+    # the default 4096 views do not fit: the same seeded sample of views on every run
+    _, a = _bench_dump(tmp_path / "a", "--steps", "2")
+    _, b = _bench_dump(tmp_path / "b", "--steps", "5")
+    total = sum(os.path.getsize(os.path.join(tmp_path / "a", f)) for f in os.listdir(tmp_path / "a"))
+    assert total <= 64 * 10 ** 6
+    idx = a["view_index"].astype(np.int64)
+    assert 0 < len(idx) < 4096 and np.all(np.diff(idx) > 0) and idx[-1] < 4096
+    for name in a:
+        assert np.array_equal(a[name], b[name]), name
+    # a sampled view is the view of that global world id (synthetic worlds depend on their id only)
+    for k in (0, len(idx) // 2, len(idx) - 1):
+        ref = oracle_mod.FlatScene(scenes.synthetic_scene(1, first_world=int(idx[k]))).render()
+        assert np.array_equal(a["rgb"][k], ref["rgb"][0].astype(np.float32))
+        np.testing.assert_allclose(a["depth"][k].reshape(ref["depth"][0].shape), ref["depth"][0], rtol=1e-4, atol=0)
