@@ -24,6 +24,10 @@ struct ImportedAsset {
 class Manager {
 public:
     enum class RenderMode { Rasterizer, Raytracer };
+    // Which outputs a step renders (the engine's render-config RenderMode RGBD / Depth, plus colour
+    // only): an output that is not rendered has no tensor -- its getters fail as segmaskTensor()
+    // does in Rasterizer mode.  The segmask (Raytracer mode) is rendered under every setting.
+    enum class RenderOutputs { RGBD, Depth, RGB };
 
     struct GeometryConfig {
         const madrona::math::Vector3 *vertices;
@@ -73,6 +77,8 @@ public:
         // Rows per world at least (the reference's maxInstancesPerWorld, src/mgr.cpp:378-388):
         // spare rows start hidden and unbound, see refreshObjects().
         uint32_t maxInstancesPerWorld = 0;
+        // Outputs rendered (MRX_FLAG_NO_RGB / MRX_FLAG_NO_DEPTH): RGBD = both, as the reference.
+        RenderOutputs renderOutputs = RenderOutputs::RGBD;
     };
 
     // Aborts (FATAL-style, like the reference) when construction fails.

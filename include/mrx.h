@@ -91,7 +91,13 @@ enum {
     MRX_FLAG_VISIBILITY_IDS = 1u << 0,
     /* several devices (device_ids): mrx_step only posts the render to the per-device host threads and returns;
      * every other entry point joins them first (the same as MRX_SHARD_ASYNC=1 in the environment) */
-    MRX_FLAG_SHARD_ASYNC = 1u << 1
+    MRX_FLAG_SHARD_ASYNC = 1u << 1,
+    /* output selection (the engine's RenderMode RGBD / Depth, plus colour only): a render stores only
+     * the outputs selected, and the tensor of an output that is not is never allocated -- mrx_buffer /
+     * mrx_buffer_shard / mrx_copy_to_host on it fail with MRX_E_UNSUPPORTED.  The segmask (Raytracer
+     * mode) and the visibility ids are written under every setting.  Both bits together: MRX_E_INVALID. */
+    MRX_FLAG_NO_RGB = 1u << 2,      /* depth only */
+    MRX_FLAG_NO_DEPTH = 1u << 3     /* rgb only   */
 };
 
 /* Manager::Config + Config::RenderConfig, /root/reference/src/mgr.hpp:49-88.

@@ -281,7 +281,9 @@ struct SetupArgs {
     int32_t transposed;
 };
 
-template <int IDS, bool TEX, int TW, int TH, bool FINAL, int ZS = TW>
+// OUT: output selection (raster.hpp OutSel) -- fixed in the flat kernel, kOutByPointer (a null output is skipped
+// at run time) in the tile kernel.  Depth only: no colour is looked up or stashed, no texel is loaded.
+template <int IDS, bool TEX, int TW, int TH, bool FINAL, int ZS = TW, int OUT = kOutByPointer>
 __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long long *zbuf, const float4 *shadeTab,
                                              const float (*coldTab)[kCold], uint32_t view, uint32_t tileX0,
                                              uint32_t tileY0, int wave, int lane)
@@ -299,6 +301,7 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
     const size_t tileBase = ((size_t)view * p.nslow + tileY0) * p.nfast + tileX0;
     const bool full = (p.nfast & 3u) == 0 && tileX0 + TW <= p.nfast && tileY0 + TH <= p.nslow;
     const uint32_t fy = tileY0 + 8u * wave + ly;
+    const bool doRgb = storesRgb<OUT>(p.rgb), doDepth = storesDepth<OUT>(p.depth);
 #pragma unroll
     for (int hf = 0; hf < kHalves; ++hf) {
         unsigned long long *zrow = zbuf + (8 * wave + ly) * ZS + 32 * hf + 4 * lx;
@@ -337,7 +340,7 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
         // Textured winners: the texel loads of the half's four pixels are all issued before any
         // is used (addresses of untextured pixels point at texel 0) -- under per-pixel branches
         // every load waited for the one before it.
-        if (TEX && __ballot(anyTexOn) != 0) {
+        if (TEX && OUT != kOutDepth && doRgb && __ballot(anyTexOn) != 0) {
             uint32_t texAddr[kRegionBlocks], texel[kRegionBlocks];
 #pragma unroll
             for (int b = 0; b < kRegionBlocks; ++b) {
@@ -383,7 +386,8 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
                 // (pixels without a winner yet get the background, which whoever wins them
                 // later -- or the tile's last resolve -- overwrites)
                 if (anyMine) {
-                    streamStore16(p.writeThrough, p.rgb + o, rgba[0], rgba[1], rgba[2], rgba[3]);
+                    if (doRgb)
+                        streamStore16(p.writeThrough, p.rgb + o, rgba[0], rgba[1], rgba[2], rgba[3]);
                     if (IDS == 2)
                         streamStore16(p.writeThrough, p.ids + o, (uint32_t)seg[0], (uint32_t)seg[1], (uint32_t)seg[2],
                                       (uint32_t)seg[3]);
@@ -392,7 +396,8 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
 #pragma unroll
                 for (int b = 0; b < kRegionBlocks; ++b)
                     if (mine[b] && fx0 + b < p.nfast && fy < p.nslow) {
-                        streamStore4(p.writeThrough, p.rgb + o + b, rgba[b]);
+                        if (doRgb)
+                            streamStore4(p.writeThrough, p.rgb + o + b, rgba[b]);
                         if (IDS == 2)
                             streamStore4(p.writeThrough, p.ids + o + b, (uint32_t)seg[b]);
                     }
@@ -406,7 +411,9 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
         // pixels resolved in an earlier round: their colour / label come back from the tensors
         if (__ballot(anyStashed) != 0) {
             if (anyStashed && full) {
-                const u32x4 prgb = streamLoad16(p.rgb + o);
+                u32x4 prgb = { 0u, 0u, 0u, 0u };
+                if (doRgb)
+                    prgb = streamLoad16(p.rgb + o);
                 u32x4 pseg = { 0u, 0u, 0u, 0u };
                 if (IDS == 2)
                     pseg = streamLoad16(p.ids + o);
@@ -420,7 +427,8 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
 #pragma unroll
                 for (int b = 0; b < kRegionBlocks; ++b)
                     if (low[b] != 0u && (low[b] & kStashed) == kStashed && fx0 + b < p.nfast && fy < p.nslow) {
-                        rgba[b] = streamLoad4(p.rgb + o + b);
+                        if (doRgb)
+                            rgba[b] = streamLoad4(p.rgb + o + b);
                         if (IDS == 2)
                             seg[b] = (int32_t)streamLoad4(p.ids + o + b);
                     }
@@ -429,21 +437,26 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
         uint32_t dep[kRegionBlocks], id[kRegionBlocks];
 #pragma unroll
         for (int b = 0; b < kRegionBlocks; ++b) {
-            dep[b] = low[b] != 0u ? __float_as_uint(__builtin_amdgcn_rcpf(__uint_as_float(itBits[b]))) : 0u;
+            if (OUT != kOutRGB)
+                dep[b] = low[b] != 0u ? __float_as_uint(__builtin_amdgcn_rcpf(__uint_as_float(itBits[b]))) : 0u;
             id[b] = IDS == 2 ? (uint32_t)seg[b]
                              : (low[b] != 0u ? (~(low[b] >> kSlotBits) & kKeyMask) : 0xFFFFFFFFu);
         }
         if (full) {
-            streamStore16(p.writeThrough, p.rgb + o, rgba[0], rgba[1], rgba[2], rgba[3]);
-            streamStore16(p.writeThrough, p.depth + o, dep[0], dep[1], dep[2], dep[3]);
+            if (doRgb)
+                streamStore16(p.writeThrough, p.rgb + o, rgba[0], rgba[1], rgba[2], rgba[3]);
+            if (doDepth)
+                streamStore16(p.writeThrough, p.depth + o, dep[0], dep[1], dep[2], dep[3]);
             if (IDS)
                 streamStore16(p.writeThrough, p.ids + o, id[0], id[1], id[2], id[3]);
         } else if (fy < p.nslow) {
 #pragma unroll
             for (int b = 0; b < kRegionBlocks; ++b)
                 if (fx0 + b < p.nfast) {
-                    streamStore4(p.writeThrough, p.rgb + o + b, rgba[b]);
-                    streamStore4(p.writeThrough, p.depth + o + b, dep[b]);
+                    if (doRgb)
+                        streamStore4(p.writeThrough, p.rgb + o + b, rgba[b]);
+                    if (doDepth)
+                        streamStore4(p.writeThrough, p.depth + o + b, dep[b]);
                     if (IDS)
                         streamStore4(p.writeThrough, p.ids + o + b, id[b]);
                 }
@@ -1323,7 +1336,10 @@ constexpr size_t flatLdsBytes(bool tex)
            (size_t)kFlatTris * kInstRecDw * 4u;
 }
 
-template <int IDS, bool TEX>
+// OUT: output selection (raster.hpp OutSel: kOutRGBD, kOutDepth or kOutRGB), fixed per instantiation.  Depth only:
+// the set-up does no colour work and writes every record in the untextured form (object id only), the resolve loads
+// no texel and stores no rgb; rgb only: no depth reciprocal, no depth store.
+template <int IDS, bool TEX, int OUT = kOutRGBD>
 __global__ __launch_bounds__(kWave * 8, MRX_FLAT_ZBUFS == 2 ? 4 : 6)
 void bvhFlatKernel(const RasterParams p)
 {
@@ -1441,15 +1457,16 @@ void bvhFlatKernel(const RasterParams p)
         bool valid = false;
         if (hasT) {
             float shade[4] = { 0.f, 0.f, 0.f, 0.f }, cold[kCold];
-            valid = setupTriangleCore<false>(p, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
+            valid = setupTriangleCore<false, OUT != kOutDepth>(p, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
+            const bool texRec = OUT != kOutDepth && valid && __float_as_int(shade[1]) >= 0;
             if (!TEX)
                 shadeTab[lane + 1] = make_float4(shade[0], shade[1], shade[2], __int_as_float(lane));
-            else if (!(valid && __float_as_int(shade[1]) >= 0)) {
+            else if (!texRec) {
                 float *dst = coldTab[lane + 1];
                 dst[0] = shade[0];
                 *reinterpret_cast<float2 *>(dst + 10) = make_float2(__uint_as_float(0u), shade[2]);
             }
-            if (TEX && valid && __float_as_int(shade[1]) >= 0) {
+            if (TEX && texRec) {
                 // (u/v planes as the general kernel derives them: uvPlanes() from the edge planes and |1/d|)
                 const float4 *tsrc = reinterpret_cast<const float4 *>(p.tris + myTri);
                 const float4 t2 = tsrc[2], t3 = tsrc[3];
@@ -1640,7 +1657,7 @@ void bvhFlatKernel(const RasterParams p)
             KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(pk));
             const ResolveArgs ra = { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough };
-            resolveStrip<IDS, TEX, TW, TH, true, kFlatZS>(ra, zb, shadeTab, coldTab, view, tileX0, tileY0, wave, lane);
+            resolveStrip<IDS, TEX, TW, TH, true, kFlatZS, OUT>(ra, zb, shadeTab, coldTab, view, tileX0, tileY0, wave, lane);
         }
         MRX_STAMP(5);
         if (--left == 0)
@@ -1695,25 +1712,34 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
             return ge;
         if (dev < 0 || dev >= kMaxDevices)
             return hipErrorInvalidDevice;
-#define MRX_FLAT(I, T)                                                                          \
+#define MRX_FLAT_O(I, T, O)                                                                     \
     do {                                                                                       \
         static bool allowed[kMaxDevices] = {};                                                 \
         {                                                                                      \
             std::lock_guard<std::mutex> guard(attrMutex);                                      \
             if (!allowed[dev]) {                                                               \
-                const hipError_t e = hipFuncSetAttribute((const void *)bvhFlatKernel<I, T>,   \
+                const hipError_t e = hipFuncSetAttribute((const void *)bvhFlatKernel<I, T, O>, \
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)flatLdsBytes(T)); \
                 if (e != hipSuccess)                                                           \
                     return e;                                                                  \
                 allowed[dev] = true;                                                           \
             }                                                                                  \
         }                                                                                      \
-        bvhFlatKernel<I, T><<<grid, block, flatLdsBytes(T), stream>>>(p);                      \
+        bvhFlatKernel<I, T, O><<<grid, block, flatLdsBytes(T), stream>>>(p);                   \
+    } while (0)
+        // output selection: one instantiation per setting (kOutRGBD = the kernel as it always was)
+        const OutSel out = outSelOf(p.rgb, p.depth);
+#define MRX_FLAT(I, T)                                                                          \
+    do {                                                                                       \
+        if (out == kOutDepth)    MRX_FLAT_O(I, T, kOutDepth);                                  \
+        else if (out == kOutRGB) MRX_FLAT_O(I, T, kOutRGB);                                    \
+        else                     MRX_FLAT_O(I, T, kOutRGBD);                                   \
     } while (0)
         if (ids == 2) { if (tex) MRX_FLAT(2, true); else MRX_FLAT(2, false); }
         else if (ids == 1) { if (tex) MRX_FLAT(1, true); else MRX_FLAT(1, false); }
         else { if (tex) MRX_FLAT(0, true); else MRX_FLAT(0, false); }
 #undef MRX_FLAT
+#undef MRX_FLAT_O
         return hipGetLastError();
     }
     // tile shape: p.bvhTile = 0 (64x64), 1 (64x32: TW 64, TH 32), 2 (32x32)

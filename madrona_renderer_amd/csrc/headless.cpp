@@ -4,7 +4,12 @@
 //
 //   renderer_headless NUM_WORLDS NUM_STEPS rt|rast BATCH_WIDTH BATCH_HEIGHT
 //                     [--dump-last-frame file_name_without_extension]
-//                     [--scene synthetic|demo] [--depth] [--gpus N]
+//                     [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb]
+//
+// --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
+// renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
+// output that exists -- for depth only, a grey tile of 1/depth (nearest hit of the frame white,
+// background black) unless --depth asks for the reference's depth image.
 //
 // --gpus N (no counterpart upstream: the reference has a single gpuID,
 // mgr.hpp:50) renders the worlds on N devices of the node through ONE Manager
@@ -48,6 +53,7 @@ struct Args {
     Mode mode = Mode::Rasterizer;
     bool dump = false, dumpDepth = false, demo = false;
     uint32_t gpus = 1;
+    Manager::RenderOutputs outputs = Manager::RenderOutputs::RGBD;
     std::string outName;
 };
 
@@ -55,7 +61,7 @@ struct Args {
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -82,12 +88,22 @@ Args parse(int argc, char **argv)
             a.dumpDepth = true;
         } else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) {
             a.gpus = (uint32_t)std::atoi(argv[++i]);
+        } else if (!std::strcmp(argv[i], "--outputs") && i + 1 < argc) {
+            const char *o = argv[++i];
+            if (!std::strcmp(o, "rgbd")) a.outputs = Manager::RenderOutputs::RGBD;
+            else if (!std::strcmp(o, "depth")) a.outputs = Manager::RenderOutputs::Depth;
+            else if (!std::strcmp(o, "rgb")) a.outputs = Manager::RenderOutputs::RGB;
+            else usage(argv[0]);
         } else {
             usage(argv[0]);
         }
     }
     if (a.numWorlds == 0 || a.width == 0 || a.height == 0 || a.gpus == 0 || a.gpus > a.numWorlds)
         usage(argv[0]);
+    if (a.dumpDepth && a.outputs == Manager::RenderOutputs::RGB) {
+        std::fprintf(stderr, "--depth: depth is not rendered with --outputs rgb\n");
+        std::exit(EXIT_FAILURE);
+    }
     return a;
 }
 
@@ -201,9 +217,13 @@ void buildDemo(Scene &s, uint32_t n, const std::string &dataDir)
 // Tiled dump, as /root/reference/src/dump.cpp:45-119: ceil(sqrt(N)) rows of
 // images; depth as grey 255 * min(d / 255, 1).  Raytracer storage is [x][y]
 // and is transposed back (dump.cpp:9-21); rasterizer storage is row-major.
+// DumpWhat::InvDepth (a depth-only renderer's default): grey 255 * dmin / d, dmin = the
+// nearest depth of the frame, 0 for background.
+enum class DumpWhat { Rgb, Depth, InvDepth };
 bool dumpTiled(const std::string &name, mrx_renderer *shard, uint32_t numImages, uint32_t resX,
-               uint32_t resY, bool depth, bool transpose)
+               uint32_t resY, DumpWhat what, bool transpose)
 {
+    const bool depth = what != DumpWhat::Rgb;
     const size_t bytesPerImage = (size_t)4 * resX * resY;
     std::vector<uint8_t> host(bytesPerImage * numImages);
     if (mrx_copy_to_host(shard, depth ? MRX_BUF_DEPTH : MRX_BUF_RGB,
@@ -211,6 +231,14 @@ bool dumpTiled(const std::string &name, mrx_renderer *shard, uint32_t numImages,
         std::fprintf(stderr, "%s\n", mrx_last_error());
         return false;
     }
+    float dmin = 0.0f;
+    if (what == DumpWhat::InvDepth)
+        for (size_t i = 0; i < host.size() / 4; ++i) {
+            float d;
+            std::memcpy(&d, host.data() + 4 * i, 4);
+            if (d > 0.0f && (dmin == 0.0f || d < dmin))
+                dmin = d;
+        }
     const uint32_t tilesY = (uint32_t)std::ceil(std::sqrt((double)numImages));
     const uint32_t tilesX = (uint32_t)std::ceil((double)numImages / tilesY);
     const uint32_t outW = tilesX * resX, outH = tilesY * resY;
@@ -225,7 +253,9 @@ bool dumpTiled(const std::string &name, mrx_renderer *shard, uint32_t numImages,
                 if (depth) {
                     float d;
                     std::memcpy(&d, src + 4 * si, 4);
-                    const uint8_t g = (uint8_t)(255.0f * std::fmin(d / 255.0f, 1.0f));
+                    const uint8_t g = what == DumpWhat::InvDepth
+                                          ? (uint8_t)(d > 0.0f ? 255.0f * std::fmin(dmin / d, 1.0f) : 0.0f)
+                                          : (uint8_t)(255.0f * std::fmin(d / 255.0f, 1.0f));
                     dst[0] = dst[1] = dst[2] = g;
                     dst[3] = 255;
                 } else {
@@ -297,6 +327,7 @@ int main(int argc, char **argv)
         cfg.deviceIDs = devices.data();
         cfg.numDevices = args.gpus;
     }
+    cfg.renderOutputs = args.outputs;
 
     Manager mgr(cfg);              // aborts (FATAL) on failure, like the reference
     mgr.sync();
@@ -326,7 +357,9 @@ int main(int argc, char **argv)
             const bool rt = args.mode == Mode::Raycaster;
             const uint32_t resY = rt ? args.width : args.height;
             const std::string name = args.gpus == 1 ? args.outName : args.outName + ".gpu" + std::to_string(g);
-            ok = dumpTiled(name, sh, hi - lo, args.width, resY, args.dumpDepth, rt) && ok;
+            const DumpWhat what = args.dumpDepth ? DumpWhat::Depth
+                                  : args.outputs == Manager::RenderOutputs::Depth ? DumpWhat::InvDepth : DumpWhat::Rgb;
+            ok = dumpTiled(name, sh, hi - lo, args.width, resY, what, rt) && ok;
         }
     }
     if (!ok)

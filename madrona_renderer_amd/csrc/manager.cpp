@@ -94,6 +94,10 @@ Manager::Manager(const Config &cfg)
     c.device_ids = cfg.deviceIDs;
     c.num_devices = cfg.numDevices;
     c.max_instances_per_world = cfg.maxInstancesPerWorld;
+    if (cfg.renderOutputs == RenderOutputs::Depth)
+        c.flags |= MRX_FLAG_NO_RGB;
+    else if (cfg.renderOutputs == RenderOutputs::RGB)
+        c.flags |= MRX_FLAG_NO_DEPTH;
     // build-only knobs travel by environment so Config stays field-compatible
     if (const char *v = std::getenv("MADRONA_MI355_VISIBILITY"))
         if (std::atoi(v) != 0)

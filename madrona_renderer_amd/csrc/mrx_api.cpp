@@ -172,8 +172,10 @@ bool firstKindIsOneBlock(size_t px)
     return px * 4 < (128ull << 20);
 }
 
-hipError_t allocOutputs(size_t px, bool wantIds, bool oneAllocation, DevBuf<uint32_t> &rgb,
-                        DevBuf<float> &depth, DevBuf<int32_t> &ids)
+// Output selection (MRX_FLAG_NO_RGB / MRX_FLAG_NO_DEPTH): a tensor that is not selected is
+// not allocated, and its slab drops out of the layout -- the first tensor present owns the block.
+hipError_t allocOutputs(size_t px, bool wantRgb, bool wantDepth, bool wantIds, bool oneAllocation,
+                        DevBuf<uint32_t> &rgb, DevBuf<float> &depth, DevBuf<int32_t> &ids)
 {
     const size_t depthPhase = outPhase("MRX_OUT_SKEW_DEPTH_KB", 256u << 10);
     const size_t idsPhase = outPhase("MRX_OUT_SKEW_IDS_KB", 64u << 10);
@@ -183,7 +185,7 @@ hipError_t allocOutputs(size_t px, bool wantIds, bool oneAllocation, DevBuf<uint
         // distance is up to the allocator -- this is the other kind of
         // candidate of the placement search: half-GiB outputs were only ever
         // fast this way, 128 MiB ones reliably only in one allocation.
-        hipError_t e = rgb.alloc(px);
+        hipError_t e = wantRgb ? rgb.alloc(px) : hipSuccess;
         size_t gapBytes = 0;
         if (const char *dbg = std::getenv("MRX_OUT_GAP_MB"))    // diagnostic: a held allocation between the tensors
             gapBytes = (size_t)std::atoll(dbg) << 20;
@@ -193,8 +195,9 @@ hipError_t allocOutputs(size_t px, bool wantIds, bool oneAllocation, DevBuf<uint
             if (gapBytes && sp.alloc(gapBytes) == hipSuccess)
                 heldGaps.push_back(sp);
         };
-        if (e == hipSuccess) {
-            gap();
+        if (e == hipSuccess && wantDepth) {
+            if (wantRgb)
+                gap();
             e = depth.alloc(px, depthPhase);
             depth.ptr = reinterpret_cast<float *>(static_cast<char *>(depth.base) + depthPhase);
         }
@@ -208,19 +211,27 @@ hipError_t allocOutputs(size_t px, bool wantIds, bool oneAllocation, DevBuf<uint
         }
         return e;
     }
+    // the first tensor present at offset 0; depth at phase 256 KiB of the period after the rgb slab, ids at
+    // phase 64 KiB of the period after the slab before them
     const size_t tb = (px * 4 + kOutPeriod - 1) / kOutPeriod * kOutPeriod;
-    const size_t depthOff = tb + depthPhase;
-    const size_t idsOff = depthOff + tb + kOutPeriod - (depthOff % kOutPeriod) + idsPhase;
-    const size_t total = (wantIds ? idsOff : depthOff) + px * 4;
+    const size_t depthOff = wantRgb ? tb + depthPhase : 0;
+    const size_t idsOff = wantDepth ? depthOff + tb + kOutPeriod - (depthOff % kOutPeriod) + idsPhase
+                                    : wantRgb ? tb + idsPhase : 0;
+    const size_t end = (wantIds ? idsOff : wantDepth ? depthOff : 0) + px * 4;
+    const size_t total = end;
     const char *how = std::getenv("MRX_OUT_ALLOC");
     int dev = 0;
     (void)hipGetDevice(&dev);
-    const hipError_t e = (how && how[0] == 'v') ? rgb.allocVmm(px, total - px * 4, dev) : rgb.alloc(px, total - px * 4);
+    auto own = [&](auto &buf) {
+        return (how && how[0] == 'v') ? buf.allocVmm(px, total - px * 4, dev) : buf.alloc(px, total - px * 4);
+    };
+    const hipError_t e = wantRgb ? own(rgb) : wantDepth ? own(depth) : own(ids);
     if (e != hipSuccess)
         return e;
-    char *base = static_cast<char *>(rgb.base);
-    depth.view(base + depthOff, px);
-    if (wantIds)
+    char *base = static_cast<char *>(wantRgb ? rgb.base : wantDepth ? depth.base : ids.base);
+    if (wantRgb && wantDepth)
+        depth.view(base + depthOff, px);
+    if (wantIds && (wantRgb || wantDepth))
         ids.view(base + idsOff, px);
     return hipSuccess;
 }
@@ -1338,7 +1349,8 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
         if (const char *dbg = std::getenv("MRX_OUT_PRE_MB"))
             if (pre.alloc((size_t)std::atoll(dbg) << 20) != hipSuccess)
                 (void)hipGetLastError();
-        MRX_HIP(allocOutputs(px, rt || (cfg.flags & MRX_FLAG_VISIBILITY_IDS), firstKindIsOneBlock(px), r.rgb, r.depth, r.ids));
+        MRX_HIP(allocOutputs(px, !(cfg.flags & MRX_FLAG_NO_RGB), !(cfg.flags & MRX_FLAG_NO_DEPTH),
+                             rt || (cfg.flags & MRX_FLAG_VISIBILITY_IDS), firstKindIsOneBlock(px), r.rgb, r.depth, r.ids));
         const char *hold = std::getenv("MRX_OUT_PRE_HOLD");
         if (!(hold && hold[0] == '1'))
             pre.release();
@@ -1511,7 +1523,7 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     inf.bvh_depth = blas.maxDepth;
     inf.max_world_instances = maxWorldInst;
     inf.num_shards = 1;
-    inf.bytes_per_step = (uint64_t)px * (wantIds ? 12u : 8u) +
+    inf.bytes_per_step = (uint64_t)px * (4u * ((r.rgb.ptr ? 1u : 0u) + (r.depth.ptr ? 1u : 0u)) + (wantIds ? 4u : 0u)) +
                          44ull * inf.num_instances + 28ull * nviews;
     return bindGeometry(r);
 }
@@ -1553,9 +1565,11 @@ int mrx_device_count(void)
 // MRX_PLACEMENT_TRIES=1 switches the search off.
 static int choosePlacement(mrx_renderer *r)
 {
-    const size_t px = r->rgb.count;
+    const bool wantRgb = r->rgb.ptr != nullptr, wantDepth = r->depth.ptr != nullptr;
     const bool wantIds = r->ids.ptr != nullptr;
-    const size_t bytes = px * 4 * (wantIds ? 3 : 2);
+    const size_t px = wantRgb ? r->rgb.count : r->depth.count;
+    // (keyed on the bytes actually allocated: an output that is not selected has no tensor)
+    const size_t bytes = px * 4 * ((wantRgb ? 1 : 0) + (wantDepth ? 1 : 0) + (wantIds ? 1 : 0));
     int maxTries = (bytes >= (256ull << 20) && bytes <= (16ull << 30)) ? 2 : 1;
     if (const char *dbg = std::getenv("MRX_PLACEMENT_TRIES"))
         maxTries = std::max(1, std::min(16, std::atoi(dbg)));
@@ -1623,7 +1637,7 @@ static int choosePlacement(mrx_renderer *r)
         if (sp.alloc((size_t)(2 * ((k * 37) % 64 + 1)) << 20) != hipSuccess)
             (void)hipGetLastError();
         Cand c;
-        const hipError_t ae = allocOutputs(px, wantIds, ((k & 1) == 0) == firstKindIsOneBlock(px),
+        const hipError_t ae = allocOutputs(px, wantRgb, wantDepth, wantIds, ((k & 1) == 0) == firstKindIsOneBlock(px),
                                            c.rgb, c.depth, c.ids);
         sp.release();
         if (ae != hipSuccess) {
@@ -1738,6 +1752,9 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
         return fail(MRX_E_INVALID, "raw geometry arrays are null while num_meshes is not zero");
     if (cfg->kernel_variant < 0 || cfg->kernel_variant >= mrx::kNumVariants)
         return fail(MRX_E_INVALID, "bad kernel_variant");
+    if ((cfg->flags & MRX_FLAG_NO_RGB) && (cfg->flags & MRX_FLAG_NO_DEPTH))
+        return fail(MRX_E_INVALID, "no output selected: MRX_FLAG_NO_RGB and MRX_FLAG_NO_DEPTH together leave "
+                                   "neither rgb nor depth to render");
     if (cfg->max_instances_per_world > (1u << 20))
         return fail(MRX_E_INVALID, "max_instances_per_world out of range");
     if (cfg->num_devices > 1 && !cfg->device_ids)
@@ -1975,10 +1992,18 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
     case MRX_BUF_RGB:       // mgr.cpp:547-568
         dims[0] = V; dims[1] = S; dims[2] = F; dims[3] = 4;
         *ndim = 4; *dtype = MRX_DTYPE_U8; ptr = r->rgb.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED, "rgb not rendered: this renderer was created depth-only (MRX_FLAG_NO_RGB)");
+            return nullptr;
+        }
         break;
     case MRX_BUF_DEPTH:     // mgr.cpp:570-590
         dims[0] = V; dims[1] = S; dims[2] = F; dims[3] = 1;
         *ndim = rt ? 3 : 4; *dtype = MRX_DTYPE_F32; ptr = r->depth.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED, "depth not rendered: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)");
+            return nullptr;
+        }
         break;
     case MRX_BUF_SEGMASK:   // mgr.cpp:592-605
         if (!rt) {

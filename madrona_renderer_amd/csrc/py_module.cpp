@@ -141,6 +141,12 @@ PYBIND11_MODULE(madrona_renderer, m)
     py::enum_<Manager::RenderMode>(m, "RenderMode")
         .value("Rasterizer", Manager::RenderMode::Rasterizer)
         .value("Raytracer", Manager::RenderMode::Raytracer);
+    // which outputs a step renders (not in the reference): rgb_tensor() / depth_tensor() of an
+    // output that is not rendered raise RuntimeError
+    py::enum_<Manager::RenderOutputs>(m, "RenderOutputs")
+        .value("RGBD", Manager::RenderOutputs::RGBD)
+        .value("Depth", Manager::RenderOutputs::Depth)
+        .value("RGB", Manager::RenderOutputs::RGB);
 
     py::class_<ImportedAsset>(m, "ImportedAsset")
         .def(py::init([](std::string path, int64_t mat_id) {
@@ -239,7 +245,8 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<ImportedInstance> &instances,
                          const std::vector<ImportedCamera> &cameras,
                          const std::vector<Sim::WorldInit> &worlds,
-                         const std::vector<int> &device_ids, int max_instances_per_world) {
+                         const std::vector<int> &device_ids, int max_instances_per_world,
+                         Manager::RenderOutputs render_outputs) {
                  if (mesh_vertices.size() && (mesh_vertices.ndim() != 2 || mesh_vertices.shape(1) != 3))
                      throw py::value_error("mesh_vertices must have shape [N, 3]");
                  if (mesh_uvs.size() && (mesh_uvs.ndim() != 2 || mesh_uvs.shape(1) != 2))
@@ -300,6 +307,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                  if (max_instances_per_world < 0)
                      throw py::value_error("max_instances_per_world must not be negative");
                  cfg.maxInstancesPerWorld = (uint32_t)max_instances_per_world;
+                 cfg.renderOutputs = render_outputs;
                  return new Manager(cfg);
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -311,8 +319,10 @@ PYBIND11_MODULE(madrona_renderer, m)
              py::arg("worlds"),
              // not in the reference (its callers never pass them): device_ids = [d0, d1, ...] makes this
              // one renderer span several devices (gpu_id is then ignored), max_instances_per_world
-             // reserves hidden, unbound rows per world (see refresh_objects)
-             py::arg("device_ids") = std::vector<int>(), py::arg("max_instances_per_world") = 0)
+             // reserves hidden, unbound rows per world (see refresh_objects), render_outputs renders only depth
+             // (RenderOutputs.Depth) or only rgb (RenderOutputs.RGB)
+             py::arg("device_ids") = std::vector<int>(), py::arg("max_instances_per_world") = 0,
+             py::arg("render_outputs") = Manager::RenderOutputs::RGBD)
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)

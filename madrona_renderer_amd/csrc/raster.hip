@@ -162,7 +162,8 @@ __device__ __forceinline__ void rasterBandBrute(const WaveLds &L, uint64_t valid
     }
 }
 
-template <bool IDS, bool MULTI>
+// OUT: output selection (raster.hpp OutSel: kOutRGBD, kOutDepth or kOutRGB)
+template <bool IDS, bool MULTI, int OUT = kOutRGBD>
 __global__ __launch_bounds__(kWave *kWavesPerBlock)
 void rasterBruteKernel(const RasterParams p)
 {
@@ -234,8 +235,10 @@ void rasterBruteKernel(const RasterParams p)
                 const bool hit = best[b] > p.invFar;
                 const float dep = hit ? 1.0f / best[b] : 0.0f;
                 const size_t o = ((size_t)t.view * p.nslow + fy) * p.nfast + fx;
-                p.rgb[o] = outRgba[b];
-                p.depth[o] = dep;
+                if (OUT != kOutDepth)
+                    p.rgb[o] = outRgba[b];
+                if (OUT != kOutRGB)
+                    p.depth[o] = dep;
                 if (IDS)
                     p.ids[o] = outId[b];
             }
@@ -376,18 +379,24 @@ __device__ __forceinline__ void outputRegion(const RasterParams &p, const TileCt
     if (fy >= p.nslow || (p.debugSkip & 1u))
         return;
     const size_t o = ((size_t)t.view * p.nslow + fy) * p.nfast + fx0;
+    // (output selection: a runtime guard on each tensor's stores)
+    const bool doRgb = storesRgb<kOutByPointer>(p.rgb), doDepth = storesDepth<kOutByPointer>(p.depth);
     if ((p.nfast & 3u) == 0 && fx0 + 3 < p.nfast) {
-        streamStore16(p.writeThrough, p.rgb + o, rgba[0], rgba[1], rgba[2], rgba[3]);
-        streamStore16(p.writeThrough, p.depth + o, __float_as_uint(dep[0]), __float_as_uint(dep[1]),
-                      __float_as_uint(dep[2]), __float_as_uint(dep[3]));
+        if (doRgb)
+            streamStore16(p.writeThrough, p.rgb + o, rgba[0], rgba[1], rgba[2], rgba[3]);
+        if (doDepth)
+            streamStore16(p.writeThrough, p.depth + o, __float_as_uint(dep[0]), __float_as_uint(dep[1]),
+                          __float_as_uint(dep[2]), __float_as_uint(dep[3]));
         if (IDS)
             streamStore16(p.writeThrough, p.ids + o, (uint32_t)id[0], (uint32_t)id[1], (uint32_t)id[2], (uint32_t)id[3]);
     } else {
 #pragma unroll
         for (int b = 0; b < kRegionBlocks; ++b) {
             if (fx0 + b < p.nfast) {
-                streamStore4(p.writeThrough, p.rgb + o + b, rgba[b]);
-                streamStore4(p.writeThrough, p.depth + o + b, __float_as_uint(dep[b]));
+                if (doRgb)
+                    streamStore4(p.writeThrough, p.rgb + o + b, rgba[b]);
+                if (doDepth)
+                    streamStore4(p.writeThrough, p.depth + o + b, __float_as_uint(dep[b]));
                 if (IDS)
                     streamStore4(p.writeThrough, p.ids + o + b, (uint32_t)id[b]);
             }
@@ -554,8 +563,9 @@ constexpr uint32_t kTileValid = 4u;
 // Shade + store one region of a tile (group kernel).  `bid` is the byte offset
 // of the winner's shading record (the background has its own record, so the
 // lookup is unconditional); base pointers are wave-uniform.
-template <bool IDS, bool FULL, bool TEX, typename LDS>
-__device__ __forceinline__ void storeRegion(const RasterParams &p, const LDS &L,
+// OUT: output selection (raster.hpp OutSel); doRgb / doDepth = storesRgb / storesDepth of the kernel.
+template <bool IDS, bool FULL, bool TEX, int OUT, typename LDS>
+__device__ __forceinline__ void storeRegion(const RasterParams &p, const LDS &L, bool doRgb, bool doDepth,
                                             uint32_t *rgbTile, float *depthTile, int32_t *idsTile,
                                             uint32_t pixOff, uint32_t fx0, uint32_t fy,
                                             bool anyTex, const float (&px)[kRegionBlocks], float py,
@@ -569,17 +579,20 @@ __device__ __forceinline__ void storeRegion(const RasterParams &p, const LDS &L,
 #pragma unroll
     for (int b = 0; b < kRegionBlocks; ++b) {
         const float *h = reinterpret_cast<const float *>(shadeBase + bid[b]);
-        rgba[b] = __float_as_uint(h[0]);
+        if (OUT != kOutDepth)
+            rgba[b] = __float_as_uint(h[0]);
         if (IDS)
             id[b] = __float_as_int(p.idsAreSegmask ? h[2] : h[3]);
         // depth = 1/best: v_rcp_f32 (<= 1 ulp); textured colour below uses the
         // correctly rounded quotient because texel choice depends on it
-        dep[b] = bid[b] != LDS::kBackground * 16 ? __builtin_amdgcn_rcpf(best[b]) : 0.0f;
+        if (OUT != kOutRGB)
+            dep[b] = bid[b] != LDS::kBackground * 16 ? __builtin_amdgcn_rcpf(best[b]) : 0.0f;
     }
     // TEX is a kernel-level switch: texel loads inside the work loop make the
     // compiler drain vmcnt at every loop header, which would also wait for the
-    // previous strip's stores
-    if (TEX && anyTex) {
+    // previous strip's stores -- and so is the output selection of the kernels that
+    // carry the shipped configurations: a depth-only instantiation has no texel load
+    if (TEX && OUT != kOutDepth && anyTex && (OUT != kOutByPointer || doRgb)) {
 #pragma unroll
         for (int b = 0; b < kRegionBlocks; ++b) {
             const int32_t rec = bid[b] >> 4;
@@ -591,17 +604,21 @@ __device__ __forceinline__ void storeRegion(const RasterParams &p, const LDS &L,
     if (p.debugSkip & 1u)
         return;
     if (FULL) {
-        streamStore16(p.writeThrough, rgbTile + pixOff, rgba[0], rgba[1], rgba[2], rgba[3]);
-        streamStore16(p.writeThrough, depthTile + pixOff, __float_as_uint(dep[0]), __float_as_uint(dep[1]),
-                      __float_as_uint(dep[2]), __float_as_uint(dep[3]));
+        if (doRgb)
+            streamStore16(p.writeThrough, rgbTile + pixOff, rgba[0], rgba[1], rgba[2], rgba[3]);
+        if (doDepth)
+            streamStore16(p.writeThrough, depthTile + pixOff, __float_as_uint(dep[0]), __float_as_uint(dep[1]),
+                          __float_as_uint(dep[2]), __float_as_uint(dep[3]));
         if (IDS)
             streamStore16(p.writeThrough, idsTile + pixOff, (uint32_t)id[0], (uint32_t)id[1], (uint32_t)id[2], (uint32_t)id[3]);
     } else if (fy < p.nslow) {
 #pragma unroll
         for (int b = 0; b < kRegionBlocks; ++b) {
             if (fx0 + b < p.nfast) {
-                streamStore4(p.writeThrough, rgbTile + pixOff + b, rgba[b]);
-                streamStore4(p.writeThrough, depthTile + pixOff + b, __float_as_uint(dep[b]));
+                if (doRgb)
+                    streamStore4(p.writeThrough, rgbTile + pixOff + b, rgba[b]);
+                if (doDepth)
+                    streamStore4(p.writeThrough, depthTile + pixOff + b, __float_as_uint(dep[b]));
                 if (IDS)
                     streamStore4(p.writeThrough, idsTile + pixOff + b, (uint32_t)id[b]);
             }
@@ -611,7 +628,7 @@ __device__ __forceinline__ void storeRegion(const RasterParams &p, const LDS &L,
 
 // A region no triangle can touch: background everywhere, no per-pixel work.
 template <bool IDS, bool FULL>
-__device__ __forceinline__ void storeBackground(const RasterParams &p, uint32_t *rgbTile,
+__device__ __forceinline__ void storeBackground(const RasterParams &p, bool doRgb, bool doDepth, uint32_t *rgbTile,
                                                 float *depthTile, int32_t *idsTile,
                                                 uint32_t pixOff, uint32_t fx0, uint32_t fy)
 {
@@ -619,16 +636,20 @@ __device__ __forceinline__ void storeBackground(const RasterParams &p, uint32_t 
         return;
     const uint32_t bg = 0xFF000000u;
     if (FULL) {
-        streamStore16(p.writeThrough, rgbTile + pixOff, bg, bg, bg, bg);
-        streamStore16(p.writeThrough, depthTile + pixOff, 0u, 0u, 0u, 0u);
+        if (doRgb)
+            streamStore16(p.writeThrough, rgbTile + pixOff, bg, bg, bg, bg);
+        if (doDepth)
+            streamStore16(p.writeThrough, depthTile + pixOff, 0u, 0u, 0u, 0u);
         if (IDS)
             streamStore16(p.writeThrough, idsTile + pixOff, ~0u, ~0u, ~0u, ~0u);
     } else if (fy < p.nslow) {
 #pragma unroll
         for (int b = 0; b < kRegionBlocks; ++b) {
             if (fx0 + b < p.nfast) {
-                streamStore4(p.writeThrough, rgbTile + pixOff + b, bg);
-                streamStore4(p.writeThrough, depthTile + pixOff + b, 0u);
+                if (doRgb)
+                    streamStore4(p.writeThrough, rgbTile + pixOff + b, bg);
+                if (doDepth)
+                    streamStore4(p.writeThrough, depthTile + pixOff + b, 0u);
                 if (IDS)
                     streamStore4(p.writeThrough, idsTile + pixOff + b, ~0u);
             }
@@ -660,7 +681,8 @@ constexpr int groupWaves(bool tex) { return tex ? 4 : 8; }
 // set-up waves' path to their first pose loads reads nothing but the twelve leading header arguments (GroupHeader,
 // raster.hpp), which the command processor preloads into SGPRs (-mllvm -amdgpu-kernarg-preload-count=12): the loads
 // go out without a round trip to the argument block; `p` is read for what comes after.
-template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST>
+// OUT (raster.hpp OutSel): the output selection of the instantiation.
+template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT>
 __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances,
                                                 uint32_t hPool, uint32_t hShape, uint32_t hGroups, uint32_t hPrefix,
                                                 uint32_t hFirst01, uint32_t hFirst23, const RasterParams p)
@@ -863,7 +885,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                     p.sx, p.ox, p.sz, p.oz, p.s6bPad, p.ambient, p.diffuse, p.transposed };
                 InstXform x;
                 instanceTransform(sa, vc, wt.inst, x);
-                valid = setupTriangleCore<true>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c, lds.shade[rec], lds.cold[rec]);
+                valid = setupTriangleCore<true, OUT != kOutDepth>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
+                                                                  lds.shade[rec], lds.cold[rec]);
             }
             MRX_STAMP(2);
             float4 *dst = reinterpret_cast<float4 *>(lds.planes[rec]);
@@ -938,6 +961,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     uint32_t *rgbTile = nullptr;
     float *depthTile = nullptr;
     int32_t *idsTile = nullptr;
+    const bool doRgb = storesRgb<OUT>(p.rgb), doDepth = storesDepth<OUT>(p.depth);
     for (;;) {
         uint32_t item = 0;
         if (lane == 0)
@@ -997,9 +1021,9 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             }
             if (!any) {
                 if (full)
-                    storeBackground<IDS, true>(p, rgbTile, depthTile, idsTile, pixOff, fx0, fy);
+                    storeBackground<IDS, true>(p, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy);
                 else
-                    storeBackground<IDS, false>(p, rgbTile, depthTile, idsTile, pixOff, fx0, fy);
+                    storeBackground<IDS, false>(p, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy);
                 continue;
             }
             const float (&px)[kRegionBlocks] = pxTile[hf];
@@ -1022,10 +1046,10 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                 }
             }
             if (full)
-                storeRegion<IDS, true, TEX>(p, lds, rgbTile, depthTile, idsTile, pixOff, fx0, fy,
+                storeRegion<IDS, true, TEX, OUT>(p, lds, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy,
                                             anyTex, px, py, best, bid);
             else
-                storeRegion<IDS, false, TEX>(p, lds, rgbTile, depthTile, idsTile, pixOff, fx0, fy,
+                storeRegion<IDS, false, TEX, OUT>(p, lds, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy,
                                              anyTex, px, py, best, bid);
         }
     }
@@ -1039,21 +1063,25 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
 
 // The two entry points of the body: the plain one (arguments = RasterParams, as every other kernel here) and the
 // FAST one with the preloaded header in front.
-template <bool IDS, int SLOTS, bool TEX, int XMODE = 0>
+// OUT: output selection (raster.hpp OutSel): kOutRGBD or kOutDepth fixed per instantiation; rgb only takes
+// kOutByPointer -- a runtime guard on the depth stores -- because a fixed rgb-only instantiation of the 128-slot
+// kernel spilled 20 VGPRs to scratch
+template <bool IDS, int SLOTS, bool TEX, int XMODE = 0, int OUT = kOutRGBD>
 // (the second bound is waves per SIMD; 256-slot groups are LDS-limited to 3 per CU)
 __global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : (SLOTS > 128 ? 6 : 8))
 void rasterGroupKernel(const RasterParams p)
 {
-    groupKernelBody<IDS, SLOTS, TEX, XMODE, false>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
+    groupKernelBody<IDS, SLOTS, TEX, XMODE, false, OUT>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
 }
 
-template <bool IDS, bool TEX, int XMODE>
+// OUT: output selection (raster.hpp OutSel: kOutRGBD, kOutDepth or kOutRGB), fixed per instantiation
+template <bool IDS, bool TEX, int XMODE, int OUT>
 __global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 8)
 void rasterGroupKernelFast(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
                            const RasterParams p)
 {
-    groupKernelBody<IDS, 16, TEX, XMODE, true>(hPose, hGeom, hViews, hInstances, hPool, hShape, hGroups, hPrefix, hFirst01,
+    groupKernelBody<IDS, 16, TEX, XMODE, true, OUT>(hPose, hGeom, hViews, hInstances, hPool, hShape, hGroups, hPrefix, hFirst01,
                                                hFirst23, p);
 }
 
@@ -1072,13 +1100,21 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
     if (variant == kVariantBrute) {
         // v1 reference: one wave per tile, every triangle at every pixel
         const dim3 grid((items + kWavesPerBlock - 1) / kWavesPerBlock);
-        if (ids) {
-            if (multi) rasterBruteKernel<true, true><<<grid, block, 0, stream>>>(p);
-            else       rasterBruteKernel<true, false><<<grid, block, 0, stream>>>(p);
-        } else {
-            if (multi) rasterBruteKernel<false, true><<<grid, block, 0, stream>>>(p);
-            else       rasterBruteKernel<false, false><<<grid, block, 0, stream>>>(p);
-        }
+#define MRX_BRUTE(O)                                                                     \
+    do {                                                                                 \
+        if (ids) {                                                                       \
+            if (multi) rasterBruteKernel<true, true, O><<<grid, block, 0, stream>>>(p);   \
+            else       rasterBruteKernel<true, false, O><<<grid, block, 0, stream>>>(p);  \
+        } else {                                                                         \
+            if (multi) rasterBruteKernel<false, true, O><<<grid, block, 0, stream>>>(p);  \
+            else       rasterBruteKernel<false, false, O><<<grid, block, 0, stream>>>(p); \
+        }                                                                                \
+    } while (0)
+        const OutSel out = outSelOf(p.rgb, p.depth);
+        if (out == kOutDepth)    MRX_BRUTE(kOutDepth);
+        else if (out == kOutRGB) MRX_BRUTE(kOutRGB);
+        else                     MRX_BRUTE(kOutRGBD);
+#undef MRX_BRUTE
     } else if (large) {
         // more triangles per world than the group kernel holds: one workgroup per tile
         if (ids) rasterChunkedKernel<true><<<dim3(items), block, 0, stream>>>(p);
@@ -1172,23 +1208,31 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
             h.first23 = p.uniFirstTri[2] | (p.uniFirstTri[3] << 16);
         }
 #define MRX_GROUP_ARGS h.pose, h.geom, h.views, h.instances, h.poolTris, h.shape, h.groups, h.prefix, h.first01, h.first23, q
-#define MRX_GROUP_X(S, X)                                                      \
+#define MRX_GROUP_O(S, X, O, OP)                                               \
     do {                                                                       \
         if (fast && S == 16) {                                                 \
             if (p.anyTextured) {                                               \
-                if (ids) rasterGroupKernelFast<true, true, X><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
-                else     rasterGroupKernelFast<false, true, X><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);  \
+                if (ids) rasterGroupKernelFast<true, true, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
+                else     rasterGroupKernelFast<false, true, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);  \
             } else {                                                           \
-                if (ids) rasterGroupKernelFast<true, false, X><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);  \
-                else     rasterGroupKernelFast<false, false, X><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); \
+                if (ids) rasterGroupKernelFast<true, false, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);  \
+                else     rasterGroupKernelFast<false, false, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); \
             }                                                                  \
         } else if (p.anyTextured) {                                            \
-            if (ids) rasterGroupKernel<true, S, true, X><<<grid, gblock, 0, stream>>>(q);   \
-            else     rasterGroupKernel<false, S, true, X><<<grid, gblock, 0, stream>>>(q);  \
+            if (ids) rasterGroupKernel<true, S, true, X, OP><<<grid, gblock, 0, stream>>>(q);   \
+            else     rasterGroupKernel<false, S, true, X, OP><<<grid, gblock, 0, stream>>>(q);  \
         } else {                                                               \
-            if (ids) rasterGroupKernel<true, S, false, X><<<grid, gblock, 0, stream>>>(q);  \
-            else     rasterGroupKernel<false, S, false, X><<<grid, gblock, 0, stream>>>(q); \
+            if (ids) rasterGroupKernel<true, S, false, X, OP><<<grid, gblock, 0, stream>>>(q);  \
+            else     rasterGroupKernel<false, S, false, X, OP><<<grid, gblock, 0, stream>>>(q); \
         }                                                                      \
+    } while (0)
+        // output selection: one instantiation per setting (kOutRGBD = the kernels as they always were)
+        const OutSel out = outSelOf(p.rgb, p.depth);
+#define MRX_GROUP_X(S, X)                                                      \
+    do {                                                                       \
+        if (out == kOutDepth)    MRX_GROUP_O(S, X, kOutDepth, kOutDepth);      \
+        else if (out == kOutRGB) MRX_GROUP_O(S, X, kOutRGB, kOutByPointer);    \
+        else                     MRX_GROUP_O(S, X, kOutRGBD, kOutRGBD);        \
     } while (0)
 #define MRX_GROUP(S) MRX_GROUP_X(S, 0)
         if (slots == 16) {
@@ -1205,6 +1249,7 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
         else MRX_GROUP(256);
 #undef MRX_GROUP_ARGS
 #undef MRX_GROUP_X
+#undef MRX_GROUP_O
 #undef MRX_GROUP
     }
     return hipGetLastError();

@@ -212,6 +212,21 @@ struct GroupHeader {
 // cross earlier -- from 65 triangles up to 640 views, from 91 up to 1024 untextured ones: mrx_api.cpp).
 constexpr uint32_t kBvhMinTris = 129;
 
+// Output selection (mrx_config.flags MRX_FLAG_NO_RGB / MRX_FLAG_NO_DEPTH).  The host passes a null pointer for an
+// output that is not selected.  The kernels that carry the shipped configurations (rasterGroupKernelFast, bvhFlatKernel)
+// take the setting as a template parameter and compile the unselected output's work out; the others take
+// kOutByPointer and skip the stores of a null output at run time.
+enum OutSel : int {
+    kOutRGBD = 0,       // rgb and depth
+    kOutDepth = 1,      // depth only: no colour set-up, no texel loads, no rgb stores
+    kOutRGB = 2,        // rgb only: no depth reciprocal, no depth stores
+    kOutByPointer = 3   // whatever pointers are not null (wave-uniform runtime guard)
+};
+inline OutSel outSelOf(const void *rgb, const void *depth)
+{
+    return !rgb ? kOutDepth : !depth ? kOutRGB : kOutRGBD;
+}
+
 // Kernel variants (mrx_config.kernel_variant).
 enum KernelVariant : int32_t {
     kVariantDefault = 0,     // group kernel up to kBvhMinTris-1 triangles per world, BVH above

@@ -17,6 +17,19 @@ constexpr int kWave = 64;
 constexpr int kCold = 12;        // dwords: u/v planes, lit colour
 constexpr int kRegionBlocks = 4; // a lane owns 4 consecutive pixels of a 32x8 region
 
+// Does a kernel instantiated for output selection OUT (raster.hpp OutSel) store rgb / depth?  Compile-time
+// constants for kOutRGBD / kOutDepth / kOutRGB; for kOutByPointer a wave-uniform test of the output pointer.
+template <int OUT>
+__device__ __forceinline__ bool storesRgb(const void *rgb)
+{
+    return OUT == kOutByPointer ? rgb != nullptr : OUT != kOutDepth;
+}
+template <int OUT>
+__device__ __forceinline__ bool storesDepth(const void *depth)
+{
+    return OUT == kOutByPointer ? depth != nullptr : OUT != kOutRGB;
+}
+
 // S2: every 3-term dot product is one rounded product and two fused steps
 __device__ __forceinline__ float dot3(float ax, float ay, float az,
                                       float bx, float by, float bz)
@@ -115,10 +128,12 @@ __device__ __forceinline__ void instanceTransform(const PARAMS &p, const ViewCon
 // |1/d| instead -- the caller derives them with uvPlanes() once it knows the
 // triangle needs a record, instead of carrying twelve registers through its
 // slot allocation.
+// COLOR = false (depth-only kernels): no colour work at all -- neither u/v planes nor the S7 lit
+// colour; shade[0] and cold[] are left unwritten, the rest of the record is as with COLOR = true.
 // PARAMS: RasterParams, or any struct with the members read here (tris, triMats, s6bPad, sx, sz,
 // ox, oz, transposed, diffuse, ambient) -- the BVH kernel passes a copy it reads from the
 // kernel-argument segment batch by batch instead of holding the values in scalar registers.
-template <bool UVPLANES = true, typename PARAMS = RasterParams>
+template <bool UVPLANES = true, bool COLOR = true, typename PARAMS = RasterParams>
 __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (&lv)[3],
                                                   const InstXform &x, uint32_t tri, int32_t obj,
                                                   int32_t kWorld, TriPlanes &out,
@@ -226,6 +241,12 @@ __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (
         out.Dx = tr ? az : ax;
         out.Dy = tr ? ax : az;
         out.Dc = __builtin_fmaf(nn[2], p.oz, __builtin_fmaf(nn[0], p.ox, nn[1])) * rd;
+    }
+    if (!COLOR) {
+        shade[1] = __int_as_float(tex);
+        shade[2] = obj >= 0 ? mc.w : __int_as_float(obj);
+        shade[3] = __int_as_float(kWorld);
+        return valid;
     }
     // u/v planes (S8) are only ever read for textured triangles
     if (!UVPLANES) {

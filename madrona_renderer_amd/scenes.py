@@ -227,11 +227,13 @@ def demo_scene(num_worlds=4, render_mode="Raytracer", width=64, height=64,
         worlds=[(2, 0, 1, 0)] * num_worlds)
 
 
-def make_renderer(desc, gpu_id=0, device_ids=None):
+def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
     """Instantiate the product renderer (compiled ``madrona_renderer`` module,
     HIP only) from a SceneDesc, with the reference's constructor kwargs.
     ``device_ids`` = [d0, d1, ...] makes the one renderer span several devices
-    (contiguous world ranges, one shard per listed device)."""
+    (contiguous world ranges, one shard per listed device).  ``render_outputs``
+    (a ``RenderOutputs`` member or its name: "RGBD", "Depth", "RGB"; None = RGBD)
+    selects the outputs a step renders."""
     from . import load_module
     m = load_module()
     extra = {}
@@ -239,6 +241,10 @@ def make_renderer(desc, gpu_id=0, device_ids=None):
         extra["device_ids"] = [int(d) for d in device_ids]
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
+    if render_outputs is not None:
+        if isinstance(render_outputs, str):
+            render_outputs = getattr(m.RenderOutputs, render_outputs)
+        extra["render_outputs"] = render_outputs
     return m.MadronaRenderer(
         gpu_id=gpu_id,
         num_worlds=desc.num_worlds,

@@ -1,0 +1,99 @@
+#!/usr/bin/env python3
+"""Kernel time of each output selection (RGBD, Depth, RGB: Manager::RenderOutputs) on the shapes
+that matter, one JSON line per (configuration, setting):
+
+  python scripts/bench_outputs.py [--rounds 5] [--budget-ms 30] [--only headline,c2,...]
+
+Every renderer of a configuration is created and warmed first; then the settings alternate within
+the process, `rounds` times, each measurement a batch of back-to-back renders between two events
+(time_renders) of about `budget-ms`.  Reported: the median and the spread (min / max) of the
+kernel us per render, views/s at the median, the algorithmic output bytes per view of the setting
+and the fraction of 8 TB/s they make at the median (bytes_per_step of the renderer: the tensors
+written plus the pose rows read).  bench.py is untouched: this is a measurement of its own.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+HBM_PEAK_GBPS = 8000.0
+SETTINGS = ("RGBD", "Depth", "RGB")
+
+
+def configs(scenes):
+    # (key, label, scene factory, kernel_variant)
+    return [
+        ("headline", "4096 worlds x 64x64 cube+plane (the headline)", lambda: scenes.synthetic_scene(4096), None),
+        ("c2", "1024 worlds x 64x64 cube+plane (BASELINE configs[1])", lambda: scenes.synthetic_scene(1024), None),
+        ("configs2", "4096 worlds x 128x128 cube+plane+wall (BASELINE configs[2])",
+         lambda: scenes.synthetic_scene(4096, width=128, height=128, with_wall=True), None),
+        ("configs4", "4096 worlds x 256x256 Raytracer, textured (BASELINE configs[4], default dispatch)",
+         lambda: scenes.synthetic_scene(4096, width=256, height=256, textured=True, render_mode="Raytracer"), None),
+        ("bvh482", "1024 worlds x 64x64, 40 cubes + plane = 482 triangles per world (BVH tile kernel)",
+         lambda: scenes.cube_field(1024, 40), None),
+    ]
+
+
+def make(scenes, factory, setting, variant):
+    if variant is not None:
+        os.environ["MADRONA_MI355_KERNEL"] = str(variant)
+    try:
+        return scenes.make_renderer(factory(), render_outputs=setting)
+    finally:
+        os.environ.pop("MADRONA_MI355_KERNEL", None)
+
+
+def us_per_render(r, steps):
+    return r.time_renders(steps) * 1000.0 / steps
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--budget-ms", type=float, default=30.0, help="device time of one measurement")
+    ap.add_argument("--only", default="", help="comma-separated configuration keys")
+    a = ap.parse_args(argv)
+    if a.rounds < 3:
+        ap.error("--rounds must be at least 3")
+    from madrona_renderer_amd import scenes
+    only = set(filter(None, a.only.split(",")))
+    for key, label, factory, variant in configs(scenes):
+        if only and key not in only:
+            continue
+        rs = {s: make(scenes, factory, s, variant) for s in SETTINGS}
+        views = factory().num_views
+        # warm every shape: clocks up, first launches (XCC report, cold caches) out of the way
+        steps = {}
+        for s, r in rs.items():
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < 0.2:
+                est = us_per_render(r, 20)
+            steps[s] = max(10, min(5000, int(a.budget_ms * 1000.0 / max(est, 1.0))))
+        times = {s: [] for s in SETTINGS}
+        for _ in range(a.rounds):
+            for s in SETTINGS:
+                times[s].append(us_per_render(rs[s], steps[s]))
+        base = statistics.median(times["RGBD"])
+        for s in SETTINGS:
+            med = statistics.median(times[s])
+            b = int(rs[s].bytes_per_step())
+            print(json.dumps({
+                "config": key, "workload": label, "setting": s, "render_path": rs[s].render_path(),
+                "views": views, "steps": steps[s], "rounds": a.rounds,
+                "kernel_us_median": round(med, 3), "kernel_us_min": round(min(times[s]), 3),
+                "kernel_us_max": round(max(times[s]), 3), "kernel_us_all": [round(t, 3) for t in times[s]],
+                "ratio_to_rgbd": round(med / base, 4),
+                "views_per_s": round(views / (med * 1e-6)),
+                "bytes_per_view": round(b / views, 1),
+                "frac_8tbps": round(b / (med * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4),
+            }), flush=True)
+        del rs
+
+
+if __name__ == "__main__":
+    main()
