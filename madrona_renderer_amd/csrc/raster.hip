@@ -556,8 +556,16 @@ struct GroupLds {
     uint32_t tileInfo[kGroupTilesMax][4];   // view, x0, y0, flags | first record << 8
     uint32_t nextItem;                  // (tile, strip) work counter of phase R
     uint8_t itemOrder[kGroupTilesMax * 8];  // work item -> tile * 8 + strip
+    // FAST untextured kernels (16 slots, one-tile views): S2 writes each work item in the form phase R consumes --
+    // x: surviving slots of the strip's left half (bits 0..15) and right half (16..31),
+    // y: tile | strip << 4 | kItem* flags -- at its place in the work order (itemPos: tile * 8 + strip -> item)
+    uint2 items[SLOTS == 16 ? kGroupTilesMax * 8 : 1];
+    uint8_t itemPos[SLOTS == 16 ? kGroupTilesMax * 8 : 1];
 };
 constexpr uint32_t kTileValid = 4u;
+constexpr uint32_t kItemValid = 1u << 8;      // the tile's view is part of the batch
+constexpr uint32_t kItemNearFree = 1u << 9;   // every surviving slot stays behind the near plane over the strip
+constexpr uint32_t kItemAnyTex = 1u << 10;    // a surviving slot of the strip is textured
 
 
 // Shade + store one region of a tile (group kernel).  `bid` is the byte offset
@@ -657,6 +665,38 @@ __device__ __forceinline__ void storeBackground(const RasterParams &p, bool doRg
     }
 }
 
+// S2 of the group kernel for one (tile j, triangle slot k) pair: the region bits of the wave's two strips
+// (bit 2 * strip + half), whether the triangle stays behind the near plane over them and whether it is
+// textured; nothing for a dead slot or a view past the end of the batch.
+template <typename LDS>
+__device__ __forceinline__ uint32_t classifyPair(const LDS &L, int j, int k, int wave, float invNear, float invFar,
+                                                 bool &nearOk, bool &tex)
+{
+    nearOk = false;
+    tex = false;
+    const uint32_t info = L.tileInfo[j][3];
+    const int rec = (int)(info >> 8) + k;
+    if (!(info & kTileValid) || !L.live[rec])
+        return 0u;
+    const float4 *src = reinterpret_cast<const float4 *>(L.planes[rec]);
+    const float4 a = src[0], b = src[1], cc = src[2], bb = src[3];
+    TriPlanes c;
+    c.A0 = a.x; c.A1 = a.y; c.A2 = a.z; c.Dx = a.w;
+    c.B0 = b.x; c.B1 = b.y; c.B2 = b.z; c.Dy = b.w;
+    c.C0 = cc.x; c.C1 = cc.y; c.C2 = cc.z; c.Dc = cc.w;
+    c.bbX0 = bb.x; c.bbX1 = bb.y; c.bbY0 = bb.z; c.bbY1 = bb.w;
+    const uint32_t tx0 = L.tileInfo[j][1], ty0 = L.tileInfo[j][2];
+    uint32_t m;
+    switch (wave & 3) {
+    case 0: m = classifyStrips<0, 2>(c, tx0, ty0, invNear, invFar, nearOk); break;
+    case 1: m = classifyStrips<2, 4>(c, tx0, ty0, invNear, invFar, nearOk); break;
+    case 2: m = classifyStrips<4, 6>(c, tx0, ty0, invNear, invFar, nearOk); break;
+    default: m = classifyStrips<6, 8>(c, tx0, ty0, invNear, invFar, nearOk); break;
+    }
+    tex = __float_as_int(L.shade[rec][1]) >= 0;
+    return m;
+}
+
 // What the group kernel's set-up reads per triangle (instanceTransform / setupTriangleCore are templates over
 // the parameter type): pointers from the preloaded header or from RasterParams, scalars from RasterParams.
 struct GroupSetupArgs {
@@ -712,6 +752,10 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     const float *aCamPos = FAST ? reinterpret_cast<const float *>(hPose + lay.camPos) : p.camPos;
     const int32_t *aInstObj = FAST ? reinterpret_cast<const int32_t *>(hPose + lay.instObj) : p.instObj;
     const uint32_t tilesPerView = FAST ? 1u : p.tilesFast * p.tilesSlow;
+    // FAST, untextured (16 slots, one-tile views): S2 hands phase R ready-made work items (GroupLds::items).
+    // The plain entry and the textured kernels keep the per-tile masks: measured slower with the items
+    //  -- the plain entry carries both loops, the textured one lost its register budget.
+    constexpr bool readyItems = FAST && !TEX;
     // ---- which views / tiles this workgroup owns (launchRaster):
     //  A  grpPerView == 1: grpViews whole views (all their tiles);
     //  B  otherwise: grpChunkTiles tiles of one view.
@@ -777,8 +821,9 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             stamps[i] = __builtin_amdgcn_s_memrealtime();                      \
     } while (0)
     MRX_STAMP(0);
-    for (int i = threadIdx.x; i < numPairs; i += groupWaves(TEX) * kWave)
-        lds.masks[i] = 0u;
+    if (!readyItems)
+        for (int i = threadIdx.x; i < numPairs; i += groupWaves(TEX) * kWave)
+            lds.masks[i] = 0u;
 
     // ---- S1: one lane per (view vi of the group, triangle slot k): setup.
     //      Wave 0 covers the first 64 records, wave 1 a fifth 16-slot view or
@@ -812,8 +857,13 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             const uint32_t g = tile * 8u + strip;
             const bool ok = strip < 8u && g >= firstStrip && g < firstStrip + numStrips;
             const uint64_t m = __ballot(ok);
-            if (ok)
-                lds.itemOrder[base + __builtin_popcountll(m & ((1ull << lane) - 1ull))] = (uint8_t)g;
+            const uint32_t pos = base + __builtin_popcountll(m & ((1ull << lane) - 1ull));
+            if (readyItems) {
+                if (strip < 8u)                   // every (tile, strip) of the group: its item, or none
+                    lds.itemPos[g] = ok ? (uint8_t)pos : (uint8_t)0xFF;
+            } else if (ok) {
+                lds.itemOrder[pos] = (uint8_t)g;
+            }
             base += (uint32_t)__builtin_popcountll(m);
         }
     }
@@ -912,31 +962,42 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     //      (four regions) of the pairs (w>>2)*64 + lane, + 64 * (waves / 4), ...;
     //      results are OR-ed in LDS: bits 0..15 regions, bits 16..19
     //      "near-free over this wave's strips".
+    //      readyItems: a pass of a wave covers four whole tiles (lane = 16 * tile + slot), so the
+    //      wave assembles its strips' work items (GroupLds::items) by ballot instead.
     constexpr int kPairStride = (groupWaves(TEX) / 4) * kWave;
     for (int pair = (wave >> 2) * kWave + lane; pair - lane < numPairs; pair += kPairStride) {
+        if (readyItems) {
+            uint32_t m = 0;
+            bool nearOk = false, tex = false;
+            if (pair < numPairs)
+                m = classifyPair(lds, pair / SLOTS, pair % SLOTS, wave, invNear, invFar, nearOk, tex);
+            m >>= 4 * (wave & 3);                 // bit 2i + hf: strip 2 (wave & 3) + i, half hf
+            const uint64_t l0 = __ballot(m & 1u), r0 = __ballot(m & 2u), l1 = __ballot(m & 4u), r1 = __ballot(m & 8u);
+            const uint64_t near0 = __ballot((m & 3u) && !nearOk), near1 = __ballot((m & 12u) && !nearOk);
+            const uint64_t tex0 = __ballot((m & 3u) && tex), tex1 = __ballot((m & 12u) && tex);
+            if (lane % 16 == 0 && pair < numPairs) {
+                // lane 16 t: tile j = pair / 16, its slots are bits 16 t .. 16 t + 15 of the ballots
+                const uint32_t j = (uint32_t)pair / 16u;
+                const uint32_t valid = firstView + j < aNumViews ? kItemValid : 0u;
+                const auto put = [&](uint32_t strip, uint64_t l, uint64_t r, uint64_t nearHit, uint64_t texHit) {
+                    const uint32_t pos = lds.itemPos[j * 8u + strip];
+                    if (pos == 0xFFu)
+                        return;                   // left to the other workgroup of the pair (XCD-aware split)
+                    const uint32_t desc = j | strip << 4 | valid |
+                                          (((nearHit >> lane) & 0xFFFFu) == 0 ? kItemNearFree : 0u) |
+                                          (((texHit >> lane) & 0xFFFFu) != 0 ? kItemAnyTex : 0u);
+                    lds.items[pos] = make_uint2((uint32_t)((l >> lane) & 0xFFFFu) | (uint32_t)((r >> lane) & 0xFFFFu) << 16,
+                                                desc);
+                };
+                put(2u * (wave & 3), l0, r0, near0, tex0);
+                put(2u * (wave & 3) + 1u, l1, r1, near1, tex1);
+            }
+            continue;
+        }
         if (pair >= numPairs)
             continue;
-        const int j = pair / SLOTS, k = pair % SLOTS;
-        const uint32_t info = lds.tileInfo[j][3];
-        const int rec = (int)(info >> 8) + k;
-        if (!(info & kTileValid) || !lds.live[rec])
-            continue;
-        const float4 *src = reinterpret_cast<const float4 *>(lds.planes[rec]);
-        const float4 a = src[0], b = src[1], cc = src[2], bb = src[3];
-        TriPlanes c;
-        c.A0 = a.x; c.A1 = a.y; c.A2 = a.z; c.Dx = a.w;
-        c.B0 = b.x; c.B1 = b.y; c.B2 = b.z; c.Dy = b.w;
-        c.C0 = cc.x; c.C1 = cc.y; c.C2 = cc.z; c.Dc = cc.w;
-        c.bbX0 = bb.x; c.bbX1 = bb.y; c.bbY0 = bb.z; c.bbY1 = bb.w;
-        const uint32_t tx0 = lds.tileInfo[j][1], ty0 = lds.tileInfo[j][2];
-        bool nearOk = false;
-        uint32_t m;
-        switch (wave & 3) {
-        case 0: m = classifyStrips<0, 2>(c, tx0, ty0, invNear, invFar, nearOk); break;
-        case 1: m = classifyStrips<2, 4>(c, tx0, ty0, invNear, invFar, nearOk); break;
-        case 2: m = classifyStrips<4, 6>(c, tx0, ty0, invNear, invFar, nearOk); break;
-        default: m = classifyStrips<6, 8>(c, tx0, ty0, invNear, invFar, nearOk); break;
-        }
+        bool nearOk, tex;
+        uint32_t m = classifyPair(lds, pair / SLOTS, pair % SLOTS, wave, invNear, invFar, nearOk, tex);
         if (nearOk)
             m |= 1u << (16 + (wave & 3));
         if (m)
@@ -962,6 +1023,16 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     float *depthTile = nullptr;
     int32_t *idsTile = nullptr;
     const bool doRgb = storesRgb<OUT>(p.rgb), doDepth = storesDepth<OUT>(p.depth);
+    uint32_t itemMasks = 0;     // readyItems: the item's surviving slots, left half bits 0..15, right half 16..31
+    if (readyItems) {
+        // the tile of a one-tile view sits at the view's origin: what depends on the tile origin is set once
+        full = (p.nfast & 3u) == 0 && 64u <= p.nfast && 64u <= p.nslow;
+#pragma unroll
+        for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+            for (int b = 0; b < kRegionBlocks; ++b)
+                pxTile[hf][b] = (float)(hf * 32 + 4 * lx + b);
+    }
     for (;;) {
         uint32_t item = 0;
         if (lane == 0)
@@ -969,41 +1040,61 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
         item = __builtin_amdgcn_readfirstlane(item);
         if (item >= numStrips)
             break;
-        item = __builtin_amdgcn_readfirstlane((uint32_t)lds.itemOrder[item]);
-        const int j = (int)(item >> 3), strip = (int)(item & 7u);
-        if (j != cachedTile) {
-            const uint32_t info = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][3]);
-            if (!(info & kTileValid))
+        int j, strip;
+        if (readyItems) {
+            // one ticket, one 8-byte read: the item is ready to go
+            const uint2 d = lds.items[item];
+            itemMasks = __builtin_amdgcn_readfirstlane(d.x);
+            const uint32_t desc = __builtin_amdgcn_readfirstlane(d.y);
+            if (!(desc & kItemValid))
                 continue;                           // a view past the end of the batch
-            cachedTile = j;
-            recBase = (int)(info >> 8);
-            view = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][0]);
-            tileX0 = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][1]);
-            tileY0 = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][2]);
-            const size_t tileBase = ((size_t)view * p.nslow + tileY0) * p.nfast + tileX0;
+            j = (int)(desc & 15u);
+            strip = (int)((desc >> 4) & 7u);
+            nearFree = (desc & kItemNearFree) != 0;
+            anyTex = (desc & kItemAnyTex) != 0;
+            recBase = j * SLOTS;
+            const size_t tileBase = (size_t)(firstView + (uint32_t)j) * p.nslow * p.nfast;
             rgbTile = p.rgb + tileBase;
             depthTile = p.depth + tileBase;
             idsTile = IDS ? p.ids + tileBase : nullptr;
-            full = (p.nfast & 3u) == 0 && tileX0 + 64u <= p.nfast && tileY0 + 64u <= p.nslow;
-            // lane k looks at the region masks of triangle slots k, 64 + k, ... of tile j
-            anyTex = false;
-            nearFree = true;
+        } else {
+            item = __builtin_amdgcn_readfirstlane((uint32_t)lds.itemOrder[item]);
+            j = (int)(item >> 3);
+            strip = (int)(item & 7u);
+            if (j != cachedTile) {
+                const uint32_t info = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][3]);
+                if (!(info & kTileValid))
+                    continue;                           // a view past the end of the batch
+                cachedTile = j;
+                recBase = (int)(info >> 8);
+                view = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][0]);
+                tileX0 = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][1]);
+                tileY0 = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][2]);
+                const size_t tileBase = ((size_t)view * p.nslow + tileY0) * p.nfast + tileX0;
+                rgbTile = p.rgb + tileBase;
+                depthTile = p.depth + tileBase;
+                idsTile = IDS ? p.ids + tileBase : nullptr;
+                full = (p.nfast & 3u) == 0 && tileX0 + 64u <= p.nfast && tileY0 + 64u <= p.nslow;
+                // lane k looks at the region masks of triangle slots k, 64 + k, ... of tile j
+                anyTex = false;
+                nearFree = true;
 #pragma unroll
-            for (int sub = 0; sub < SUBS; ++sub) {
-                const int slot = sub * kWave + lane;
-                mask[sub] = lane < LANES ? lds.masks[j * SLOTS + slot] : 0u;
-                const int32_t tex = lane < LANES ? __float_as_int(lds.shade[recBase + slot][1]) : -1;
-                anyTex = anyTex || __ballot((mask[sub] & 0xFFFFu) != 0 && tex >= 0) != 0;
-                // every surviving triangle stays behind the near plane over the
-                // whole tile: the per-pixel near test is dropped for the tile
-                nearFree = nearFree &&
-                           __ballot((mask[sub] & 0xFFFFu) != 0 && ((mask[sub] >> 16) & 0xFu) != 0xFu) == 0;
+                for (int sub = 0; sub < SUBS; ++sub) {
+                    const int slot = sub * kWave + lane;
+                    mask[sub] = lane < LANES ? lds.masks[j * SLOTS + slot] : 0u;
+                    const int32_t tex = lane < LANES ? __float_as_int(lds.shade[recBase + slot][1]) : -1;
+                    anyTex = anyTex || __ballot((mask[sub] & 0xFFFFu) != 0 && tex >= 0) != 0;
+                    // every surviving triangle stays behind the near plane over the
+                    // whole tile: the per-pixel near test is dropped for the tile
+                    nearFree = nearFree &&
+                               __ballot((mask[sub] & 0xFFFFu) != 0 && ((mask[sub] >> 16) & 0xFu) != 0xFu) == 0;
+                }
+#pragma unroll
+                for (int hf = 0; hf < 2; ++hf)
+#pragma unroll
+                    for (int b = 0; b < kRegionBlocks; ++b)
+                        pxTile[hf][b] = (float)(tileX0 + hf * 32 + 4 * lx + b);
             }
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf)
-#pragma unroll
-                for (int b = 0; b < kRegionBlocks; ++b)
-                    pxTile[hf][b] = (float)(tileX0 + hf * 32 + 4 * lx + b);
         }
         const uint32_t fy = tileY0 + strip * 8 + ly;
         const float py = (float)fy;
@@ -1016,7 +1107,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             bool any = false;
 #pragma unroll
             for (int sub = 0; sub < SUBS; ++sub) {
-                act[sub] = __ballot((mask[sub] >> (2 * strip + hf)) & 1u);
+                act[sub] = readyItems ? (uint64_t)((itemMasks >> (16 * hf)) & 0xFFFFu)
+                                     : __ballot((mask[sub] >> (2 * strip + hf)) & 1u);
                 any = any || act[sub] != 0;
             }
             if (!any) {
