@@ -129,6 +129,9 @@ public:
     void setStream(void *hipStream);                // launch on this stream from now on
     void setShardStream(uint32_t shard, void *hipStream);   // the same for one shard of several
     const char *renderPath() const;                 // "raster" (tiled raster kernels) or "bvh"
+    // the kernel the last render launched (mrx_raster_entry): "group-fast", "group", "chunked", "brute",
+    // "bvh", or "none" before the first render
+    const char *rasterEntry() const;
 
     uint32_t numAgents;
 

@@ -254,6 +254,15 @@ int64_t mrx_shard_split(uint32_t num_worlds, uint32_t shard, uint32_t num_shards
  *    it, whatever the caller was compiled against; mrx_info_sized(r, &info, sizeof info) writes
  *    min(size, sizeof(mrx_info_t)) bytes, so a caller gets exactly the fields it knows (ABI 4).
  *    The struct only ever grows at its end. */
+/* -- which kernel the last render launched, as the host picked it: MRX_ENTRY_NONE before the first render
+ *    (mrx_create renders once), then one of the raster entries -- the group kernel's FAST instantiations, the
+ *    group kernel, the chunked kernel, the brute-force kernel -- or the BVH path.  A renderer that spans several
+ *    devices reports its first shard's; MRX_E_INVALID for a null renderer. */
+enum {
+    MRX_ENTRY_NONE = 0, MRX_ENTRY_GROUP_FAST = 1, MRX_ENTRY_GROUP = 2, MRX_ENTRY_CHUNKED = 3,
+    MRX_ENTRY_BRUTE = 4, MRX_ENTRY_BVH = 5
+};
+int mrx_raster_entry(mrx_renderer *r);
 int mrx_info(mrx_renderer *r, mrx_info_t *out);
 int mrx_info_sized(mrx_renderer *r, void *out, size_t size);
 void *mrx_stream(mrx_renderer *r);

@@ -232,6 +232,15 @@ const char *Manager::renderPath() const
     return info.render_path == 1 ? "bvh" : "raster";
 }
 
+const char *Manager::rasterEntry() const
+{
+    static const char *const names[] = {"none", "group-fast", "group", "chunked", "brute", "bvh"};
+    const int e = mrx_raster_entry(impl_->r);
+    if (e < 0 || e >= (int)(sizeof names / sizeof names[0]))
+        detail::fatal(mrx_last_error());
+    return names[e];
+}
+
 void Manager::setStream(void *hipStream)
 {
     if (mrx_set_stream(impl_->r, hipStream) != MRX_OK)

@@ -279,6 +279,7 @@ struct mrx_renderer {
     DevBuf<uint32_t> bvhLeafTris, worldInstStart, viewWorld, instKBase;
     DevBuf<mrx::ObjInfo> objInfo;
     bool useBvh = false;
+    int32_t lastEntry = mrx::kEntryNone;        // the kernel the last launch() ran (mrx_raster_entry)
     // host copies the geometry binding is (re)built from (bindGeometry): the object each
     // instance row is bound to, the world -> row and view -> world tables, the BLAS set
     std::vector<int32_t> boundObj;
@@ -318,9 +319,11 @@ struct mrx_renderer {
         // every 32nd -- the phase of a queue changes rarely)
         ++launches;
         params.xccReport = (xccDev && (launches <= 4 || (launches & 31u) == 0)) ? xccDev : nullptr;
-        if (useBvh)
+        if (useBvh) {
+            lastEntry = mrx::kEntryBvh;
             return mrx::launchBvh(params, stream);
-        return mrx::launchRaster(params, info.max_world_triangles, variant, stream);
+        }
+        return mrx::launchRaster(params, info.max_world_triangles, variant, stream, &lastEntry);
     }
 
     ~mrx_renderer()
@@ -1873,6 +1876,18 @@ static int wantsShard(const char *what)
 {
     return fail(MRX_E_UNSUPPORTED, std::string(what) + ": this renderer spans several devices -- "
                                    "address one shard (mrx_shard / mrx_buffer_shard)");
+}
+
+static_assert(mrx::kEntryNone == MRX_ENTRY_NONE && mrx::kEntryGroupFast == MRX_ENTRY_GROUP_FAST &&
+                  mrx::kEntryGroup == MRX_ENTRY_GROUP && mrx::kEntryChunked == MRX_ENTRY_CHUNKED &&
+                  mrx::kEntryBrute == MRX_ENTRY_BRUTE && mrx::kEntryBvh == MRX_ENTRY_BVH,
+              "raster.hpp RasterEntry and mrx.h MRX_ENTRY_* disagree");
+
+int mrx_raster_entry(mrx_renderer *r)
+{
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    return r->shards.empty() ? r->lastEntry : r->shards[0]->lastEntry;
 }
 
 int mrx_num_shards(mrx_renderer *r) { return !r ? 0 : r->shards.empty() ? 1 : (int)r->shards.size(); }

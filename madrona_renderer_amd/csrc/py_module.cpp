@@ -384,6 +384,7 @@ PYBIND11_MODULE(madrona_renderer, m)
         .def("elapsed_ms", &Manager::elapsedMs)
         .def("bytes_per_step", &Manager::bytesPerStep)
         .def("render_path", [](Manager &self) { return std::string(self.renderPath()); })
+        .def("raster_entry", [](Manager &self) { return std::string(self.rasterEntry()); })
         .def("placement",
              [](Manager &self) {
                  float us[16] = {}, kept = 0.f;

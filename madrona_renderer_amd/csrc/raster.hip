@@ -1180,7 +1180,7 @@ void rasterGroupKernelFast(const char *hPose, const char *hGeom, uint32_t hViews
 }  // namespace
 
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
-                        int32_t variant, hipStream_t stream)
+                        int32_t variant, hipStream_t stream, int32_t *entry)
 {
     const uint32_t items = p.numViews * p.tilesFast * p.tilesSlow;
     if (items == 0)
@@ -1191,6 +1191,7 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
     const bool large = maxWorldTris > (uint32_t)kGroupSlotsMax;
     if (variant == kVariantBrute) {
         // v1 reference: one wave per tile, every triangle at every pixel
+        if (entry) *entry = kEntryBrute;
         const dim3 grid((items + kWavesPerBlock - 1) / kWavesPerBlock);
 #define MRX_BRUTE(O)                                                                     \
     do {                                                                                 \
@@ -1209,6 +1210,7 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
 #undef MRX_BRUTE
     } else if (large) {
         // more triangles per world than the group kernel holds: one workgroup per tile
+        if (entry) *entry = kEntryChunked;
         if (ids) rasterChunkedKernel<true><<<dim3(items), block, 0, stream>>>(p);
         else     rasterChunkedKernel<false><<<dim3(items), block, 0, stream>>>(p);
     } else {
@@ -1293,6 +1295,7 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
             fast = p.uniFirstTri[i] < 65536u;
         if (const char *dbg = std::getenv("MRX_GROUP_FAST"))      // 0: never (A/B and tests)
             fast = fast && std::atoi(dbg) != 0;
+        if (entry) *entry = fast ? kEntryGroupFast : kEntryGroup;
         if (fast) {
             h.shape = vg | (q.xcdSkew << 8) | (q.xcdRotate << 12) | (p.uniInstances << 13) | (p.uniCamsPerWorld << 16) | (1u << 31);
             h.prefix = p.uniPrefix[1] | (p.uniPrefix[2] << 8) | (p.uniPrefix[3] << 16) | (p.uniPrefix[4] << 24);

@@ -274,8 +274,13 @@ inline bool bvhDispatchFlat(bool raytracer, uint32_t numViews, uint32_t nfast, u
            (uint64_t)numViews * tpv >= 192ull * cus;
 }
 
+// Which kernel a launch ran (mrx_raster_entry; the values are include/mrx.h's MRX_ENTRY_*): launchRaster writes
+// the raster entry it picked to *entry, host side; no kernel sees it.
+enum RasterEntry : int32_t {
+    kEntryNone = 0, kEntryGroupFast = 1, kEntryGroup = 2, kEntryChunked = 3, kEntryBrute = 4, kEntryBvh = 5,
+};
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
-                        int32_t variant, hipStream_t stream);
+                        int32_t variant, hipStream_t stream, int32_t *entry = nullptr);
 
 // BVH path: per-step TLAS in LDS, wave-packet traversal of TLAS + BLAS,
 // exact S6 leaf test (bvh.hip).  p.bvhPassInst is filled in by the caller.

@@ -1,7 +1,7 @@
 """Output selection on the MI355X (-m gpu): a renderer created depth-only or rgb-only stores, in the
 output it renders, exactly the bytes an RGBD renderer of the same scene and poses stores -- and
 visibility ids / segmask as well -- and that output meets the oracle at the parity bar (RGBA8
-equal, depth rtol 1e-4).  The output it does not render has no tensor."""
+equal, depth within 1 ulp and rtol 1e-4).  The output it does not render has no tensor."""
 import ctypes
 import dataclasses
 import os
@@ -12,7 +12,7 @@ import pytest
 from madrona_renderer_amd import scenes
 from tests import meshes as tmeshes
 from tests.test_output_select_cpu import MRX_FLAG_NO_DEPTH, MRX_FLAG_NO_RGB, small_config
-from tests.util import render_oracle
+from tests.util import depth_ulps, render_oracle
 
 pytestmark = pytest.mark.gpu
 
@@ -71,6 +71,8 @@ def _against_oracle(sel, desc, outputs, visibility, raytracer, views=None):
     if outputs == "Depth":
         d = _t(sel.depth_tensor())[:n].cpu().numpy().reshape(ref["depth"][:n].shape)
         np.testing.assert_allclose(d, ref["depth"][:n], rtol=1e-4, atol=0)
+        ulps = depth_ulps(d, ref["depth"][:n])
+        assert ulps <= 1, f"depth differs by {ulps} ulp"
     else:
         rgb = _t(sel.rgb_tensor())[:n].cpu().numpy()
         bad = int((rgb != ref["rgb"][:n]).any(axis=-1).sum())

@@ -38,8 +38,28 @@ def fetch(r, visibility=True, raytracer=False):
     return out
 
 
-def assert_parity(got, ref, depth_rtol=1e-4):
-    """Bit-exact visibility and colour; depth within the north star's 1e-4."""
+def depth_ulps(got, ref):
+    """Largest distance in float32 ulps between two depth buffers: background (0) must be exactly 0 in both,
+    covered pixels nonzero of the same sign; the distance is that of their int32 bit patterns."""
+    got = np.ascontiguousarray(got, np.float32)
+    ref = np.ascontiguousarray(ref, np.float32)
+    assert got.shape == ref.shape
+    bg_got, bg_ref = got == 0, ref == 0
+    bad = int((bg_got != bg_ref).sum())
+    assert bad == 0, f"{bad} pixels differ in background / covered depth"
+    cov = ~bg_ref
+    bad = int((np.signbit(got[cov]) != np.signbit(ref[cov])).sum())
+    assert bad == 0, f"{bad} depth values differ in sign"
+    if not cov.any():
+        return 0
+    gi = got[cov].view(np.int32).astype(np.int64)
+    ri = ref[cov].view(np.int32).astype(np.int64)
+    return int(np.abs(gi - ri).max())
+
+
+def assert_parity(got, ref, depth_rtol=1e-4, depth_ulp=1):
+    """Bit-exact visibility and colour; depth within `depth_ulp` float32 ulps of the oracle (DESIGN.md section 3:
+    1/best through v_rcp_f32) and within the north star's 1e-4."""
     if "tri_id" in got:
         bad = int((got["tri_id"] != ref["tri_id"]).sum())
         assert bad == 0, f"{bad} pixels differ in visibility"
@@ -50,6 +70,8 @@ def assert_parity(got, ref, depth_rtol=1e-4):
     assert bad == 0, f"{bad} pixels differ in colour"
     assert got["depth"].shape == ref["depth"].shape
     np.testing.assert_allclose(got["depth"], ref["depth"], rtol=depth_rtol, atol=0)
+    ulps = depth_ulps(got["depth"], ref["depth"])
+    assert ulps <= depth_ulp, f"depth differs by {ulps} ulp (bound {depth_ulp})"
 
 
 def digest(arr):
