@@ -263,6 +263,30 @@ enum {
     MRX_ENTRY_BRUTE = 4, MRX_ENTRY_BVH = 5
 };
 int mrx_raster_entry(mrx_renderer *r);
+/* -- the BVH path's launch shape as the host chose it for the bound geometry (mrx_create, mrx_refresh_objects):
+ *    what the next BVH render launches.  kernel is MRX_BVH_KERNEL_NONE when the raster kernels render; the other
+ *    fields are filled in all the same.  The flat kernel has no record table or large-triangle list (their caps
+ *    read 0).  A renderer that spans several devices reports its first shard's; MRX_E_INVALID for a null
+ *    renderer or output. */
+enum { MRX_BVH_KERNEL_NONE = 0, MRX_BVH_KERNEL_TILE = 1, MRX_BVH_KERNEL_FLAT = 2 };
+typedef struct {
+    int32_t kernel;            /* MRX_BVH_KERNEL_* */
+    uint32_t tile_w, tile_h;   /* pixels of a workgroup's tile, over the storage axes (fast, slow) */
+    uint32_t classify;         /* the instantiation that classifies listed large triangles per strip */
+    uint32_t textured;         /* the textured instantiation (48-byte records) */
+    uint32_t record_cap;       /* records a round's table holds: textured tex_cap, else 512 / 768 / 1024 */
+    uint32_t record_usable;    /* of them usable before the round ends (slot 1023 marks stashed pixels) */
+    uint32_t tex_cap;          /* records of a textured round (bvhTexCap, 64 ... 1008) */
+    uint32_t big_cap;          /* large-triangle list entries per round (64, 96 with classify) */
+    uint32_t pass_inst;        /* TLAS instances per pass */
+    uint32_t group_views;      /* views per workgroup: 1, 2, 4 or 8 */
+    uint32_t mixed;            /* pairs and single views in one launch (group_views = 2) */
+    uint32_t priority;         /* wave-priority mode of the younger workgroups (0 off) */
+    uint32_t group_tiles;      /* tiles of a view per workgroup, one after the other */
+    int32_t small_area;        /* triangles whose box in the tile covers more pixels go on the large list */
+    uint32_t workgroups;       /* of the launch */
+} mrx_bvh_launch_t;
+int mrx_bvh_launch(mrx_renderer *r, mrx_bvh_launch_t *out);
 int mrx_info(mrx_renderer *r, mrx_info_t *out);
 int mrx_info_sized(mrx_renderer *r, void *out, size_t size);
 void *mrx_stream(mrx_renderer *r);

@@ -1695,6 +1695,51 @@ size_t bvhLdsBytes(uint32_t passInst, bool textured, bool classify, uint32_t gro
     return ldsFor(passInst, textured, 64, 64, classify, groupViews, texCap);
 }
 
+BvhLaunchShape bvhLaunchShape(const RasterParams &p)
+{
+    BvhLaunchShape s = {};
+    const bool tex = p.anyTextured != 0;
+    s.textured = tex ? 1u : 0u;
+    s.passInst = p.bvhPassInst;
+    s.smallArea = p.bvhSmallArea;
+    s.texCap = p.bvhTexCap;
+    if (p.bvhFlat) {
+        // (the flat kernel: the record table is the world, nothing overflows -- no rounds, no list)
+        const uint32_t tpv = ((p.nfast + 63u) / 64u) * ((p.nslow + 63u) / 64u);
+        s.flat = 1;
+        s.tileW = s.tileH = 64u;
+        s.groupViews = 1u;
+        s.groupTiles = std::max<uint32_t>(1u, std::min<uint32_t>(p.bvhGroupTiles, tpv));
+        s.workgroups = p.numViews * ((tpv + s.groupTiles - 1) / s.groupTiles);
+        return s;
+    }
+    // as launchBvh and bvhTileKernel work them out
+    const int tw = p.bvhTile == 2 ? 32 : 64, th = p.bvhTile == 0 ? 64 : 32;
+    const bool cls = p.bvhTile == 0 && p.bvhClassify;
+    const uint32_t tilesPerView = ((p.nfast + tw - 1) / tw) * ((p.nslow + th - 1) / th);
+    const uint32_t groupViews = p.bvhGroupViews & 0xFFFFu;
+    const bool multi = groupViews > 1;
+    s.tileW = (uint32_t)tw;
+    s.tileH = (uint32_t)th;
+    s.classify = cls ? 1u : 0u;
+    s.recordCap = tex ? p.bvhTexCap : (uint32_t)tabCap(false, tw, th, cls);
+    s.recordUsable = tex ? std::min(s.recordCap, kStashed) : (uint32_t)tabUsable((int)s.recordCap);
+    s.bigCap = (uint32_t)bigCap(tw, th, cls, tex);
+    s.groupViews = groupViews;
+    s.groupTiles = multi ? 1u : std::max<uint32_t>(1u, std::min<uint32_t>(p.bvhGroupTiles, tilesPerView));
+    s.priority = (p.bvhGroupViews >> 17) & 7u;
+    s.workgroups = multi ? (p.numViews + groupViews - 1) / groupViews
+                         : p.numViews * ((tilesPerView + s.groupTiles - 1) / s.groupTiles);
+    if (groupViews == 2 && (p.bvhGroupViews & 0x10000u)) {
+        const uint32_t resident = 2u * (p.bvhGroupViews >> 20);
+        if (resident >= s.workgroups && resident <= p.numViews) {
+            s.workgroups = resident;
+            s.mixed = 1u;
+        }
+    }
+    return s;
+}
+
 hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
 {
     if (p.numViews == 0)

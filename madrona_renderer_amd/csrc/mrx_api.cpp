@@ -1890,6 +1890,35 @@ int mrx_raster_entry(mrx_renderer *r)
     return r->shards.empty() ? r->lastEntry : r->shards[0]->lastEntry;
 }
 
+int mrx_bvh_launch(mrx_renderer *r, mrx_bvh_launch_t *out)
+{
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (!out)
+        return fail(MRX_E_INVALID, "null output");
+    const mrx_renderer &sh = r->shards.empty() ? *r : *r->shards[0];
+    const mrx::BvhLaunchShape s = mrx::bvhLaunchShape(sh.params);
+    mrx_bvh_launch_t o = {};
+    o.kernel = !sh.useBvh ? MRX_BVH_KERNEL_NONE : s.flat ? MRX_BVH_KERNEL_FLAT : MRX_BVH_KERNEL_TILE;
+    o.tile_w = s.tileW;
+    o.tile_h = s.tileH;
+    o.classify = s.classify;
+    o.textured = s.textured;
+    o.record_cap = s.recordCap;
+    o.record_usable = s.recordUsable;
+    o.tex_cap = s.texCap;
+    o.big_cap = s.bigCap;
+    o.pass_inst = s.passInst;
+    o.group_views = s.groupViews;
+    o.mixed = s.mixed;
+    o.priority = s.priority;
+    o.group_tiles = s.groupTiles;
+    o.small_area = s.smallArea;
+    o.workgroups = s.workgroups;
+    *out = o;
+    return MRX_OK;
+}
+
 int mrx_num_shards(mrx_renderer *r) { return !r ? 0 : r->shards.empty() ? 1 : (int)r->shards.size(); }
 
 mrx_renderer *mrx_shard(mrx_renderer *r, int shard)

@@ -385,6 +385,31 @@ PYBIND11_MODULE(madrona_renderer, m)
         .def("bytes_per_step", &Manager::bytesPerStep)
         .def("render_path", [](Manager &self) { return std::string(self.renderPath()); })
         .def("raster_entry", [](Manager &self) { return std::string(self.rasterEntry()); })
+        .def("bvh_launch",
+             [](Manager &self) {
+                 // mrx_bvh_launch: the BVH path's launch shape for the bound geometry
+                 mrx_bvh_launch_t s = {};
+                 if (mrx_bvh_launch(static_cast<mrx_renderer *>(self.nativeHandle()), &s) != MRX_OK)
+                     throw std::runtime_error(mrx_last_error());
+                 static const char *const kernels[] = {"none", "tile", "flat"};
+                 py::dict d;
+                 d["kernel"] = kernels[s.kernel >= 0 && s.kernel <= 2 ? s.kernel : 0];
+                 d["tile"] = py::make_tuple(s.tile_w, s.tile_h);
+                 d["classify"] = s.classify != 0;
+                 d["textured"] = s.textured != 0;
+                 d["record_cap"] = s.record_cap;
+                 d["record_usable"] = s.record_usable;
+                 d["tex_cap"] = s.tex_cap;
+                 d["big_cap"] = s.big_cap;
+                 d["pass_inst"] = s.pass_inst;
+                 d["group_views"] = s.group_views;
+                 d["mixed"] = s.mixed != 0;
+                 d["priority"] = s.priority;
+                 d["group_tiles"] = s.group_tiles;
+                 d["small_area"] = s.small_area;
+                 d["workgroups"] = s.workgroups;
+                 return d;
+             })
         .def("placement",
              [](Manager &self) {
                  float us[16] = {}, kept = 0.f;

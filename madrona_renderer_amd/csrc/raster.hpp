@@ -289,4 +289,14 @@ constexpr uint32_t kBvhMaxWorldTris = 0x1FFFFEu;   // the depth buffer's key hol
 // dynamic LDS bytes one workgroup of the BVH kernel needs for `passInst` instance records
 size_t bvhLdsBytes(uint32_t passInst, bool textured, bool classify, uint32_t groupViews, uint32_t texCap);
 
+// What launchBvh launches for `p`, worked out the way it does (mrx_bvh_launch; include/mrx.h mrx_bvh_launch_t has
+// the meaning of each field).  Host only.
+struct BvhLaunchShape {
+    int32_t flat;
+    uint32_t tileW, tileH, classify, textured, recordCap, recordUsable, texCap, bigCap, passInst;
+    uint32_t groupViews, mixed, priority, groupTiles, workgroups;
+    int32_t smallArea;
+};
+BvhLaunchShape bvhLaunchShape(const RasterParams &p);
+
 }  // namespace mrx
