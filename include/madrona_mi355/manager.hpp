@@ -28,6 +28,9 @@ public:
     // only): an output that is not rendered has no tensor -- its getters fail as segmaskTensor()
     // does in Rasterizer mode.  The segmask (Raytracer mode) is rendered under every setting.
     enum class RenderOutputs { RGBD, Depth, RGB };
+    // The projection of a camera (attachEntityToView's vfov / znear, src/sim.cpp:168-171): degrees, 0 < vfov < 180;
+    // znear > 0, 0 = the mode's default (Raytracer mode: below its far plane, 1000).  {90, 0} is every view's default.
+    struct CameraProjection { float vfovDeg; float znear; };
 
     struct GeometryConfig {
         const madrona::math::Vector3 *vertices;
@@ -79,6 +82,9 @@ public:
         uint32_t maxInstancesPerWorld = 0;
         // Outputs rendered (MRX_FLAG_NO_RGB / MRX_FLAG_NO_DEPTH): RGBD = both, as the reference.
         RenderOutputs renderOutputs = RenderOutputs::RGBD;
+        // [numCameras] projections parallel to rcfg.cameras (nullptr: every camera {90, 0}); a view takes its
+        // camera row's, as it takes its pose.
+        const CameraProjection *cameraProjections = nullptr;
     };
 
     // Aborts (FATAL-style, like the reference) when construction fails.
@@ -132,6 +138,11 @@ public:
     // the kernel the last render launched (mrx_raster_entry): "group-fast", "group", "chunked", "brute",
     // "bvh", or "none" before the first render
     const char *rasterEntry() const;
+    // per-view projection (views of the whole job): set views [first, first + count) -- stream-ordered, the next
+    // step renders with them; false (and nothing changed) when a value is out of range -- and read them back
+    bool setViewProjection(uint32_t first, uint32_t count, const CameraProjection *proj);
+    void viewProjection(uint32_t first, uint32_t count, CameraProjection *out) const;
+    uint32_t numViews() const;
 
     uint32_t numAgents;
 

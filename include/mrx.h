@@ -63,6 +63,15 @@ typedef struct {
     uint32_t cameras_offset;
 } mrx_world_init;
 
+/* The projection of a camera (the vfov / znear arguments of RenderingSystem::attachEntityToView,
+ * /root/reference/src/sim.cpp:168-171): vertical field of view in degrees, 0 < vfov_deg < 180, and the near
+ * plane, znear > 0 (Raytracer mode: also < 1000, its far plane); znear = 0 means the mode's default (0.001 in
+ * Rasterizer mode, 0.1 in Raytracer mode).  The defaults, {90, 0}, give the constants every view had before. */
+typedef struct {
+    float vfov_deg;
+    float znear;
+} mrx_projection;
+
 /* madrona::imp::SourceMaterial as the reference fills it,
  * /root/reference/src/bindings.cpp:44-49 (28 bytes). */
 typedef struct {
@@ -148,8 +157,13 @@ typedef struct {
      * renderables at run time (src/sim.inl:5-8).  Spare rows start hidden and unbound
      * (ObjectID -1, identity pose); see mrx_refresh_objects. */
     uint32_t max_instances_per_world;
+    /* -- per-camera projection (a caller that sets struct_size = MRX_CONFIG_V4_SIZE or MRX_CONFIG_V2_SIZE passes
+     * none): [num_cameras] entries parallel to `cameras`, NULL = every camera {90, 0}.  A view takes the projection
+     * of the camera row it is assembled from (mrx_world_init.cameras_offset), as it takes its pose. */
+    const mrx_projection *camera_projections;
 } mrx_config;
 #define MRX_CONFIG_V2_SIZE ((uint32_t)offsetof(mrx_config, device_ids))
+#define MRX_CONFIG_V4_SIZE ((uint32_t)offsetof(mrx_config, camera_projections))
 
 typedef struct mrx_renderer mrx_renderer;
 
@@ -373,6 +387,18 @@ uint32_t mrx_group_fill(uint32_t num_cus);
  *    compute unit in the batch (BASELINE configs[4]); 1 / 0. */
 int mrx_dispatch_flat(int raytracer, uint32_t num_views, uint32_t width, uint32_t height, uint32_t max_world_triangles,
                       uint32_t max_world_instances, uint32_t num_cus);
+
+/* -- per-view projection.  View indices are the whole job's (a renderer of several shards splits the range).
+ *    mrx_set_view_projection sets views [first_view, first_view + count) and is stream-ordered: renders enqueued
+ *    before it use the old values, the next render the new ones (each shard's table is updated by a copy on its
+ *    stream).  Every value is checked before anything changes: MRX_E_INVALID leaves the renderer as it was.
+ *    mrx_view_projection reads the current values back, defaults resolved (znear never 0). */
+int mrx_set_view_projection(mrx_renderer *r, uint32_t first_view, uint32_t count, const mrx_projection *proj);
+int mrx_view_projection(mrx_renderer *r, uint32_t first_view, uint32_t count, mrx_projection *out);
+/*    The constants of one projection (host only, no renderer needed) -- DESIGN.md S5: out = sx, ox, sz, oz,
+ *    1/znear, S6b pad, for views of width x height pixels (Raytracer mode: width x width) in `render_mode`.
+ *    Both launch forms (uniform and per-view) take their constants from here. */
+int mrx_projection_constants(uint32_t width, uint32_t height, int render_mode, mrx_projection proj, float out[6]);
 
 int mrx_device_count(void);
 int mrx_abi_version(void);

@@ -96,7 +96,9 @@ __device__ __forceinline__ void loadViewConst(const PARAMS &p, uint32_t view, Vi
 // lies safely in front of the eye plane (far enough, relative to the size of
 // the terms it is summed from, for the quotient to be meaningful), and whether
 // it lies safely behind it.
-__device__ __forceinline__ void projectCorner(const RasterParams &p, const float (&MV)[3][3],
+// PROJ: RasterParams (uniform form) or the view's ViewProj record (per-view form): its ox, oz are read
+template <typename PROJ>
+__device__ __forceinline__ void projectCorner(const PROJ &pj, const float (&MV)[3][3],
                                               const float (&tv)[3], float cx, float cy, float cz,
                                               float isx, float isz, float &fx, float &fz, bool &front,
                                               bool &behind)
@@ -110,8 +112,8 @@ __device__ __forceinline__ void projectCorner(const RasterParams &p, const float
     // safely behind the eye plane: a box whose eight corners all are holds nothing visible
     behind = P[1] < -1e-3f * scale;
     const float iw = __builtin_amdgcn_rcpf(P[1]);
-    fx = (P[0] * iw - p.ox) * isx;
-    fz = (P[2] * iw - p.oz) * isz;
+    fx = (P[0] * iw - pj.ox) * isx;
+    fz = (P[2] * iw - pj.oz) * isz;
 }
 
 // Image bounds -> padded storage rectangle.  Not `front`: the box reaches the
@@ -140,8 +142,8 @@ __device__ __forceinline__ Rect finishRect(const PARAMS &p, float x0, float x1, 
 // rounding of the sums they come from, the quotients use the near or far side of the
 // sphere whichever widens the interval, and a sphere that reaches the eye plane gives the
 // unbounded rectangle.
-template <typename PARAMS>
-__device__ __forceinline__ Rect sphereRect(const PARAMS &p, const InstXform &x, float4 omin, float4 omax,
+template <typename PARAMS, typename PROJ>
+__device__ __forceinline__ Rect sphereRect(const PARAMS &p, const PROJ &pj, const InstXform &x, float4 omin, float4 omax,
                                            float isx, float isz)
 {
     const float c[3] = { 0.5f * (omin.x + omax.x), 0.5f * (omin.y + omax.y), 0.5f * (omin.z + omax.z) };
@@ -161,8 +163,8 @@ __device__ __forceinline__ Rect sphereRect(const PARAMS &p, const InstXform &x, 
     const float zl = P[2] - R - pad[2], zh = P[2] + R + pad[2];
     const float qxl = xl * (xl >= 0.0f ? ifa : in), qxh = xh * (xh >= 0.0f ? in : ifa);
     const float qzl = zl * (zl >= 0.0f ? ifa : in), qzh = zh * (zh >= 0.0f ? in : ifa);
-    const float fa = (qxl - p.ox) * isx, fb = (qxh - p.ox) * isx;
-    const float ga = (qzl - p.oz) * isz, gb = (qzh - p.oz) * isz;
+    const float fa = (qxl - pj.ox) * isx, fb = (qxh - pj.ox) * isx;
+    const float ga = (qzl - pj.oz) * isz, gb = (qzh - pj.oz) * isz;
     Rect r = finishRect(p, fminf(fa, fb), fmaxf(fa, fb), fminf(ga, gb), fmaxf(ga, gb), front);
     if (yf < 0.0f) {                                  // the whole sphere behind the eye plane: nothing visible
         r.x0 = r.y0 = __builtin_inff();
@@ -485,10 +487,11 @@ __device__ __forceinline__ void viewInstances(const PARAMS &p, uint32_t view, ui
 // Phase I for chunks chFirst, chFirst + chStep, ... of the nI instances of a pass (rows from passBase on),
 // lane = instance: the TLAS records and rectangles of a view, into the block at `rec` ([passInst][24] records,
 // then [passInst] rectangles).
-template <typename PARAMS>
-__device__ __forceinline__ void tlasChunks(const PARAMS &p, const ViewConst &vc, uint32_t passBase, uint32_t nI,
-                                           uint32_t chFirst, uint32_t chStep, float *rec, uint32_t passInst, float isx,
-                                           float isz, int lane)
+// PROJ: where the view's ox, oz come from (RasterParams, or the view's ViewProj record in the per-view form)
+template <typename PARAMS, typename PROJ>
+__device__ __forceinline__ void tlasChunks(const PARAMS &p, const PROJ &pj, const ViewConst &vc, uint32_t passBase,
+                                           uint32_t nI, uint32_t chFirst, uint32_t chStep, float *rec, uint32_t passInst,
+                                           float isx, float isz, int lane)
 {
     float4 *const rects = reinterpret_cast<float4 *>(rec + (size_t)passInst * kInstRecDw);
     for (uint32_t ch = chFirst; ch * kWave < nI; ch += chStep) {
@@ -501,7 +504,7 @@ __device__ __forceinline__ void tlasChunks(const PARAMS &p, const ViewConst &vc,
         const uint32_t kBase = p.instKBase[row];
         InstXform x;
         instanceTransform(p, vc, row, x);
-        Rect r = sphereRect(p, x, omin, omax, isx, isz);
+        Rect r = sphereRect(p, pj, x, omin, omax, isx, isz);
         if (!(obj >= 0) || __float_as_uint(o0.y) == 0u) {    // nothing to draw: a rectangle nothing meets
             r.x0 = r.y0 = __builtin_inff();
             r.x1 = r.y1 = -__builtin_inff();
@@ -529,9 +532,10 @@ __device__ __forceinline__ void tlasChunks(const PARAMS &p, const ViewConst &vc,
 // instantiation: it has no pass loop (fewer scalar registers live through the traversal), and the plain
 // kernel has none to spare for the group's state (482-triangle worlds, one view per workgroup: 25.4 us
 // without it, 26.5 us with the state compiled in).
-template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
-__global__ __launch_bounds__(kWave *(TH / 8), 4)
-void bvhTileKernel(const RasterParams p)
+// PV: per-view projection: the view constants come from the table's record of the tile's view (MULTI:
+// of each view of the group in turn; phase I: of the wave's view); PV = false is the kernel as it always was.
+template <int IDS, bool TEX, int TW, int TH, bool CLS, bool MULTI, bool PV>
+__device__ __forceinline__ void tileKernelBody(const RasterParams p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     // (touchKernelArguments(), which buys the raster kernels 0.1 - 0.4 us per launch, measured nothing here --
@@ -652,8 +656,11 @@ void bvhTileKernel(const RasterParams p)
     uint32_t i0 = 0, i1 = 0;
     if (tI < left)
         viewInstances(p, myView, i0, i1);
-    const float isx = __builtin_amdgcn_rcpf(p.sx), isz = __builtin_amdgcn_rcpf(p.sz);
-    const float invNear = p.invNear, invFar = p.invFar;
+    // (PV: the record of the tile's view -- MULTI: of each view of the group in turn)
+    ViewProj pr = viewProjOf(p, PV, view);
+    float isx = __builtin_amdgcn_rcpf(PV ? pr.sx : p.sx), isz = __builtin_amdgcn_rcpf(PV ? pr.sz : p.sz);
+    float invNear = PV ? pr.invNear : p.invNear;
+    const float invFar = p.invFar;
     float TX0 = (float)tileX0, TX1 = (float)(tileX0 + TW - 1);
     float TY0 = (float)tileY0, TY1 = (float)(tileY0 + TH - 1);
     const int smallArea = p.bvhSmallArea;
@@ -717,7 +724,18 @@ void bvhTileKernel(const RasterParams p)
         float *const myRec = instRec + (size_t)tI * MRX_TLAS_DW;
         if (kLvInLds && ch0 * kWave < nI)
             loadViewConst(p, myView, vc);
-        tlasChunks(p, vc, passBase, nI, ch0, chStride, myRec, passInst, isx, isz, lane);
+        if (PV && MULTI) {
+            // (phase I builds the TLAS of the wave's view of the group; a wave past the group's last view has no
+            // instances and reads the group's first record instead)
+            const ViewProj pm = viewProjOf(p, true, tI < left ? myView : view);
+            tlasChunks(p, pm, vc, passBase, nI, ch0, chStride, myRec, passInst, __builtin_amdgcn_rcpf(pm.sx),
+                       __builtin_amdgcn_rcpf(pm.sz), lane);
+        } else {
+            if (PV)
+                tlasChunks(p, pr, vc, passBase, nI, ch0, chStride, myRec, passInst, isx, isz, lane);
+            else
+                tlasChunks(p, p, vc, passBase, nI, ch0, chStride, myRec, passInst, isx, isz, lane);
+        }
         // (the header after the records: ahead of them its write would wait for the camera loads before the
         // instance loads are even issued)
         if (kLvInLds && ch0 == 0 && lane == 0) {
@@ -775,7 +793,10 @@ void bvhTileKernel(const RasterParams p)
                             const float4 a0 = irec[0], a1 = irec[1], a2 = irec[2];
                             const float nMV[3][3] = { { a0.x, a0.y, a0.z }, { a0.w, a1.x, a1.y }, { a1.z, a1.w, a2.x } };
                             const float nTv[3] = { a2.y, a2.z, a2.w };
-                            projectCorner(p, nMV, nTv, cx, cy, cz, isx, isz, fx, fz, f, bh);
+                            if (PV)
+                                projectCorner(pr, nMV, nTv, cx, cy, cz, isx, isz, fx, fz, f, bh);
+                            else
+                                projectCorner(p, nMV, nTv, cx, cy, cz, isx, isz, fx, fz, f, bh);
                             float x0 = fx, x1 = fx, z0 = fz, z1 = fz;
                             int fr = (f ? 1 : 0) | (bh ? 2 : 0);
 #pragma unroll
@@ -882,8 +903,9 @@ void bvhTileKernel(const RasterParams p)
                     // kernel-argument segment instead of living in scalar registers: see ResolveArgs)
                     KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
                     asm volatile("" : "+s"(pk));
-                    const SetupArgs sa = { pk->tris, pk->triMats, pk->sx, pk->ox, pk->sz, pk->oz, pk->s6bPad,
-                                           pk->ambient, pk->diffuse, pk->transposed };
+                    const SetupArgs sa = { pk->tris, pk->triMats, PV ? pr.sx : pk->sx, PV ? pr.ox : pk->ox, PV ? pr.sz : pk->sz,
+                                           PV ? pr.oz : pk->oz, PV ? pr.s6bPad : pk->s6bPad, pk->ambient, pk->diffuse,
+                                           pk->transposed };
                     const bool valid = setupTriangleCore<false>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold);
                     live = valid && c.bbX1 >= TX0 && c.bbX0 <= TX1 && c.bbY1 >= TY0 && c.bbY0 <= TY1;
                     // The planes at the tile's corners: fl(A x + fl(B y + C)) is monotone in x and in
@@ -1238,9 +1260,15 @@ void bvhTileKernel(const RasterParams p)
         for (int i = lane; i < ZS * 8; i += kWave)
             zbuf[8 * wave * ZS + i] = packHit(invFar, 0u);
         if (MULTI) {
-            // the next view of the group: its TLAS is the next block
+            // the next view of the group: its TLAS is the next block (and its projection, per-view form)
             ++view;
             instRec += MRX_TLAS_DW;
+            if (PV) {
+                pr = viewProjOf(p, true, view);
+                isx = __builtin_amdgcn_rcpf(pr.sx);
+                isz = __builtin_amdgcn_rcpf(pr.sz);
+                invNear = pr.invNear;
+            }
             if (prioMode >= 2) {
                 if (young)
                     __builtin_amdgcn_s_setprio(0);
@@ -1270,6 +1298,21 @@ void bvhTileKernel(const RasterParams p)
 #undef MRX_TLAS_DW
 #undef MRX_INST_RECT
 #undef MRX_TLAS_HDR
+}
+
+template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
+__global__ __launch_bounds__(kWave *(TH / 8), 4)
+void bvhTileKernel(const RasterParams p)
+{
+    tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, false>(p);
+}
+
+// the per-view form (p.viewProj)
+template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
+__global__ __launch_bounds__(kWave *(TH / 8), 4)
+void bvhTileKernelPV(const RasterParams p)
+{
+    tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, true>(p);
 }
 
 
@@ -1339,9 +1382,9 @@ constexpr size_t flatLdsBytes(bool tex)
 // OUT: output selection (raster.hpp OutSel: kOutRGBD, kOutDepth or kOutRGB), fixed per instantiation.  Depth only:
 // the set-up does no colour work and writes every record in the untextured form (object id only), the resolve loads
 // no texel and stores no rgb; rgb only: no depth reciprocal, no depth store.
-template <int IDS, bool TEX, int OUT = kOutRGBD>
-__global__ __launch_bounds__(kWave * 8, MRX_FLAT_ZBUFS == 2 ? 4 : 6)
-void bvhFlatKernel(const RasterParams p)
+// PV: per-view projection -- a workgroup renders tiles of one view: its record is workgroup-uniform
+template <int IDS, bool TEX, int OUT, bool PV>
+__device__ __forceinline__ void flatKernelBody(const RasterParams p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
     constexpr int TW = 64, TH = 64, kWaves = 8, kHalves = 2;
@@ -1374,7 +1417,8 @@ void bvhFlatKernel(const RasterParams p)
             stamps[i] = __builtin_amdgcn_s_memrealtime();                      \
     } while (0)
     MRX_STAMP(0);
-    const float invNear = p.invNear, invFar = p.invFar;
+    const ViewProj pr = viewProjOf(p, PV, view);
+    const float invNear = PV ? pr.invNear : p.invNear, invFar = p.invFar;
     if (wave != 0) {
         // both depth buffers, by the seven waves that have nothing to load
         for (uint32_t i = (uint32_t)(wave - 1) * kWave + (uint32_t)lane; i < kFlatZBufs * kFlatZS * TH; i += (kWaves - 1) * kWave)
@@ -1457,7 +1501,13 @@ void bvhFlatKernel(const RasterParams p)
         bool valid = false;
         if (hasT) {
             float shade[4] = { 0.f, 0.f, 0.f, 0.f }, cold[kCold];
-            valid = setupTriangleCore<false, OUT != kOutDepth>(p, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
+            if (PV) {
+                const SetupArgs sa = { p.tris, p.triMats, pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, p.ambient, p.diffuse,
+                                       p.transposed };
+                valid = setupTriangleCore<false, OUT != kOutDepth>(sa, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
+            } else {
+                valid = setupTriangleCore<false, OUT != kOutDepth>(p, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
+            }
             const bool texRec = OUT != kOutDepth && valid && __float_as_int(shade[1]) >= 0;
             if (!TEX)
                 shadeTab[lane + 1] = make_float4(shade[0], shade[1], shade[2], __int_as_float(lane));
@@ -1676,6 +1726,21 @@ void bvhFlatKernel(const RasterParams p)
 #undef MRX_STAMP
 }
 
+template <int IDS, bool TEX, int OUT = kOutRGBD>
+__global__ __launch_bounds__(kWave * 8, MRX_FLAT_ZBUFS == 2 ? 4 : 6)
+void bvhFlatKernel(const RasterParams p)
+{
+    flatKernelBody<IDS, TEX, OUT, false>(p);
+}
+
+// the per-view form (p.viewProj): output selection by pointer
+template <int IDS, bool TEX>
+__global__ __launch_bounds__(kWave * 8, MRX_FLAT_ZBUFS == 2 ? 4 : 6)
+void bvhFlatKernelPV(const RasterParams p)
+{
+    flatKernelBody<IDS, TEX, kOutByPointer, true>(p);
+}
+
 }  // namespace
 
 namespace {
@@ -1757,26 +1822,29 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
             return ge;
         if (dev < 0 || dev >= kMaxDevices)
             return hipErrorInvalidDevice;
-#define MRX_FLAT_O(I, T, O)                                                                     \
+#define MRX_FLAT_K(K)                                                                           \
     do {                                                                                       \
         static bool allowed[kMaxDevices] = {};                                                 \
         {                                                                                      \
             std::lock_guard<std::mutex> guard(attrMutex);                                      \
             if (!allowed[dev]) {                                                               \
-                const hipError_t e = hipFuncSetAttribute((const void *)bvhFlatKernel<I, T, O>, \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)flatLdsBytes(T)); \
+                const hipError_t e = hipFuncSetAttribute((const void *)K,                     \
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)flatLdsBytes(tex)); \
                 if (e != hipSuccess)                                                           \
                     return e;                                                                  \
                 allowed[dev] = true;                                                           \
             }                                                                                  \
         }                                                                                      \
-        bvhFlatKernel<I, T, O><<<grid, block, flatLdsBytes(T), stream>>>(p);                   \
+        K<<<grid, block, flatLdsBytes(tex), stream>>>(p);                                      \
     } while (0)
-        // output selection: one instantiation per setting (kOutRGBD = the kernel as it always was)
+#define MRX_FLAT_O(I, T, O) MRX_FLAT_K((bvhFlatKernel<I, T, O>))
+        // output selection: one instantiation per setting (kOutRGBD = the kernel as it always was); the per-view
+        // form (p.viewProj) has one instantiation that selects by pointer
         const OutSel out = outSelOf(p.rgb, p.depth);
 #define MRX_FLAT(I, T)                                                                          \
     do {                                                                                       \
-        if (out == kOutDepth)    MRX_FLAT_O(I, T, kOutDepth);                                  \
+        if (p.viewProj)          MRX_FLAT_K((bvhFlatKernelPV<I, T>));                          \
+        else if (out == kOutDepth) MRX_FLAT_O(I, T, kOutDepth);                                \
         else if (out == kOutRGB) MRX_FLAT_O(I, T, kOutRGB);                                    \
         else                     MRX_FLAT_O(I, T, kOutRGBD);                                   \
     } while (0)
@@ -1785,6 +1853,7 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
         else { if (tex) MRX_FLAT(0, true); else MRX_FLAT(0, false); }
 #undef MRX_FLAT
 #undef MRX_FLAT_O
+#undef MRX_FLAT_K
         return hipGetLastError();
     }
     // tile shape: p.bvhTile = 0 (64x64), 1 (64x32: TW 64, TH 32), 2 (32x32)
@@ -1824,20 +1893,26 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
         if (dev < 0 || dev >= kMaxDevices)
             return hipErrorInvalidDevice;
     }
-#define MRX_BVH(I, T, W, H, C, M)                                                               \
+#define MRX_BVH_K(K)                                                                            \
     do {                                                                                       \
         static size_t allowed[kMaxDevices] = {};                                               \
         {                                                                                      \
             std::lock_guard<std::mutex> guard(attrMutex);                                      \
             if (lds > allowed[dev]) {                                                          \
-                const hipError_t e = hipFuncSetAttribute((const void *)bvhTileKernel<I, T, W, H, C, M>, \
+                const hipError_t e = hipFuncSetAttribute((const void *)K,                     \
                                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
                 if (e != hipSuccess)                                                           \
                     return e;                                                                  \
                 allowed[dev] = lds;                                                            \
             }                                                                                  \
         }                                                                                      \
-        bvhTileKernel<I, T, W, H, C, M><<<grid, block, lds, stream>>>(p);                      \
+        K<<<grid, block, lds, stream>>>(p);                                                    \
+    } while (0)
+    // the per-view form (p.viewProj): the same shape, its per-view instantiation
+#define MRX_BVH(I, T, W, H, C, M)                                                               \
+    do {                                                                                       \
+        if (p.viewProj) MRX_BVH_K((bvhTileKernelPV<I, T, W, H, C, M>));                        \
+        else            MRX_BVH_K((bvhTileKernel<I, T, W, H, C, M>));                          \
     } while (0)
 #define MRX_BVH_SHAPE(I, T)                                                                    \
     do {                                                                                       \
@@ -1857,6 +1932,7 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
     }
 #undef MRX_BVH_SHAPE
 #undef MRX_BVH
+#undef MRX_BVH_K
     return hipGetLastError();
 }
 

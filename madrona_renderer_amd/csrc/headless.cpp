@@ -5,6 +5,7 @@
 //   renderer_headless NUM_WORLDS NUM_STEPS rt|rast BATCH_WIDTH BATCH_HEIGHT
 //                     [--dump-last-frame file_name_without_extension]
 //                     [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb]
+//                     [--vfov DEG] [--znear Z]   (every camera's projection; no counterpart upstream)
 //
 // --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
 // renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
@@ -55,13 +56,27 @@ struct Args {
     uint32_t gpus = 1;
     Manager::RenderOutputs outputs = Manager::RenderOutputs::RGBD;
     std::string outName;
+    // --vfov DEG / --znear Z: the projection of every camera (0 = the mode's default near plane)
+    float vfov = 90.0f, znear = 0.0f;
 };
+
+// a number of the whole argument, finite
+float parseFloat(const char *flag, const char *s)
+{
+    char *end = nullptr;
+    const float v = std::strtof(s, &end);
+    if (!*s || *end || !std::isfinite(v)) {
+        std::fprintf(stderr, "%s: not a number: %s\n", flag, s);
+        std::exit(EXIT_FAILURE);
+    }
+    return v;
+}
 
 [[noreturn]] void usage(const char *argv0)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -88,6 +103,18 @@ Args parse(int argc, char **argv)
             a.dumpDepth = true;
         } else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) {
             a.gpus = (uint32_t)std::atoi(argv[++i]);
+        } else if (!std::strcmp(argv[i], "--vfov") && i + 1 < argc) {
+            a.vfov = parseFloat("--vfov", argv[++i]);
+            if (!(a.vfov > 0.0f && a.vfov < 180.0f)) {
+                std::fprintf(stderr, "--vfov: %s is not in (0, 180) degrees\n", argv[i]);
+                std::exit(EXIT_FAILURE);
+            }
+        } else if (!std::strcmp(argv[i], "--znear") && i + 1 < argc) {
+            a.znear = parseFloat("--znear", argv[++i]);
+            if (!(a.znear > 0.0f)) {
+                std::fprintf(stderr, "--znear: %s is not > 0\n", argv[i]);
+                std::exit(EXIT_FAILURE);
+            }
         } else if (!std::strcmp(argv[i], "--outputs") && i + 1 < argc) {
             const char *o = argv[++i];
             if (!std::strcmp(o, "rgbd")) a.outputs = Manager::RenderOutputs::RGBD;
@@ -100,6 +127,10 @@ Args parse(int argc, char **argv)
     }
     if (a.numWorlds == 0 || a.width == 0 || a.height == 0 || a.gpus == 0 || a.gpus > a.numWorlds)
         usage(argv[0]);
+    if (a.mode == Mode::Raycaster && !(a.znear < 1000.0f)) {
+        std::fprintf(stderr, "--znear: must be below the Raytracer far plane (1000)\n");
+        std::exit(EXIT_FAILURE);
+    }
     if (a.dumpDepth && a.outputs == Manager::RenderOutputs::RGB) {
         std::fprintf(stderr, "--depth: depth is not rendered with --outputs rgb\n");
         std::exit(EXIT_FAILURE);
@@ -322,6 +353,9 @@ int main(int argc, char **argv)
     rc.numInstances = (uint32_t)s.instances.size();
     rc.cameras = s.cameras.data();
     rc.numCameras = (uint32_t)s.cameras.size();
+    const std::vector<Manager::CameraProjection> projections(s.cameras.size(), { args.vfov, args.znear });
+    if (args.vfov != 90.0f || args.znear != 0.0f)
+        cfg.cameraProjections = projections.data();
     rc.worlds = s.worlds.data();
     if (args.gpus > 1) {
         cfg.deviceIDs = devices.data();

@@ -94,6 +94,8 @@ Manager::Manager(const Config &cfg)
     c.device_ids = cfg.deviceIDs;
     c.num_devices = cfg.numDevices;
     c.max_instances_per_world = cfg.maxInstancesPerWorld;
+    static_assert(sizeof(mrx_projection) == sizeof(CameraProjection), "projection ABI");
+    c.camera_projections = reinterpret_cast<const mrx_projection *>(cfg.cameraProjections);
     if (cfg.renderOutputs == RenderOutputs::Depth)
         c.flags |= MRX_FLAG_NO_RGB;
     else if (cfg.renderOutputs == RenderOutputs::RGB)
@@ -218,6 +220,30 @@ uint64_t Manager::bytesPerStep() const
 }
 
 void *Manager::nativeHandle() const { return impl_->r; }
+
+bool Manager::setViewProjection(uint32_t first, uint32_t count, const CameraProjection *proj)
+{
+    const int rc = mrx_set_view_projection(impl_->r, first, count, reinterpret_cast<const mrx_projection *>(proj));
+    if (rc == MRX_E_INVALID)
+        return false;
+    if (rc != MRX_OK)
+        detail::fatal(mrx_last_error());
+    return true;
+}
+
+void Manager::viewProjection(uint32_t first, uint32_t count, CameraProjection *out) const
+{
+    if (mrx_view_projection(impl_->r, first, count, reinterpret_cast<mrx_projection *>(out)) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+uint32_t Manager::numViews() const
+{
+    mrx_info_t inf {};
+    if (mrx_info(impl_->r, &inf) != MRX_OK)
+        detail::fatal(mrx_last_error());
+    return inf.num_views;
+}
 
 int Manager::placement(float *candUs, int capacity, float *keptUs) const
 {

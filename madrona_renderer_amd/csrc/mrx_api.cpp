@@ -50,6 +50,37 @@ constexpr double kVfovDeg = 90.0;      // /root/reference/src/sim.cpp:170
 constexpr float kRasterZNear = 0.001f; // /root/reference/src/sim.cpp:170
 constexpr float kRtZNear = 0.1f;       // /root/reference/src/mgr.cpp:477
 constexpr float kRtZFar = 1000.f;      // /root/reference/src/mgr.cpp:478
+
+// DESIGN.md S5 for one projection (mrx_projection_constants): checks it and works out the view constants in double,
+// rounded once to float, in the order the oracle uses (oracle.projection_constants).  H is the height as rendered
+// (Raytracer mode: = W).  `resolved` receives the projection with the mode's default znear filled in.
+int projectionConstants(uint32_t W, uint32_t H, bool rt, const mrx_projection &in, mrx::ViewProj &out,
+                        mrx_projection *resolved = nullptr)
+{
+    if (!(std::isfinite(in.vfov_deg) && in.vfov_deg > 0.0f && in.vfov_deg < 180.0f))
+        return fail(MRX_E_INVALID, "vfov_deg " + std::to_string(in.vfov_deg) + " is not in (0, 180)");
+    const float znear = in.znear == 0.0f ? (rt ? kRtZNear : kRasterZNear) : in.znear;
+    if (!(std::isfinite(znear) && znear > 0.0f))
+        return fail(MRX_E_INVALID, "znear " + std::to_string(in.znear) + " is not > 0");
+    if (rt && !(znear < kRtZFar))
+        return fail(MRX_E_INVALID, "znear " + std::to_string(in.znear) + " is not below the Raytracer far plane (1000)");
+    if (W == 0 || H == 0)
+        return fail(MRX_E_INVALID, "bad view size");
+    const float th = (float)std::tan((double)in.vfov_deg * M_PI / 360.0);
+    const double asp = (double)W / (double)H;
+    out.sx = (float)(2.0 * (double)th * asp / (double)W);
+    out.ox = (float)((1.0 / (double)W - 1.0) * (double)th * asp);
+    out.sz = (float)(-2.0 * (double)th / (double)H);
+    out.oz = (float)((1.0 - 1.0 / (double)H) * (double)th);
+    out.invNear = 1.0f / znear;
+    // S6b pad: a surface point nearer than znear along +Y that still projects
+    // into the image lies within znear * |longest ray| of the eye
+    out.s6bPad = (float)((double)znear * std::sqrt(1.0 + (double)th * (double)th * (1.0 + asp * asp)) * 1.001);
+    out.pad[0] = out.pad[1] = 0.0f;
+    if (resolved)
+        *resolved = mrx_projection{ in.vfov_deg, znear };
+    return MRX_OK;
+}
 constexpr double kLightDir[3] = { 1.0, -1.0, -0.05 };  // mgr.cpp:357
 constexpr float kAmbient = 0.25f;
 constexpr float kDiffuse = 0.75f;
@@ -306,6 +337,14 @@ struct mrx_renderer {
     // output allocation it timed, in order, and of the one it kept
     std::vector<float> placementUs;
     float placementKeptUs = 0.0f;
+    // per-view projection: the projection of every view of this renderer (defaults resolved), its
+    // device table (launched with only while the views differ: params.viewProj), the pinned staging the table is
+    // copied from on the stream, and the event after the last such copy (the staging is reused once it has passed)
+    std::vector<mrx_projection> proj;
+    DevBuf<mrx::ViewProj> projDev;
+    mrx::ViewProj *projStage = nullptr;
+    hipEvent_t projEv = nullptr;
+    bool projCopyPending = false;
 
     hipError_t launch()
     {
@@ -338,6 +377,11 @@ struct mrx_renderer {
         viewTris.release(); viewTriCount.release();
         instPos.release(); instRot.release(); instScale.release();
         camPos.release(); camRot.release(); instObj.release();
+        projDev.release();
+        if (projStage)
+            (void)hipHostFree(projStage);
+        if (projEv)
+            (void)hipEventDestroy(projEv);
         poseBlock.release(); geomBlock.release();
         rgb.release(); depth.release(); ids.release(); stamps.release();
         if (xccHost) (void)hipHostFree(xccHost);
@@ -1048,6 +1092,53 @@ int bindGeometry(mrx_renderer &r)
     return chooseBvhGroups(r);
 }
 
+// The launch form of the projections in r.proj.  Every view the same: its constants go in the
+// kernel arguments and params.viewProj is null (the uniform form -- a renderer of default cameras launches exactly
+// what it always did).  Views that differ: the table is copied to the device on the renderer's stream, behind every
+// render enqueued so far and ahead of every later one, and the kernels' per-view instantiations read it.
+int applyProjection(mrx_renderer &r)
+{
+    mrx::RasterParams &p = r.params;
+    const bool rt = r.mode == MRX_MODE_RAYTRACER;
+    const uint32_t W = rt ? p.nslow : p.nfast, H = rt ? p.nfast : p.nslow;
+    const mrx_projection dflt = { (float)kVfovDeg, 0.0f };
+    const mrx_projection &first = r.proj.empty() ? dflt : r.proj[0];
+    bool uniform = true;
+    for (const mrx_projection &q : r.proj)
+        uniform = uniform && std::memcmp(&q, &first, sizeof q) == 0;
+    mrx::ViewProj c;
+    int rc = projectionConstants(W, H, rt, first, c);
+    if (rc != MRX_OK)
+        return rc;
+    p.sx = c.sx; p.ox = c.ox; p.sz = c.sz; p.oz = c.oz;
+    p.invNear = c.invNear;
+    p.s6bPad = c.s6bPad;
+    if (uniform) {
+        p.viewProj = nullptr;
+        return MRX_OK;
+    }
+    const size_t n = r.proj.size();
+    MRX_HIP(hipSetDevice(r.device));
+    if (!r.projDev.ptr) {
+        MRX_HIP(r.projDev.alloc(n, 256));
+        MRX_HIP(hipHostMalloc((void **)&r.projStage, n * sizeof(mrx::ViewProj), hipHostMallocDefault));
+        MRX_HIP(hipEventCreateWithFlags(&r.projEv, hipEventDisableTiming));
+    }
+    // the staging is what the last copy reads: it is overwritten only once that copy has run
+    if (r.projCopyPending)
+        MRX_HIP(hipEventSynchronize(r.projEv));
+    for (size_t v = 0; v < n; ++v) {
+        rc = projectionConstants(W, H, rt, r.proj[v], r.projStage[v]);
+        if (rc != MRX_OK)
+            return rc;
+    }
+    MRX_HIP(hipMemcpyAsync(r.projDev.ptr, r.projStage, n * sizeof(mrx::ViewProj), hipMemcpyHostToDevice, r.stream));
+    MRX_HIP(hipEventRecord(r.projEv, r.stream));
+    r.projCopyPending = true;
+    p.viewProj = r.projDev.ptr;
+    return MRX_OK;
+}
+
 int buildScene(const mrx_config &cfg, mrx_renderer &r)
 {
     using namespace mrx;
@@ -1242,6 +1333,7 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     worldInstStart.assign(1, 0u);
     viewWorld.clear();
     r.worldCams.clear();
+    r.proj.clear();
     uint32_t maxWorldInst = 0;
     for (uint32_t w = 0; w < cfg.num_worlds; ++w) {
         const mrx_world_init &wi = cfg.worlds[w];
@@ -1273,6 +1365,9 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
             camPos.insert(camPos.end(), cam.position, cam.position + 3);
             camRot.insert(camRot.end(), cam.rotation, cam.rotation + 4);
             viewWorld.push_back(w);
+            // (checked by mrx_create; the mode's default znear resolved below)
+            r.proj.push_back(cfg.camera_projections ? cfg.camera_projections[wi.cameras_offset + c]
+                                                    : mrx_projection{ (float)kVfovDeg, 0.0f });
         }
     }
     // the object each row draws: bound here, re-bound by mrx_refresh_objects
@@ -1390,19 +1485,19 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     p.nslow = nslow;
     p.tilesFast = (nfast + 63) / 64;
     p.tilesSlow = (nslow + 63) / 64;
-    // S5: pixel -> ray constants, double math rounded once to float
-    const float th = (float)std::tan(kVfovDeg * M_PI / 360.0);
-    const double asp = (double)W / (double)H;
-    p.sx = (float)(2.0 * (double)th * asp / (double)W);
-    p.ox = (float)((1.0 / (double)W - 1.0) * (double)th * asp);
-    p.sz = (float)(-2.0 * (double)th / (double)H);
-    p.oz = (float)((1.0 - 1.0 / (double)H) * (double)th);
-    p.invNear = 1.0f / (rt ? kRtZNear : kRasterZNear);
+    // S5: pixel -> ray constants, double math rounded once to float -- per view (projectionConstants): the
+    // uniform ones in the kernel arguments, or the per-view table (applyProjection)
+    for (mrx_projection &q : r.proj) {
+        mrx::ViewProj c;
+        if (projectionConstants(W, H, rt, q, c, &q) != MRX_OK)
+            return MRX_E_INVALID;
+    }
     p.invFar = rt ? 1.0f / kRtZFar : 0.0f;
-    // S6b pad: a surface point nearer than znear along +Y that still projects
-    // into the image lies within znear * |longest ray| of the eye
-    p.s6bPad = (float)((double)(rt ? kRtZNear : kRasterZNear) *
-                       std::sqrt(1.0 + (double)th * (double)th * (1.0 + asp * asp)) * 1.001);
+    {
+        const int rc = applyProjection(r);
+        if (rc != MRX_OK)
+            return rc;
+    }
     const double ln = std::sqrt(kLightDir[0] * kLightDir[0] + kLightDir[1] * kLightDir[1] +
                                 kLightDir[2] * kLightDir[2]);
     for (int c = 0; c < 3; ++c)
@@ -1538,6 +1633,106 @@ extern "C" {
 int mrx_abi_version(void) { return MRX_ABI_VERSION; }
 
 const char *mrx_last_error(void) { return g_err.c_str(); }
+
+// the renderers that hold views [first, first + count) of the job, with the first job view of each
+static std::vector<std::pair<mrx_renderer *, uint32_t>> viewOwners(mrx_renderer *r)
+{
+    std::vector<std::pair<mrx_renderer *, uint32_t>> out;
+    uint32_t base = 0;
+    if (r->shards.empty()) {
+        out.emplace_back(r, 0u);
+        return out;
+    }
+    for (mrx_renderer *sh : r->shards) {
+        out.emplace_back(sh, base);
+        base += (uint32_t)sh->proj.size();
+    }
+    return out;
+}
+
+static int viewRange(mrx_renderer *r, uint32_t first, uint32_t count, const void *ptr)
+{
+    size_t total = 0;
+    for (const auto &o : viewOwners(r))
+        total += o.first->proj.size();
+    if ((uint64_t)first + count > total)
+        return fail(MRX_E_INVALID, "views [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                       ") outside the renderer's " + std::to_string(total));
+    if (count && !ptr)
+        return fail(MRX_E_INVALID, "null projection array");
+    return MRX_OK;
+}
+
+int mrx_set_view_projection(mrx_renderer *r, uint32_t first_view, uint32_t count, const mrx_projection *proj)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    int rc = viewRange(r, first_view, count, proj);
+    if (rc != MRX_OK)
+        return rc;
+    // every value first: a bad one leaves every view as it was
+    const bool rt = r->mode == MRX_MODE_RAYTRACER;
+    std::vector<mrx_projection> resolved(count);
+    for (uint32_t i = 0; i < count; ++i) {
+        mrx::ViewProj vp;
+        if (projectionConstants(16, 16, rt, proj[i], vp, &resolved[i]) != MRX_OK)
+            return fail(MRX_E_INVALID, "view " + std::to_string((uint64_t)first_view + i) + ": " + g_err);
+    }
+    for (const auto &o : viewOwners(r)) {
+        mrx_renderer &sh = *o.first;
+        const uint64_t lo = std::max<uint64_t>(first_view, o.second);
+        const uint64_t hi = std::min<uint64_t>((uint64_t)first_view + count, (uint64_t)o.second + sh.proj.size());
+        if (lo >= hi)
+            continue;
+        for (uint64_t v = lo; v < hi; ++v)
+            sh.proj[v - o.second] = resolved[v - first_view];
+        rc = applyProjection(sh);
+        if (rc != MRX_OK)
+            return rc;
+    }
+    return MRX_OK;
+}
+
+int mrx_view_projection(mrx_renderer *r, uint32_t first_view, uint32_t count, mrx_projection *out)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    const int rc = viewRange(r, first_view, count, out);
+    if (rc != MRX_OK)
+        return rc;
+    for (const auto &o : viewOwners(r))
+        for (size_t v = 0; v < o.first->proj.size(); ++v) {
+            const uint64_t job = (uint64_t)o.second + v;
+            if (job >= first_view && job < (uint64_t)first_view + count)
+                out[job - first_view] = o.first->proj[v];
+        }
+    return MRX_OK;
+}
+
+int mrx_projection_constants(uint32_t width, uint32_t height, int render_mode, mrx_projection proj, float out[6])
+{
+    if (!out)
+        return fail(MRX_E_INVALID, "null output");
+    if (render_mode != MRX_MODE_RASTERIZER && render_mode != MRX_MODE_RAYTRACER)
+        return fail(MRX_E_INVALID, "bad render_mode");
+    const bool rt = render_mode == MRX_MODE_RAYTRACER;
+    mrx::ViewProj c;
+    const int rc = projectionConstants(width, rt ? width : height, rt, proj, c);
+    if (rc != MRX_OK)
+        return rc;
+    out[0] = c.sx; out[1] = c.ox; out[2] = c.sz; out[3] = c.oz; out[4] = c.invNear; out[5] = c.s6bPad;
+    return MRX_OK;
+}
 
 int mrx_device_count(void)
 {
@@ -1731,7 +1926,9 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
         return fail(MRX_E_INVALID, "null argument");
     *out = nullptr;
     // ABI 2 callers pass the struct without its trailing ABI 3 fields: those read as zero
-    if (cfgIn->struct_size != sizeof(mrx_config) && cfgIn->struct_size != MRX_CONFIG_V2_SIZE)
+    // (ABI 4 callers: the struct without camera_projections, MRX_CONFIG_V4_SIZE -- every camera the default)
+    if (cfgIn->struct_size != sizeof(mrx_config) && cfgIn->struct_size != MRX_CONFIG_V2_SIZE &&
+        cfgIn->struct_size != MRX_CONFIG_V4_SIZE)
         return fail(MRX_E_INVALID, "mrx_config size mismatch (ABI)");
     mrx_config full;
     std::memset(&full, 0, sizeof full);
@@ -1760,6 +1957,14 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
                                    "neither rgb nor depth to render");
     if (cfg->max_instances_per_world > (1u << 20))
         return fail(MRX_E_INVALID, "max_instances_per_world out of range");
+    if (cfg->camera_projections)
+        for (uint32_t c = 0; c < cfg->num_cameras; ++c) {
+            mrx::ViewProj vp;
+            const bool rt = cfg->render_mode == MRX_MODE_RAYTRACER;
+            if (projectionConstants(cfg->view_width, rt ? cfg->view_width : cfg->view_height, rt,
+                                    cfg->camera_projections[c], vp) != MRX_OK)
+                return fail(MRX_E_INVALID, "camera " + std::to_string(c) + ": " + g_err);
+        }
     if (cfg->num_devices > 1 && !cfg->device_ids)
         return fail(MRX_E_INVALID, "device_ids is null while num_devices is not zero");
     if (cfg->num_devices > 64)

@@ -8,6 +8,7 @@
 #include <pybind11/stl.h>
 
 #include <array>
+#include <cmath>
 #include <cstdio>
 #include <string>
 #include <vector>
@@ -24,6 +25,30 @@ namespace detail { void setThrowOnError(bool v); }
 namespace {
 
 using namespace madRender;
+
+namespace {
+// a camera as the binding takes it: the reference's ImportedCamera (28 bytes, unchanged) and its projection
+struct PyCamera {
+    ImportedCamera cam;
+    Manager::CameraProjection proj;
+};
+
+// the mode-independent half of the projection check (mrx_projection_constants has the rest): ValueError
+void checkProjection(const Manager::CameraProjection &q)
+{
+    if (!(std::isfinite(q.vfovDeg) && q.vfovDeg > 0.0f && q.vfovDeg < 180.0f))
+        throw py::value_error("vfov must be finite and in (0, 180) degrees");
+    if (!(std::isfinite(q.znear) && q.znear >= 0.0f))
+        throw py::value_error("znear must be finite and > 0 (None: the mode's default)");
+}
+// a znear the caller gave (not None): finite and > 0
+float znearOf(float z)
+{
+    if (!(std::isfinite(z) && z > 0.0f))
+        throw py::value_error("znear must be finite and > 0 (None: the mode's default)");
+    return z;
+}
+}  // namespace
 using madrona::py::Tensor;
 using madrona::py::TensorElementType;
 
@@ -180,14 +205,21 @@ PYBIND11_MODULE(madrona_renderer, m)
              py::arg("position"), py::arg("rotation"), py::arg("scale"),
              py::arg("object_id"));
 
-    py::class_<ImportedCamera>(m, "ImportedCamera")
-        .def(py::init([](const std::array<float, 3> &pos, const std::array<float, 4> &rot) {
-                 ImportedCamera c {};
-                 c.position = { pos[0], pos[1], pos[2] };
-                 c.rotation = { rot[0], rot[1], rot[2], rot[3] };
+    // (the binding's camera carries the projection beside the 28-byte ImportedCamera; znear None = the mode's default)
+    py::class_<PyCamera>(m, "ImportedCamera")
+        .def(py::init([](const std::array<float, 3> &pos, const std::array<float, 4> &rot, float vfov, py::object znear) {
+                 PyCamera c {};
+                 c.cam.position = { pos[0], pos[1], pos[2] };
+                 c.cam.rotation = { rot[0], rot[1], rot[2], rot[3] };
+                 c.proj.vfovDeg = vfov;
+                 c.proj.znear = znear.is_none() ? 0.0f : znearOf(znear.cast<float>());
+                 checkProjection(c.proj);
                  return c;
              }),
-             py::arg("position"), py::arg("rotation"));
+             py::arg("position"), py::arg("rotation"), py::arg("vfov") = 90.0f, py::arg("znear") = py::none())
+        .def_property_readonly("vfov", [](const PyCamera &c) { return c.proj.vfovDeg; })
+        .def_property_readonly("znear", [](const PyCamera &c) -> py::object {
+            return c.proj.znear == 0.0f ? py::none() : py::cast(c.proj.znear); });
 
     py::class_<Sim::WorldInit>(m, "WorldInit")
         .def(py::init([](int64_t num_instances, int64_t instance_offset, int64_t num_cameras,
@@ -243,7 +275,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<AdditionalMaterial> &mats,
                          const std::vector<std::string> &texture_paths,
                          const std::vector<ImportedInstance> &instances,
-                         const std::vector<ImportedCamera> &cameras,
+                         const std::vector<PyCamera> &pycameras,
                          const std::vector<Sim::WorldInit> &worlds,
                          const std::vector<int> &device_ids, int max_instances_per_world,
                          Manager::RenderOutputs render_outputs) {
@@ -262,6 +294,18 @@ PYBIND11_MODULE(madrona_renderer, m)
                  if ((mesh_uvs.size() ? mesh_uvs.shape(0) : 0) !=
                      (mesh_vertices.size() ? mesh_vertices.shape(0) : 0))
                      throw py::value_error("mesh_uvs must have one row per row of mesh_vertices");
+                 std::vector<ImportedCamera> cameras(pycameras.size());
+                 std::vector<Manager::CameraProjection> projections(pycameras.size());
+                 bool anyProjection = false;
+                 for (size_t i = 0; i < pycameras.size(); ++i) {
+                     cameras[i] = pycameras[i].cam;
+                     projections[i] = pycameras[i].proj;
+                     anyProjection = anyProjection || projections[i].vfovDeg != 90.0f || projections[i].znear != 0.0f;
+                 }
+                 if (render_mode == Manager::RenderMode::Raytracer)
+                     for (const Manager::CameraProjection &q : projections)
+                         if (!(q.znear < 1000.0f))
+                             throw py::value_error("znear must be below the Raytracer far plane (1000)");
                  std::vector<const char *> cstrs(asset_paths.size());
                  std::vector<int32_t> mat_assignments(asset_paths.size());
                  for (size_t i = 0; i < asset_paths.size(); ++i) {
@@ -308,6 +352,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                      throw py::value_error("max_instances_per_world must not be negative");
                  cfg.maxInstancesPerWorld = (uint32_t)max_instances_per_world;
                  cfg.renderOutputs = render_outputs;
+                 cfg.cameraProjections = anyProjection ? projections.data() : nullptr;
                  return new Manager(cfg);
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -424,6 +469,59 @@ PYBIND11_MODULE(madrona_renderer, m)
                  return d;
              })
         .def("native_handle", [](Manager &self) { return (uint64_t)self.nativeHandle(); })
+        // per-view projection (views of the whole job from first_view on): vfov / znear are scalars (every view from
+        // first_view to the end) or sequences (one entry per view; a scalar beside a sequence is broadcast);
+        // znear None = the mode's default.  Stream-ordered: the next step renders with them.
+        .def("set_camera_projection",
+             [](Manager &self, py::object vfov, py::object znear, int64_t first_view) {
+                 const int64_t total = (int64_t)self.numViews();
+                 if (first_view < 0 || first_view > total)
+                     throw py::value_error("first_view out of range");
+                 auto asVec = [](py::object o, bool &scalar) {
+                     std::vector<float> v;
+                     scalar = !py::isinstance<py::sequence>(o) && !py::hasattr(o, "__len__");
+                     if (scalar)
+                         v.push_back(o.cast<float>());
+                     else
+                         v = py::array_t<float, py::array::c_style | py::array::forcecast>(o).cast<std::vector<float>>();
+                     return v;
+                 };
+                 bool fs = true, zs = true;
+                 std::vector<float> fv = asVec(vfov, fs), zv;
+                 if (znear.is_none())
+                     zv.push_back(0.0f);
+                 else {
+                     zv = asVec(znear, zs);
+                     for (float z : zv)
+                         znearOf(z);
+                 }
+                 if (!fs && !zs && fv.size() != zv.size())
+                     throw py::value_error("vfov and znear differ in length");
+                 const int64_t n = !fs ? (int64_t)fv.size() : !zs ? (int64_t)zv.size() : total - first_view;
+                 if (first_view + n > total)
+                     throw py::value_error("more projections than views from first_view on");
+                 std::vector<Manager::CameraProjection> proj((size_t)n);
+                 for (int64_t i = 0; i < n; ++i) {
+                     proj[(size_t)i].vfovDeg = fs ? fv[0] : fv[(size_t)i];
+                     proj[(size_t)i].znear = zs ? zv[0] : zv[(size_t)i];
+                     checkProjection(proj[(size_t)i]);
+                 }
+                 if (!self.setViewProjection((uint32_t)first_view, (uint32_t)n, proj.data()))
+                     throw py::value_error(mrx_last_error());
+             },
+             py::arg("vfov"), py::arg("znear") = py::none(), py::arg("first_view") = 0)
+        .def("camera_projection",
+             [](Manager &self) {
+                 const uint32_t n = self.numViews();
+                 std::vector<Manager::CameraProjection> proj(n);
+                 self.viewProjection(0, n, proj.data());
+                 py::array_t<float> f(n), z(n);
+                 for (uint32_t i = 0; i < n; ++i) {
+                     f.mutable_at(i) = proj[i].vfovDeg;
+                     z.mutable_at(i) = proj[i].znear;
+                 }
+                 return py::make_tuple(f, z);
+             })
         // e.g. r.set_stream(torch.cuda.current_stream().cuda_stream): pose writes and
         // step() are then ordered on that stream without a host synchronisation
         .def("set_stream",

@@ -85,10 +85,34 @@ __device__ __forceinline__ bool tileSetup(const RasterParams &p, uint32_t item, 
     return true;
 }
 
+// What the group kernel's set-up reads per triangle (instanceTransform / setupTriangleCore are templates over
+// the parameter type): pointers from the preloaded header or from RasterParams, scalars from RasterParams
+// (the projection constants: from the view's record in the per-view form).
+struct GroupSetupArgs {
+    const ObjTri *tris;
+    const TriMat *triMats;
+    const float *instPos, *instRot, *instScale;
+    float sx, ox, sz, oz, s6bPad, ambient, diffuse;
+    int32_t transposed;
+};
+
+// setupTriangle under the projection constants `pr` of the view (per-view form)
+__device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const ViewProj &pr, const ViewConst &vc,
+                                                  WorldTri wt, int32_t kWorld, TriPlanes &out, float *shade, float *cold)
+{
+    const GroupSetupArgs sa = { p.tris, p.triMats, p.instPos, p.instRot, p.instScale,
+                                pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, p.ambient, p.diffuse, p.transposed };
+    InstXform x;
+    instanceTransform(sa, vc, wt.inst, x);
+    return setupTriangleCore(sa, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold);
+}
+
 // S for one chunk of up to 64 world-triangles; returns the valid-lane mask.
+// PV: the per-view form, the view's projection constants in `pr`.
+template <bool PV>
 __device__ __forceinline__ uint64_t setupChunk(const RasterParams &p, const ViewConst &vc,
                                                const TileCtx &t, uint32_t chunk, int lane,
-                                               WaveLds &L)
+                                               WaveLds &L, const ViewProj &pr)
 {
     bool valid = false;
     const uint32_t k = chunk + lane;
@@ -96,7 +120,8 @@ __device__ __forceinline__ uint64_t setupChunk(const RasterParams &p, const View
         const WorldTri wt = p.viewTris[t.triBegin + k];
         TriPlanes c;
         float *h = L.hot[lane];
-        valid = setupTriangle(p, vc, wt, (int32_t)k, c, h + 12, L.cold[lane]);
+        valid = PV ? setupTriangleProj(p, pr, vc, wt, (int32_t)k, c, h + 12, L.cold[lane])
+                   : setupTriangle(p, vc, wt, (int32_t)k, c, h + 12, L.cold[lane]);
         h[0] = c.A0; h[1] = c.B0; h[2] = c.C0;
         h[3] = c.A1; h[4] = c.B1; h[5] = c.C1;
         h[6] = c.A2; h[7] = c.B2; h[8] = c.C2;
@@ -162,10 +187,10 @@ __device__ __forceinline__ void rasterBandBrute(const WaveLds &L, uint64_t valid
     }
 }
 
-// OUT: output selection (raster.hpp OutSel: kOutRGBD, kOutDepth or kOutRGB)
-template <bool IDS, bool MULTI, int OUT = kOutRGBD>
-__global__ __launch_bounds__(kWave *kWavesPerBlock)
-void rasterBruteKernel(const RasterParams p)
+// OUT: output selection (raster.hpp OutSel: kOutRGBD, kOutDepth or kOutRGB; kOutByPointer in the per-view form)
+// PV: per-view projection -- a wave renders one tile, so the view's record is wave-uniform
+template <bool IDS, bool MULTI, int OUT, bool PV>
+__device__ __forceinline__ void bruteKernelBody(const RasterParams p)
 {
     __shared__ WaveLds lds[kWavesPerBlock];
     touchKernelArguments();
@@ -176,16 +201,17 @@ void rasterBruteKernel(const RasterParams p)
     if (!tileSetup(p, blockIdx.x * kWavesPerBlock + wave, lane, t, vc))
         return;
     WaveLds &L = lds[wave];
+    const ViewProj pr = viewProjOf(p, PV, t.view);
 
     float pxf[8];
 #pragma unroll
     for (int bx = 0; bx < 8; ++bx)
         pxf[bx] = (float)(t.tileX0 + bx * 8 + t.lx);
-    const float invNear = p.invNear;
+    const float invNear = PV ? pr.invNear : p.invNear;
 
     uint64_t mask0 = 0;
     if (!MULTI)
-        mask0 = setupChunk(p, vc, t, 0, lane, L);
+        mask0 = setupChunk<PV>(p, vc, t, 0, lane, L, pr);
 
     for (int band = 0; band < 4; ++band) {
         float best[kBlocksPerBand];
@@ -211,7 +237,7 @@ void rasterBruteKernel(const RasterParams p)
                                       (b >> 3) ? py1 : py0, outRgba[b], outId[b]);
         } else {
             for (uint32_t chunk = 0; chunk < t.numTris; chunk += kChunk) {
-                const uint64_t mask = setupChunk(p, vc, t, chunk, lane, L);
+                const uint64_t mask = setupChunk<PV>(p, vc, t, chunk, lane, L, pr);
                 rasterBandBrute(L, mask, pxf, py0, py1, invNear, best, bid);
                 // resolve this chunk's winners before its records are replaced
 #pragma unroll
@@ -235,15 +261,30 @@ void rasterBruteKernel(const RasterParams p)
                 const bool hit = best[b] > p.invFar;
                 const float dep = hit ? 1.0f / best[b] : 0.0f;
                 const size_t o = ((size_t)t.view * p.nslow + fy) * p.nfast + fx;
-                if (OUT != kOutDepth)
+                if (storesRgb<OUT>(p.rgb))
                     p.rgb[o] = outRgba[b];
-                if (OUT != kOutRGB)
+                if (storesDepth<OUT>(p.depth))
                     p.depth[o] = dep;
                 if (IDS)
                     p.ids[o] = outId[b];
             }
         }
     }
+}
+
+template <bool IDS, bool MULTI, int OUT = kOutRGBD>
+__global__ __launch_bounds__(kWave *kWavesPerBlock)
+void rasterBruteKernel(const RasterParams p)
+{
+    bruteKernelBody<IDS, MULTI, OUT, false>(p);
+}
+
+// the per-view form (p.viewProj): one instantiation per id setting, output selection by pointer
+template <bool IDS, bool MULTI>
+__global__ __launch_bounds__(kWave *kWavesPerBlock)
+void rasterBruteKernelPV(const RasterParams p)
+{
+    bruteKernelBody<IDS, MULTI, kOutByPointer, true>(p);
 }
 
 // Bits 0..15: the tile's 32x8 regions (bit 2*strip + half) the lane's triangle
@@ -424,9 +465,9 @@ struct TileLds {
 };
 __device__ __forceinline__ const float *shadeRec(const PassRecs &L, int32_t w) { return L.shade[w]; }
 
-template <bool IDS>
-__global__ __launch_bounds__(kWave *kWavesPerBlock, 3)
-void rasterChunkedKernel(const RasterParams p)
+// PV: per-view projection -- a workgroup renders one tile of one view: its record is uniform
+template <bool IDS, bool PV>
+__device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
 {
     __shared__ TileLds lds;
     touchKernelArguments();
@@ -436,7 +477,9 @@ void rasterChunkedKernel(const RasterParams p)
     ViewConst vc;
     if (!tileSetup(p, blockIdx.x, lane, t, vc))
         return;                                   // whole workgroup leaves together
-    const float invNear = p.invNear, invFar = p.invFar;
+    // per-view projection: a wave-uniform runtime guard -- a workgroup renders one tile of one view
+    const ViewProj pr = viewProjOf(p, PV, t.view);
+    const float invNear = PV ? pr.invNear : p.invNear, invFar = p.invFar;
 
     // per-wave pixel state: strips 2*wave and 2*wave+1, two regions each
     float best[4][kRegionBlocks];
@@ -469,7 +512,10 @@ void rasterChunkedKernel(const RasterParams p)
                 bool valid = false;
                 if (k < t.numTris && !(p.debugSkip & 8u)) {
                     const WorldTri wt = p.viewTris[t.triBegin + k];
-                    valid = setupTriangle(p, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
+                    if (PV)
+                        valid = setupTriangleProj(p, pr, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
+                    else
+                        valid = setupTriangle(p, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
                 }
                 if (valid && !(p.debugSkip & 4u))
                     mask = classifyRegions(c, t, invNear, invFar);
@@ -522,6 +568,21 @@ void rasterChunkedKernel(const RasterParams p)
     }
 }
 
+template <bool IDS>
+__global__ __launch_bounds__(kWave *kWavesPerBlock, 3)
+void rasterChunkedKernel(const RasterParams p)
+{
+    chunkedKernelBody<IDS, false>(p);
+}
+
+// the per-view form (p.viewProj)
+template <bool IDS>
+__global__ __launch_bounds__(kWave *kWavesPerBlock, 3)
+void rasterChunkedKernelPV(const RasterParams p)
+{
+    chunkedKernelBody<IDS, true>(p);
+}
+
 // ---------------------------------------------------------------------------
 // Worlds of at most 256 triangles (every BASELINE scene): one workgroup renders
 // a group of views (all their tiles) or a chunk of the tiles of one view.
@@ -543,7 +604,7 @@ constexpr int kGroupTilesMax = 16;
 constexpr int kGroupSlotsMax = 256;
 constexpr int groupTilesMax(int slots) { return slots <= 128 ? kGroupTilesMax : 8; }
 
-template <int SLOTS>
+template <int SLOTS, bool PV = false>
 struct GroupLds {
     static constexpr int kRecs = SLOTS <= kChunk ? kChunk + 16 : SLOTS;
     static constexpr int kBackground = kRecs;   // record index of "nothing hit"
@@ -554,6 +615,7 @@ struct GroupLds {
     // per (tile, slot of the tile's view): region bits 0..15, near-free bits 16..19
     uint32_t masks[groupTilesMax(SLOTS) * (SLOTS <= kChunk ? kChunk : SLOTS)];
     uint32_t tileInfo[kGroupTilesMax][4];   // view, x0, y0, flags | first record << 8
+    float tileNear[PV ? kGroupTilesMax : 1];   // PV: 1/znear of each tile's view
     uint32_t nextItem;                  // (tile, strip) work counter of phase R
     uint8_t itemOrder[kGroupTilesMax * 8];  // work item -> tile * 8 + strip
     // FAST untextured kernels (16 slots, one-tile views): S2 writes each work item in the form phase R consumes --
@@ -697,16 +759,6 @@ __device__ __forceinline__ uint32_t classifyPair(const LDS &L, int j, int k, int
     return m;
 }
 
-// What the group kernel's set-up reads per triangle (instanceTransform / setupTriangleCore are templates over
-// the parameter type): pointers from the preloaded header or from RasterParams, scalars from RasterParams.
-struct GroupSetupArgs {
-    const ObjTri *tris;
-    const TriMat *triMats;
-    const float *instPos, *instRot, *instScale;
-    float sx, ox, sz, oz, s6bPad, ambient, diffuse;
-    int32_t transposed;
-};
-
 // Waves per workgroup of the group kernel: eight for untextured scenes (more
 // waves in flight absorb the stalls of a saturated store path), four for the
 // textured variant (its texel loads cost registers and vmcnt drains).
@@ -722,13 +774,15 @@ constexpr int groupWaves(bool tex) { return tex ? 4 : 8; }
 // raster.hpp), which the command processor preloads into SGPRs (-mllvm -amdgpu-kernarg-preload-count=12): the loads
 // go out without a round trip to the argument block; `p` is read for what comes after.
 // OUT (raster.hpp OutSel): the output selection of the instantiation.
-template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT>
+// PV: per-view projection: the set-up lanes read their view's record, S2 and phase R the 1/znear of
+// each tile's view, which the last wave leaves in LDS beside the tile's place.
+template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT, bool PV = false>
 __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances,
                                                 uint32_t hPool, uint32_t hShape, uint32_t hGroups, uint32_t hPrefix,
                                                 uint32_t hFirst01, uint32_t hFirst23, const RasterParams p)
 {
-    __shared__ GroupLds<SLOTS> lds;
-    constexpr int kBackground = GroupLds<SLOTS>::kBackground;
+    __shared__ GroupLds<SLOTS, PV> lds;
+    constexpr int kBackground = GroupLds<SLOTS, PV>::kBackground;
     // readfirstlane: the compiler cannot see that threadIdx.x / 64 is
     // wave-uniform and would predicate every `wave` branch instead of jumping
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -840,6 +894,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
         lds.tileInfo[lane][1] = (tile - ty * p.tilesFast) * 64u;
         lds.tileInfo[lane][2] = ty * 64u;
         lds.tileInfo[lane][3] = (firstView + vi < aNumViews ? kTileValid : 0u) | ((vi * SLOTS) << 8);
+        if (PV)
+            lds.tileNear[lane] = firstView + vi < aNumViews ? viewProjOf(p, true, firstView + vi).invNear : 0.0f;
     }
     // ... and the order of the work items.  One-tile views: strip by strip
     // across the views, top strips first -- strips above the horizon cost
@@ -926,13 +982,14 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             lds.shade[rec][1] = __int_as_float(-1);
             if ((uint32_t)k < numTris && !(dskip & 8u)) {
                 // the pose / geometry rows through pointers that come from the header (FAST) or from `p`
+                const ViewProj pr = viewProjOf(p, PV, view);
                 const GroupSetupArgs sa = {
                     FAST ? reinterpret_cast<const ObjTri *>(hGeom) : p.tris,
                     FAST ? reinterpret_cast<const TriMat *>(hGeom + geomMatsOffset(hPool)) : p.triMats,
                     FAST ? reinterpret_cast<const float *>(hPose + lay.instPos) : p.instPos,
                     FAST ? reinterpret_cast<const float *>(hPose + lay.instRot) : p.instRot,
                     FAST ? reinterpret_cast<const float *>(hPose + lay.instScale) : p.instScale,
-                    p.sx, p.ox, p.sz, p.oz, p.s6bPad, p.ambient, p.diffuse, p.transposed };
+                    pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, p.ambient, p.diffuse, p.transposed };
                 InstXform x;
                 instanceTransform(sa, vc, wt.inst, x);
                 valid = setupTriangleCore<true, OUT != kOutDepth>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
@@ -970,7 +1027,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             uint32_t m = 0;
             bool nearOk = false, tex = false;
             if (pair < numPairs)
-                m = classifyPair(lds, pair / SLOTS, pair % SLOTS, wave, invNear, invFar, nearOk, tex);
+                m = classifyPair(lds, pair / SLOTS, pair % SLOTS, wave, PV ? lds.tileNear[pair / SLOTS] : invNear, invFar,
+                                 nearOk, tex);
             m >>= 4 * (wave & 3);                 // bit 2i + hf: strip 2 (wave & 3) + i, half hf
             const uint64_t l0 = __ballot(m & 1u), r0 = __ballot(m & 2u), l1 = __ballot(m & 4u), r1 = __ballot(m & 8u);
             const uint64_t near0 = __ballot((m & 3u) && !nearOk), near1 = __ballot((m & 12u) && !nearOk);
@@ -997,7 +1055,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
         if (pair >= numPairs)
             continue;
         bool nearOk, tex;
-        uint32_t m = classifyPair(lds, pair / SLOTS, pair % SLOTS, wave, invNear, invFar, nearOk, tex);
+        uint32_t m = classifyPair(lds, pair / SLOTS, pair % SLOTS, wave, PV ? lds.tileNear[pair / SLOTS] : invNear,
+                                  invFar, nearOk, tex);
         if (nearOk)
             m |= 1u << (16 + (wave & 3));
         if (m)
@@ -1024,6 +1083,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     int32_t *idsTile = nullptr;
     const bool doRgb = storesRgb<OUT>(p.rgb), doDepth = storesDepth<OUT>(p.depth);
     uint32_t itemMasks = 0;     // readyItems: the item's surviving slots, left half bits 0..15, right half 16..31
+    float tileNear = invNear;   // 1/znear of the item's view (PV: from LDS, tile by tile)
     if (readyItems) {
         // the tile of a one-tile view sits at the view's origin: what depends on the tile origin is set once
         full = (p.nfast & 3u) == 0 && 64u <= p.nfast && 64u <= p.nslow;
@@ -1053,6 +1113,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             nearFree = (desc & kItemNearFree) != 0;
             anyTex = (desc & kItemAnyTex) != 0;
             recBase = j * SLOTS;
+            if (PV)
+                tileNear = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(lds.tileNear[j])));
             const size_t tileBase = (size_t)(firstView + (uint32_t)j) * p.nslow * p.nfast;
             rgbTile = p.rgb + tileBase;
             depthTile = p.depth + tileBase;
@@ -1070,6 +1132,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                 view = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][0]);
                 tileX0 = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][1]);
                 tileY0 = __builtin_amdgcn_readfirstlane(lds.tileInfo[j][2]);
+                if (PV)
+                    tileNear = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(lds.tileNear[j])));
                 const size_t tileBase = ((size_t)view * p.nslow + tileY0) * p.nfast + tileX0;
                 rgbTile = p.rgb + tileBase;
                 depthTile = p.depth + tileBase;
@@ -1132,9 +1196,9 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                     if (SUBS > 1 && act[sub] == 0)
                         continue;
                     if (nearFree)
-                        rasterRegion<false, 4>(lds.planes, act[sub], recBase + sub * kWave, px, py, invNear, best, bid);
+                        rasterRegion<false, 4>(lds.planes, act[sub], recBase + sub * kWave, px, py, tileNear, best, bid);
                     else
-                        rasterRegion<true, 4>(lds.planes, act[sub], recBase + sub * kWave, px, py, invNear, best, bid);
+                        rasterRegion<true, 4>(lds.planes, act[sub], recBase + sub * kWave, px, py, tileNear, best, bid);
                 }
             }
             if (full)
@@ -1177,6 +1241,26 @@ void rasterGroupKernelFast(const char *hPose, const char *hGeom, uint32_t hViews
                                                hFirst23, p);
 }
 
+// The per-view form (p.viewProj) of both entry points: XMODE 0 (the XCD phase trade and report are
+// left to the uniform form) and output selection by pointer, so that one instantiation per id / texture / slot setting
+// covers every batch.
+template <bool IDS, int SLOTS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : (SLOTS > 128 ? 6 : 8))
+void rasterGroupKernelPV(const RasterParams p)
+{
+    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
+}
+
+template <bool IDS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 8)
+void rasterGroupKernelFastPV(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
+                             uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
+                             const RasterParams p)
+{
+    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, true>(hPose, hGeom, hViews, hInstances, hPool, hShape, hGroups, hPrefix,
+                                                           hFirst01, hFirst23, p);
+}
+
 }  // namespace
 
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
@@ -1188,6 +1272,8 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
     const dim3 block(kWave * kWavesPerBlock);
     const bool ids = p.ids != nullptr;
     const bool multi = maxWorldTris > (uint32_t)kChunk;       // brute variant: chunk loop
+    // per-view projection: the same kernel family, its per-view instantiation
+    const bool pv = p.viewProj != nullptr;
     const bool large = maxWorldTris > (uint32_t)kGroupSlotsMax;
     if (variant == kVariantBrute) {
         // v1 reference: one wave per tile, every triangle at every pixel
@@ -1204,15 +1290,29 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
         }                                                                                \
     } while (0)
         const OutSel out = outSelOf(p.rgb, p.depth);
-        if (out == kOutDepth)    MRX_BRUTE(kOutDepth);
+        if (pv) {
+            if (ids) {
+                if (multi) rasterBruteKernelPV<true, true><<<grid, block, 0, stream>>>(p);
+                else       rasterBruteKernelPV<true, false><<<grid, block, 0, stream>>>(p);
+            } else {
+                if (multi) rasterBruteKernelPV<false, true><<<grid, block, 0, stream>>>(p);
+                else       rasterBruteKernelPV<false, false><<<grid, block, 0, stream>>>(p);
+            }
+        }
+        else if (out == kOutDepth) MRX_BRUTE(kOutDepth);
         else if (out == kOutRGB) MRX_BRUTE(kOutRGB);
         else                     MRX_BRUTE(kOutRGBD);
 #undef MRX_BRUTE
     } else if (large) {
         // more triangles per world than the group kernel holds: one workgroup per tile
         if (entry) *entry = kEntryChunked;
-        if (ids) rasterChunkedKernel<true><<<dim3(items), block, 0, stream>>>(p);
-        else     rasterChunkedKernel<false><<<dim3(items), block, 0, stream>>>(p);
+        if (pv) {
+            if (ids) rasterChunkedKernelPV<true><<<dim3(items), block, 0, stream>>>(p);
+            else     rasterChunkedKernelPV<false><<<dim3(items), block, 0, stream>>>(p);
+        } else {
+            if (ids) rasterChunkedKernel<true><<<dim3(items), block, 0, stream>>>(p);
+            else     rasterChunkedKernel<false><<<dim3(items), block, 0, stream>>>(p);
+        }
     } else {
         // triangle slots per view: the smallest of 16 ... 256 that holds a world
         int slots = 16;
@@ -1305,7 +1405,20 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
 #define MRX_GROUP_ARGS h.pose, h.geom, h.views, h.instances, h.poolTris, h.shape, h.groups, h.prefix, h.first01, h.first23, q
 #define MRX_GROUP_O(S, X, O, OP)                                               \
     do {                                                                       \
-        if (fast && S == 16) {                                                 \
+        if (pv) {                                                              \
+            if (fast && S == 16) {                                             \
+                if (ids) { if (p.anyTextured) rasterGroupKernelFastPV<true, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);    \
+                           else rasterGroupKernelFastPV<true, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }               \
+                else     { if (p.anyTextured) rasterGroupKernelFastPV<false, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
+                           else rasterGroupKernelFastPV<false, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }              \
+            } else if (ids) {                                                  \
+                if (p.anyTextured) rasterGroupKernelPV<true, S, true><<<grid, gblock, 0, stream>>>(q);                             \
+                else               rasterGroupKernelPV<true, S, false><<<grid, gblock, 0, stream>>>(q);                            \
+            } else {                                                           \
+                if (p.anyTextured) rasterGroupKernelPV<false, S, true><<<grid, gblock, 0, stream>>>(q);                            \
+                else               rasterGroupKernelPV<false, S, false><<<grid, gblock, 0, stream>>>(q);                           \
+            }                                                                  \
+        } else if (fast && S == 16) {                                          \
             if (p.anyTextured) {                                               \
                 if (ids) rasterGroupKernelFast<true, true, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
                 else     rasterGroupKernelFast<false, true, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);  \

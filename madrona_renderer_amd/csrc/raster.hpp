@@ -10,6 +10,15 @@ namespace mrx {
 struct BvhNode;
 struct ObjInfo;
 
+// Per-view projection (DESIGN.md S5 per view, 4.11): the constants of one view as the host works them out
+// (mrx_projection_constants), one 32-byte record per view in the device table RasterParams::viewProj.
+struct alignas(32) ViewProj {
+    float sx, ox, sz, oz;
+    float invNear, s6bPad;
+    float pad[2];
+};
+static_assert(sizeof(ViewProj) == 32, "ViewProj is one 32-byte record");
+
 // Object-space triangle: 16 dwords, one 64-byte line.
 struct alignas(16) ObjTri {
     float p[9];      // 3 vertices x xyz
@@ -163,6 +172,10 @@ struct RasterParams {
     // compute units of the device the renderer runs on (hipDeviceAttributeMultiprocessorCount at creation):
     // every "does the batch fill the chip" decision of the launchers follows from it (groupFill below)
     uint32_t numCUs;
+    // Per-view projection form: [numViews] records whose sx ox sz oz invNear s6bPad replace the uniform ones
+    // above, view by view; null = the uniform form (every view uses the kernel-argument constants).  The
+    // launchers pick the kernels' per-view instantiations from it.
+    const ViewProj *viewProj;
 };
 
 // ---- the argument header of the group kernel's fast prologue (raster.hip, FAST) -------------------------------------

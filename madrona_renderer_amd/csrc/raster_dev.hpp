@@ -301,6 +301,26 @@ __device__ __forceinline__ bool setupTriangle(const RasterParams &p,
     return setupTriangleCore(p, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold);
 }
 
+// The projection constants of a view: its record of the per-view table when `perView`, else
+// the uniform ones of the kernel arguments.  The table does not change during a launch and is read through the
+// constant address space: a wave-uniform view gives scalar loads, a per-lane one vector loads.
+typedef const __attribute__((address_space(4))) ViewProj *ConstViewProj;
+template <typename PARAMS>
+__device__ __forceinline__ ViewProj viewProjOf(const PARAMS &p, bool perView, uint32_t view)
+{
+    ViewProj r;
+    if (perView) {
+        const ConstViewProj t = (ConstViewProj)p.viewProj + view;
+        r.sx = t->sx; r.ox = t->ox; r.sz = t->sz; r.oz = t->oz;
+        r.invNear = t->invNear; r.s6bPad = t->s6bPad;
+    } else {
+        r.sx = p.sx; r.ox = p.ox; r.sz = p.sz; r.oz = p.oz;
+        r.invNear = p.invNear; r.s6bPad = p.s6bPad;
+    }
+    r.pad[0] = r.pad[1] = 0.0f;
+    return r;
+}
+
 // S8: nearest texel, repeat addressing, v up.
 __device__ __forceinline__ uint32_t shadeTextured(const RasterParams &p,
                                                   const float *cold, int32_t tex,

@@ -40,6 +40,9 @@ class SceneDesc:
     worlds: list = field(default_factory=list)          # [(ni, io, nc, co)]
     # rows per world at least (spare rows start hidden and unbound: refresh_objects)
     max_instances_per_world: int = 0
+    # per-camera projection, parallel to `cameras`: [(vfov_deg, znear or None)]; None = every camera (90, None),
+    # znear None = the mode's default (a view takes its camera row's projection, as it takes its pose)
+    camera_projections: list = None
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -227,6 +230,12 @@ def demo_scene(num_worlds=4, render_mode="Raytracer", width=64, height=64,
         worlds=[(2, 0, 1, 0)] * num_worlds)
 
 
+def _same_length(projections, cameras):
+    if len(projections) != len(cameras):
+        raise ValueError("camera_projections needs one (vfov, znear) per camera")
+    return projections
+
+
 def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
     """Instantiate the product renderer (compiled ``madrona_renderer`` module,
     HIP only) from a SceneDesc, with the reference's constructor kwargs.
@@ -266,7 +275,9 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
                                       scale=list(s), object_id=o)
                    for p, q, s, o in desc.instances],
         cameras=[m.ImportedCamera(position=list(p), rotation=list(q))
-                 for p, q in desc.cameras],
+                 for p, q in desc.cameras] if desc.camera_projections is None else
+                [m.ImportedCamera(position=list(p), rotation=list(q), vfov=float(f), znear=z)
+                 for (p, q), (f, z) in zip(desc.cameras, _same_length(desc.camera_projections, desc.cameras))],
         worlds=[m.WorldInit(num_instances=a, instance_offset=b, num_cameras=c,
                             camera_offset=d) for a, b, c, d in desc.worlds],
         **extra)
