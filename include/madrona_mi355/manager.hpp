@@ -31,6 +31,9 @@ public:
     // The projection of a camera (attachEntityToView's vfov / znear, src/sim.cpp:168-171): degrees, 0 < vfov < 180;
     // znear > 0, 0 = the mode's default (Raytracer mode: below its far plane, 1000).  {90, 0} is every view's default.
     struct CameraProjection { float vfovDeg; float znear; };
+    // The directional light of a world: the direction the light travels (any length but zero) and the two constants
+    // of lit = fma(diffuse, max(n.l, 0), ambient), both >= 0.  {(1, -1, -0.05), 0.25, 0.75} is every world's default.
+    struct Light { float direction[3]; float ambient; float diffuse; };
 
     struct GeometryConfig {
         const madrona::math::Vector3 *vertices;
@@ -85,6 +88,8 @@ public:
         // [numCameras] projections parallel to rcfg.cameras (nullptr: every camera {90, 0}); a view takes its
         // camera row's, as it takes its pose.
         const CameraProjection *cameraProjections = nullptr;
+        // [numWorlds] lights (nullptr: every world the default light); every view of a world takes its world's.
+        const Light *worldLights = nullptr;
     };
 
     // Aborts (FATAL-style, like the reference) when construction fails.
@@ -143,6 +148,11 @@ public:
     bool setViewProjection(uint32_t first, uint32_t count, const CameraProjection *proj);
     void viewProjection(uint32_t first, uint32_t count, CameraProjection *out) const;
     uint32_t numViews() const;
+    // per-world light (worlds of the whole job): set worlds [first, first + count) -- stream-ordered, the next step
+    // renders with them; false (and nothing changed) when a value is refused -- and read back what was set
+    bool setWorldLights(uint32_t first, uint32_t count, const Light *lights);
+    void worldLights(uint32_t first, uint32_t count, Light *out) const;
+    uint32_t numWorlds() const;
 
     uint32_t numAgents;
 

@@ -72,6 +72,16 @@ typedef struct {
     float znear;
 } mrx_projection;
 
+/* The directional light of a world (the one light of the reference, its src/mgr.cpp:357, per world):
+ * `direction` is the direction the light travels (any length but zero), `ambient` and `diffuse` the two constants
+ * of DESIGN.md S7, lit = fma(diffuse, max(n.l, 0), ambient), both >= 0.  All five values finite.  The default,
+ * {(1, -1, -0.05), 0.25, 0.75}, gives the colours every world had before. */
+typedef struct {
+    float direction[3];
+    float ambient;
+    float diffuse;
+} mrx_light;
+
 /* madrona::imp::SourceMaterial as the reference fills it,
  * /root/reference/src/bindings.cpp:44-49 (28 bytes). */
 typedef struct {
@@ -161,9 +171,13 @@ typedef struct {
      * none): [num_cameras] entries parallel to `cameras`, NULL = every camera {90, 0}.  A view takes the projection
      * of the camera row it is assembled from (mrx_world_init.cameras_offset), as it takes its pose. */
     const mrx_projection *camera_projections;
+    /* -- per-world light (a caller that sets struct_size to one of the sizes below passes none): [num_worlds]
+     * entries parallel to `worlds`, NULL = every world the default light.  Every view of a world takes its world's. */
+    const mrx_light *world_lights;
 } mrx_config;
 #define MRX_CONFIG_V2_SIZE ((uint32_t)offsetof(mrx_config, device_ids))
 #define MRX_CONFIG_V4_SIZE ((uint32_t)offsetof(mrx_config, camera_projections))
+#define MRX_CONFIG_V4_PROJ_SIZE ((uint32_t)offsetof(mrx_config, world_lights))
 
 typedef struct mrx_renderer mrx_renderer;
 
@@ -399,6 +413,19 @@ int mrx_view_projection(mrx_renderer *r, uint32_t first_view, uint32_t count, mr
  *    1/znear, S6b pad, for views of width x height pixels (Raytracer mode: width x width) in `render_mode`.
  *    Both launch forms (uniform and per-view) take their constants from here. */
 int mrx_projection_constants(uint32_t width, uint32_t height, int render_mode, mrx_projection proj, float out[6]);
+
+/* -- per-world light.  World indices are the whole job's (a renderer of several shards splits the range at
+ *    mrx_shard_first_world).  mrx_set_world_light sets worlds [first_world, first_world + count) and is stream-ordered
+ *    as mrx_set_view_projection is: renders enqueued before it keep the old light, the next render has the new one.
+ *    Every value is checked before anything changes: MRX_E_INVALID leaves the renderer as it was.  The light changes
+ *    colour only -- never which kernel runs, visibility, depth or the segmask.  mrx_world_light reads back what was
+ *    set (the caller's values, not normalised). */
+int mrx_set_world_light(mrx_renderer *r, uint32_t first_world, uint32_t count, const mrx_light *lights);
+int mrx_world_light(mrx_renderer *r, uint32_t first_world, uint32_t count, mrx_light *out);
+/*    The constants of one light (host only, no renderer needed) -- DESIGN.md S4 / S7: out = the unit vector towards
+ *    the light (x, y, z: -direction / |direction|, worked out in double and rounded once), ambient, diffuse.
+ *    Both launch forms (uniform and per-view) take their constants from here. */
+int mrx_light_constants(mrx_light light, float out[5]);
 
 int mrx_device_count(void);
 int mrx_abi_version(void);

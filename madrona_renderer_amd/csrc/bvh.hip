@@ -80,15 +80,18 @@ __device__ __forceinline__ int waveInclusiveSum(int v)
 }
 
 // Camera rotation / position of a view and the light direction in its frame (S2, S4).
-template <typename PARAMS>
+// PV: the direction towards the light of the view's world, from the view's record -- the view is
+// wave-uniform, the record a scalar load beside the camera's.
+template <bool PV = false, typename PARAMS>
 __device__ __forceinline__ void loadViewConst(const PARAMS &p, uint32_t view, ViewConst &vc)
 {
     const float4 q = *reinterpret_cast<const float4 *>(p.camRot + 4 * view);
+    const ViewLight lt = viewLightOf(p, PV, view);
     quatToMat(q.x, q.y, q.z, q.w, vc.Rc);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         vc.c[r] = p.camPos[3 * view + r];
-        vc.lv[r] = dot3(vc.Rc[0][r], vc.Rc[1][r], vc.Rc[2][r], p.toLight[0], p.toLight[1], p.toLight[2]);
+        vc.lv[r] = dot3(vc.Rc[0][r], vc.Rc[1][r], vc.Rc[2][r], lt.toLight[0], lt.toLight[1], lt.toLight[2]);
     }
 }
 
@@ -645,7 +648,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
     constexpr bool kLvInLds = TEX || MULTI;
     ViewConst vcAll = {};
     if (!kLvInLds)
-        loadViewConst(p, view, vcAll);
+        loadViewConst<PV>(p, view, vcAll);
     // ---- which TLAS this wave helps to build in phase I: wave w works on view w % groupViews of the
     //      group (groupViews is a power of two), chunks w / groupViews, + 8 / groupViews, ... of its
     //      instances; the instance rows of that view (none: a view past the end of the group)
@@ -723,7 +726,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
         ViewConst vc = vcAll;
         float *const myRec = instRec + (size_t)tI * MRX_TLAS_DW;
         if (kLvInLds && ch0 * kWave < nI)
-            loadViewConst(p, myView, vc);
+            loadViewConst<PV>(p, myView, vc);
         if (PV && MULTI) {
             // (phase I builds the TLAS of the wave's view of the group; a wave past the group's last view has no
             // instances and reads the group's first record instead)
@@ -903,9 +906,12 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     // kernel-argument segment instead of living in scalar registers: see ResolveArgs)
                     KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
                     asm volatile("" : "+s"(pk));
+                    // (PV: the two S7 constants of the world of the tile's view, from its light record batch by batch as
+                    // the others come from the argument segment -- MULTI: `view` is the view being rendered)
+                    const ConstViewLight lr = (ConstViewLight)pk->viewLight + view;
                     const SetupArgs sa = { pk->tris, pk->triMats, PV ? pr.sx : pk->sx, PV ? pr.ox : pk->ox, PV ? pr.sz : pk->sz,
-                                           PV ? pr.oz : pk->oz, PV ? pr.s6bPad : pk->s6bPad, pk->ambient, pk->diffuse,
-                                           pk->transposed };
+                                           PV ? pr.oz : pk->oz, PV ? pr.s6bPad : pk->s6bPad, PV ? lr->ambient : pk->ambient,
+                                           PV ? lr->diffuse : pk->diffuse, pk->transposed };
                     const bool valid = setupTriangleCore<false>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold);
                     live = valid && c.bbX1 >= TX0 && c.bbX0 <= TX1 && c.bbY1 >= TY0 && c.bbY0 <= TY1;
                     // The planes at the tile's corners: fl(A x + fl(B y + C)) is monotone in x and in
@@ -1425,7 +1431,8 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
             zbuf[i] = packHit(invFar, 0u);
     } else {
         ViewConst vc;
-        loadViewConst(p, view, vc);
+        loadViewConst<PV>(p, view, vc);
+        const ViewLight lt = viewLightOf(p, PV, view);
         InstXform y;
         int32_t objL = -1;
         uint32_t myTri = 0;
@@ -1502,7 +1509,7 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
         if (hasT) {
             float shade[4] = { 0.f, 0.f, 0.f, 0.f }, cold[kCold];
             if (PV) {
-                const SetupArgs sa = { p.tris, p.triMats, pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, p.ambient, p.diffuse,
+                const SetupArgs sa = { p.tris, p.triMats, pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse,
                                        p.transposed };
                 valid = setupTriangleCore<false, OUT != kOutDepth>(sa, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
             } else {

@@ -6,6 +6,7 @@
 //                     [--dump-last-frame file_name_without_extension]
 //                     [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb]
 //                     [--vfov DEG] [--znear Z]   (every camera's projection; no counterpart upstream)
+//                     [--light X,Y,Z[,AMBIENT,DIFFUSE]]   (every world's directional light; no counterpart upstream)
 //
 // --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
 // renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
@@ -58,6 +59,9 @@ struct Args {
     std::string outName;
     // --vfov DEG / --znear Z: the projection of every camera (0 = the mode's default near plane)
     float vfov = 90.0f, znear = 0.0f;
+    // --light X,Y,Z[,AMBIENT,DIFFUSE]: the light of every world (the direction it travels; ambient, diffuse >= 0)
+    bool hasLight = false;
+    Manager::Light light = { { 1.0f, -1.0f, -0.05f }, 0.25f, 0.75f };
 };
 
 // a number of the whole argument, finite
@@ -76,7 +80,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -109,6 +113,31 @@ Args parse(int argc, char **argv)
                 std::fprintf(stderr, "--vfov: %s is not in (0, 180) degrees\n", argv[i]);
                 std::exit(EXIT_FAILURE);
             }
+        } else if (!std::strcmp(argv[i], "--light") && i + 1 < argc) {
+            // three or five numbers; the library's own check decides (mrx_light_constants needs no device)
+            std::vector<std::string> fields(1);
+            for (const char *ch = argv[++i]; *ch; ++ch) {
+                if (*ch == ',')
+                    fields.emplace_back();
+                else
+                    fields.back() += *ch;
+            }
+            const int n = (int)fields.size();
+            float v[5] = { 0.0f, 0.0f, 0.0f, a.light.ambient, a.light.diffuse };
+            for (int k = 0; k < n && k < 5; ++k)
+                v[k] = parseFloat("--light", fields[(size_t)k].c_str());
+            float c[5];
+            const mrx_light l = { { v[0], v[1], v[2] }, v[3], v[4] };
+            if (n != 3 && n != 5) {
+                std::fprintf(stderr, "--light: wants X,Y,Z or X,Y,Z,AMBIENT,DIFFUSE, got %s\n", argv[i]);
+                std::exit(EXIT_FAILURE);
+            }
+            if (mrx_light_constants(l, c) != MRX_OK) {
+                std::fprintf(stderr, "--light: %s\n", mrx_last_error());
+                std::exit(EXIT_FAILURE);
+            }
+            a.light = { { v[0], v[1], v[2] }, v[3], v[4] };
+            a.hasLight = true;
         } else if (!std::strcmp(argv[i], "--znear") && i + 1 < argc) {
             a.znear = parseFloat("--znear", argv[++i]);
             if (!(a.znear > 0.0f)) {
@@ -356,6 +385,9 @@ int main(int argc, char **argv)
     const std::vector<Manager::CameraProjection> projections(s.cameras.size(), { args.vfov, args.znear });
     if (args.vfov != 90.0f || args.znear != 0.0f)
         cfg.cameraProjections = projections.data();
+    const std::vector<Manager::Light> lights(args.numWorlds, args.light);
+    if (args.hasLight)
+        cfg.worldLights = lights.data();
     rc.worlds = s.worlds.data();
     if (args.gpus > 1) {
         cfg.deviceIDs = devices.data();

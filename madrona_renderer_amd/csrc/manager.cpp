@@ -96,6 +96,8 @@ Manager::Manager(const Config &cfg)
     c.max_instances_per_world = cfg.maxInstancesPerWorld;
     static_assert(sizeof(mrx_projection) == sizeof(CameraProjection), "projection ABI");
     c.camera_projections = reinterpret_cast<const mrx_projection *>(cfg.cameraProjections);
+    static_assert(sizeof(mrx_light) == sizeof(Light), "light ABI");
+    c.world_lights = reinterpret_cast<const mrx_light *>(cfg.worldLights);
     if (cfg.renderOutputs == RenderOutputs::Depth)
         c.flags |= MRX_FLAG_NO_RGB;
     else if (cfg.renderOutputs == RenderOutputs::RGB)
@@ -243,6 +245,30 @@ uint32_t Manager::numViews() const
     if (mrx_info(impl_->r, &inf) != MRX_OK)
         detail::fatal(mrx_last_error());
     return inf.num_views;
+}
+
+bool Manager::setWorldLights(uint32_t first, uint32_t count, const Light *lights)
+{
+    const int rc = mrx_set_world_light(impl_->r, first, count, reinterpret_cast<const mrx_light *>(lights));
+    if (rc == MRX_E_INVALID)
+        return false;
+    if (rc != MRX_OK)
+        detail::fatal(mrx_last_error());
+    return true;
+}
+
+void Manager::worldLights(uint32_t first, uint32_t count, Light *out) const
+{
+    if (mrx_world_light(impl_->r, first, count, reinterpret_cast<mrx_light *>(out)) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+uint32_t Manager::numWorlds() const
+{
+    mrx_info_t inf {};
+    if (mrx_info(impl_->r, &inf) != MRX_OK)
+        detail::fatal(mrx_last_error());
+    return inf.num_worlds;
 }
 
 int Manager::placement(float *candUs, int capacity, float *keptUs) const

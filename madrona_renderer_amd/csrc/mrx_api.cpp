@@ -81,9 +81,39 @@ int projectionConstants(uint32_t W, uint32_t H, bool rt, const mrx_projection &i
         *resolved = mrx_projection{ in.vfov_deg, znear };
     return MRX_OK;
 }
-constexpr double kLightDir[3] = { 1.0, -1.0, -0.05 };  // mgr.cpp:357
-constexpr float kAmbient = 0.25f;
-constexpr float kDiffuse = 0.75f;
+// the light every world has unless it is given one (mgr.cpp:357; S7's constants).  The reference's direction is
+// written in double, and -0.05 is not a float: resolved from its float rounding, the z component of the unit vector
+// comes out one ulp off.  A light whose direction equals the float rounding of the default IS the default
+// (lightConstants resolves it from the doubles), so that the default given explicitly keeps every bit.
+constexpr double kLightDir[3] = { 1.0, -1.0, -0.05 };
+constexpr mrx_light kDefaultLight = { { (float)kLightDir[0], (float)kLightDir[1], (float)kLightDir[2] }, 0.25f, 0.75f };
+
+// DESIGN.md S4 / S7 for one light (mrx_light_constants): checks it and resolves the unit vector towards the light in
+// double, rounded once to float, in the order the oracle uses (oracle.to_light_vector).
+int lightConstants(const mrx_light &in, mrx::ViewLight &out)
+{
+    for (int c = 0; c < 3; ++c)
+        if (!std::isfinite(in.direction[c]))
+            return fail(MRX_E_INVALID, "light direction is not finite");
+    if (in.direction[0] == 0.0f && in.direction[1] == 0.0f && in.direction[2] == 0.0f)
+        return fail(MRX_E_INVALID, "light direction is zero");
+    if (!(std::isfinite(in.ambient) && in.ambient >= 0.0f))
+        return fail(MRX_E_INVALID, "light ambient " + std::to_string(in.ambient) + " is not a finite value >= 0");
+    if (!(std::isfinite(in.diffuse) && in.diffuse >= 0.0f))
+        return fail(MRX_E_INVALID, "light diffuse " + std::to_string(in.diffuse) + " is not a finite value >= 0");
+    double d[3] = { (double)in.direction[0], (double)in.direction[1], (double)in.direction[2] };
+    if (in.direction[0] == kDefaultLight.direction[0] && in.direction[1] == kDefaultLight.direction[1] &&
+        in.direction[2] == kDefaultLight.direction[2])
+        for (int c = 0; c < 3; ++c)
+            d[c] = kLightDir[c];
+    const double ln = std::sqrt(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+    for (int c = 0; c < 3; ++c)
+        out.toLight[c] = (float)(-d[c] / ln);
+    out.ambient = in.ambient;
+    out.diffuse = in.diffuse;
+    out.pad[0] = out.pad[1] = out.pad[2] = 0.0f;
+    return MRX_OK;
+}
 
 template <typename T>
 struct DevBuf {
@@ -345,6 +375,12 @@ struct mrx_renderer {
     mrx::ViewProj *projStage = nullptr;
     hipEvent_t projEv = nullptr;
     bool projCopyPending = false;
+    // per-world light: the light of every world of this renderer as the caller gave it, and the
+    // per-view device table with its staging -- filled and copied together with the projection table, behind the
+    // same event: the kernels' per-view instantiations read both
+    std::vector<mrx_light> lights;
+    DevBuf<mrx::ViewLight> lightDev;
+    mrx::ViewLight *lightStage = nullptr;
 
     hipError_t launch()
     {
@@ -378,8 +414,11 @@ struct mrx_renderer {
         instPos.release(); instRot.release(); instScale.release();
         camPos.release(); camRot.release(); instObj.release();
         projDev.release();
+        lightDev.release();
         if (projStage)
             (void)hipHostFree(projStage);
+        if (lightStage)
+            (void)hipHostFree(lightStage);
         if (projEv)
             (void)hipEventDestroy(projEv);
         poseBlock.release(); geomBlock.release();
@@ -1092,50 +1131,74 @@ int bindGeometry(mrx_renderer &r)
     return chooseBvhGroups(r);
 }
 
-// The launch form of the projections in r.proj.  Every view the same: its constants go in the
-// kernel arguments and params.viewProj is null (the uniform form -- a renderer of default cameras launches exactly
-// what it always did).  Views that differ: the table is copied to the device on the renderer's stream, behind every
-// render enqueued so far and ahead of every later one, and the kernels' per-view instantiations read it.
-int applyProjection(mrx_renderer &r)
+// The launch form of the projections in r.proj and the lights in r.lights.  Every view the
+// same projection and every world the same light: the constants go in the kernel arguments and params.viewProj /
+// viewLight are null (the uniform form -- a renderer of default cameras and lights launches exactly what it always
+// did).  Views or worlds that differ: both tables, one record per view, are copied to the device on the renderer's
+// stream, behind every render enqueued so far and ahead of every later one, and the kernels' per-view instantiations
+// read them; the table of whichever does not vary holds the uniform values.
+int applyViewTables(mrx_renderer &r)
 {
     mrx::RasterParams &p = r.params;
     const bool rt = r.mode == MRX_MODE_RAYTRACER;
     const uint32_t W = rt ? p.nslow : p.nfast, H = rt ? p.nfast : p.nslow;
     const mrx_projection dflt = { (float)kVfovDeg, 0.0f };
     const mrx_projection &first = r.proj.empty() ? dflt : r.proj[0];
-    bool uniform = true;
+    const mrx_light &firstLight = r.lights.empty() ? kDefaultLight : r.lights[0];
+    bool uniform = true, sameLight = true;
     for (const mrx_projection &q : r.proj)
         uniform = uniform && std::memcmp(&q, &first, sizeof q) == 0;
+    for (const mrx_light &l : r.lights)
+        sameLight = sameLight && std::memcmp(&l, &firstLight, sizeof l) == 0;
+    uniform = uniform && sameLight;
     mrx::ViewProj c;
     int rc = projectionConstants(W, H, rt, first, c);
+    if (rc != MRX_OK)
+        return rc;
+    mrx::ViewLight lc;
+    rc = lightConstants(firstLight, lc);
     if (rc != MRX_OK)
         return rc;
     p.sx = c.sx; p.ox = c.ox; p.sz = c.sz; p.oz = c.oz;
     p.invNear = c.invNear;
     p.s6bPad = c.s6bPad;
+    for (int k = 0; k < 3; ++k)
+        p.toLight[k] = lc.toLight[k];
+    p.ambient = lc.ambient;
+    p.diffuse = lc.diffuse;
     if (uniform) {
         p.viewProj = nullptr;
+        p.viewLight = nullptr;
+        p.lightTable = 0;
         return MRX_OK;
     }
     const size_t n = r.proj.size();
     MRX_HIP(hipSetDevice(r.device));
     if (!r.projDev.ptr) {
         MRX_HIP(r.projDev.alloc(n, 256));
+        MRX_HIP(r.lightDev.alloc(n, 256));
         MRX_HIP(hipHostMalloc((void **)&r.projStage, n * sizeof(mrx::ViewProj), hipHostMallocDefault));
+        MRX_HIP(hipHostMalloc((void **)&r.lightStage, n * sizeof(mrx::ViewLight), hipHostMallocDefault));
         MRX_HIP(hipEventCreateWithFlags(&r.projEv, hipEventDisableTiming));
     }
-    // the staging is what the last copy reads: it is overwritten only once that copy has run
+    // the staging is what the last copies read: it is overwritten only once they have run
     if (r.projCopyPending)
         MRX_HIP(hipEventSynchronize(r.projEv));
     for (size_t v = 0; v < n; ++v) {
         rc = projectionConstants(W, H, rt, r.proj[v], r.projStage[v]);
         if (rc != MRX_OK)
             return rc;
+        rc = lightConstants(r.lights[r.viewWorldHost[v]], r.lightStage[v]);
+        if (rc != MRX_OK)
+            return rc;
     }
     MRX_HIP(hipMemcpyAsync(r.projDev.ptr, r.projStage, n * sizeof(mrx::ViewProj), hipMemcpyHostToDevice, r.stream));
+    MRX_HIP(hipMemcpyAsync(r.lightDev.ptr, r.lightStage, n * sizeof(mrx::ViewLight), hipMemcpyHostToDevice, r.stream));
     MRX_HIP(hipEventRecord(r.projEv, r.stream));
     r.projCopyPending = true;
     p.viewProj = r.projDev.ptr;
+    p.viewLight = r.lightDev.ptr;
+    p.lightTable = sameLight ? 0u : 1u;
     return MRX_OK;
 }
 
@@ -1334,6 +1397,10 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     viewWorld.clear();
     r.worldCams.clear();
     r.proj.clear();
+    // (checked by mrx_create)
+    r.lights.assign(cfg.num_worlds, kDefaultLight);
+    if (cfg.world_lights)
+        r.lights.assign(cfg.world_lights, cfg.world_lights + cfg.num_worlds);
     uint32_t maxWorldInst = 0;
     for (uint32_t w = 0; w < cfg.num_worlds; ++w) {
         const mrx_world_init &wi = cfg.worlds[w];
@@ -1486,7 +1553,7 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     p.tilesFast = (nfast + 63) / 64;
     p.tilesSlow = (nslow + 63) / 64;
     // S5: pixel -> ray constants, double math rounded once to float -- per view (projectionConstants): the
-    // uniform ones in the kernel arguments, or the per-view table (applyProjection)
+    // uniform ones in the kernel arguments, or the per-view table (applyViewTables, with the worlds' lights: S4, S7)
     for (mrx_projection &q : r.proj) {
         mrx::ViewProj c;
         if (projectionConstants(W, H, rt, q, c, &q) != MRX_OK)
@@ -1494,16 +1561,10 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     }
     p.invFar = rt ? 1.0f / kRtZFar : 0.0f;
     {
-        const int rc = applyProjection(r);
+        const int rc = applyViewTables(r);
         if (rc != MRX_OK)
             return rc;
     }
-    const double ln = std::sqrt(kLightDir[0] * kLightDir[0] + kLightDir[1] * kLightDir[1] +
-                                kLightDir[2] * kLightDir[2]);
-    for (int c = 0; c < 3; ++c)
-        p.toLight[c] = (float)(-kLightDir[c] / ln);
-    p.ambient = kAmbient;
-    p.diffuse = kDiffuse;
     p.transposed = rt ? 1 : 0;
     // Raytracer ids are the segmask unless the caller asked for visibility ids
     p.idsAreSegmask = (rt && !(cfg.flags & MRX_FLAG_VISIBILITY_IDS)) ? 1 : 0;
@@ -1691,7 +1752,7 @@ int mrx_set_view_projection(mrx_renderer *r, uint32_t first_view, uint32_t count
             continue;
         for (uint64_t v = lo; v < hi; ++v)
             sh.proj[v - o.second] = resolved[v - first_view];
-        rc = applyProjection(sh);
+        rc = applyViewTables(sh);
         if (rc != MRX_OK)
             return rc;
     }
@@ -1731,6 +1792,98 @@ int mrx_projection_constants(uint32_t width, uint32_t height, int render_mode, m
     if (rc != MRX_OK)
         return rc;
     out[0] = c.sx; out[1] = c.ox; out[2] = c.sz; out[3] = c.oz; out[4] = c.invNear; out[5] = c.s6bPad;
+    return MRX_OK;
+}
+
+// the renderers that hold the worlds of the job, with the first job world of each
+static std::vector<std::pair<mrx_renderer *, uint32_t>> worldOwners(mrx_renderer *r)
+{
+    std::vector<std::pair<mrx_renderer *, uint32_t>> out;
+    if (r->shards.empty()) {
+        out.emplace_back(r, 0u);
+        return out;
+    }
+    for (size_t i = 0; i < r->shards.size(); ++i)
+        out.emplace_back(r->shards[i], r->shardFirstWorld[i]);
+    return out;
+}
+
+static int worldRange(mrx_renderer *r, uint32_t first, uint32_t count, const void *ptr)
+{
+    size_t total = 0;
+    for (const auto &o : worldOwners(r))
+        total += o.first->lights.size();
+    if ((uint64_t)first + count > total)
+        return fail(MRX_E_INVALID, "worlds [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                       ") outside the renderer's " + std::to_string(total));
+    if (count && !ptr)
+        return fail(MRX_E_INVALID, "null light array");
+    return MRX_OK;
+}
+
+int mrx_set_world_light(mrx_renderer *r, uint32_t first_world, uint32_t count, const mrx_light *lights)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    int rc = worldRange(r, first_world, count, lights);
+    if (rc != MRX_OK)
+        return rc;
+    // every value first: a bad one leaves every world as it was
+    for (uint32_t i = 0; i < count; ++i) {
+        mrx::ViewLight vl;
+        if (lightConstants(lights[i], vl) != MRX_OK)
+            return fail(MRX_E_INVALID, "world " + std::to_string((uint64_t)first_world + i) + ": " + g_err);
+    }
+    for (const auto &o : worldOwners(r)) {
+        mrx_renderer &sh = *o.first;
+        const uint64_t lo = std::max<uint64_t>(first_world, o.second);
+        const uint64_t hi = std::min<uint64_t>((uint64_t)first_world + count, (uint64_t)o.second + sh.lights.size());
+        if (lo >= hi)
+            continue;
+        for (uint64_t w = lo; w < hi; ++w)
+            sh.lights[w - o.second] = lights[w - first_world];
+        rc = applyViewTables(sh);
+        if (rc != MRX_OK)
+            return rc;
+    }
+    return MRX_OK;
+}
+
+int mrx_world_light(mrx_renderer *r, uint32_t first_world, uint32_t count, mrx_light *out)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    const int rc = worldRange(r, first_world, count, out);
+    if (rc != MRX_OK)
+        return rc;
+    for (const auto &o : worldOwners(r))
+        for (size_t w = 0; w < o.first->lights.size(); ++w) {
+            const uint64_t job = (uint64_t)o.second + w;
+            if (job >= first_world && job < (uint64_t)first_world + count)
+                out[job - first_world] = o.first->lights[w];
+        }
+    return MRX_OK;
+}
+
+int mrx_light_constants(mrx_light light, float out[5])
+{
+    if (!out)
+        return fail(MRX_E_INVALID, "null output");
+    mrx::ViewLight c;
+    const int rc = lightConstants(light, c);
+    if (rc != MRX_OK)
+        return rc;
+    out[0] = c.toLight[0]; out[1] = c.toLight[1]; out[2] = c.toLight[2]; out[3] = c.ambient; out[4] = c.diffuse;
     return MRX_OK;
 }
 
@@ -1926,9 +2079,10 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
         return fail(MRX_E_INVALID, "null argument");
     *out = nullptr;
     // ABI 2 callers pass the struct without its trailing ABI 3 fields: those read as zero
-    // (ABI 4 callers: the struct without camera_projections, MRX_CONFIG_V4_SIZE -- every camera the default)
+    // (ABI 4 callers: the struct without camera_projections, MRX_CONFIG_V4_SIZE -- every camera the default -- or
+    // without world_lights, MRX_CONFIG_V4_PROJ_SIZE -- every world the default light)
     if (cfgIn->struct_size != sizeof(mrx_config) && cfgIn->struct_size != MRX_CONFIG_V2_SIZE &&
-        cfgIn->struct_size != MRX_CONFIG_V4_SIZE)
+        cfgIn->struct_size != MRX_CONFIG_V4_SIZE && cfgIn->struct_size != MRX_CONFIG_V4_PROJ_SIZE)
         return fail(MRX_E_INVALID, "mrx_config size mismatch (ABI)");
     mrx_config full;
     std::memset(&full, 0, sizeof full);
@@ -1965,6 +2119,12 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
                                     cfg->camera_projections[c], vp) != MRX_OK)
                 return fail(MRX_E_INVALID, "camera " + std::to_string(c) + ": " + g_err);
         }
+    if (cfg->world_lights)
+        for (uint32_t w = 0; w < cfg->num_worlds; ++w) {
+            mrx::ViewLight vl;
+            if (lightConstants(cfg->world_lights[w], vl) != MRX_OK)
+                return fail(MRX_E_INVALID, "world " + std::to_string(w) + ": " + g_err);
+        }
     if (cfg->num_devices > 1 && !cfg->device_ids)
         return fail(MRX_E_INVALID, "device_ids is null while num_devices is not zero");
     if (cfg->num_devices > 64)
@@ -1994,6 +2154,7 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
         const uint32_t lo = shardFirstWorld(cfg->num_worlds, i, n), hi = shardFirstWorld(cfg->num_worlds, i + 1, n);
         sub.gpu_id = cfg->device_ids[i];
         sub.worlds = cfg->worlds ? cfg->worlds + lo : nullptr;
+        sub.world_lights = cfg->world_lights ? cfg->world_lights + lo : nullptr;
         sub.num_worlds = hi - lo;
         sub.num_devices = 0;
         sub.device_ids = nullptr;

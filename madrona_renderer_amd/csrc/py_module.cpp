@@ -42,6 +42,14 @@ void checkProjection(const Manager::CameraProjection &q)
         throw py::value_error("znear must be finite and > 0 (None: the mode's default)");
 }
 // a znear the caller gave (not None): finite and > 0
+// the light check of the library (mrx_light_constants): ValueError
+void checkLight(const Manager::Light &l)
+{
+    float c[5];
+    const mrx_light in = { { l.direction[0], l.direction[1], l.direction[2] }, l.ambient, l.diffuse };
+    if (mrx_light_constants(in, c) != MRX_OK)
+        throw py::value_error(mrx_last_error());
+}
 float znearOf(float z)
 {
     if (!(std::isfinite(z) && z > 0.0f))
@@ -278,7 +286,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<PyCamera> &pycameras,
                          const std::vector<Sim::WorldInit> &worlds,
                          const std::vector<int> &device_ids, int max_instances_per_world,
-                         Manager::RenderOutputs render_outputs) {
+                         Manager::RenderOutputs render_outputs, py::object world_lights) {
                  if (mesh_vertices.size() && (mesh_vertices.ndim() != 2 || mesh_vertices.shape(1) != 3))
                      throw py::value_error("mesh_vertices must have shape [N, 3]");
                  if (mesh_uvs.size() && (mesh_uvs.ndim() != 2 || mesh_uvs.shape(1) != 2))
@@ -353,6 +361,23 @@ PYBIND11_MODULE(madrona_renderer, m)
                  cfg.maxInstancesPerWorld = (uint32_t)max_instances_per_world;
                  cfg.renderOutputs = render_outputs;
                  cfg.cameraProjections = anyProjection ? projections.data() : nullptr;
+                 // world_lights: [(direction, ambient, diffuse)] per world, or None
+                 std::vector<Manager::Light> lights;
+                 if (!world_lights.is_none()) {
+                     const py::sequence seq = world_lights.cast<py::sequence>();
+                     if ((int64_t)py::len(seq) != num_worlds)
+                         throw py::value_error("world_lights needs one (direction, ambient, diffuse) per world");
+                     for (const py::handle &h : seq) {
+                         const py::tuple t = py::tuple(py::reinterpret_borrow<py::object>(h));
+                         if (t.size() != 3)
+                             throw py::value_error("world_lights entries are (direction, ambient, diffuse)");
+                         const std::array<float, 3> d = t[0].cast<std::array<float, 3>>();
+                         const Manager::Light l = { { d[0], d[1], d[2] }, t[1].cast<float>(), t[2].cast<float>() };
+                         checkLight(l);
+                         lights.push_back(l);
+                     }
+                     cfg.worldLights = lights.data();
+                 }
                  return new Manager(cfg);
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -367,7 +392,9 @@ PYBIND11_MODULE(madrona_renderer, m)
              // reserves hidden, unbound rows per world (see refresh_objects), render_outputs renders only depth
              // (RenderOutputs.Depth) or only rgb (RenderOutputs.RGB)
              py::arg("device_ids") = std::vector<int>(), py::arg("max_instances_per_world") = 0,
-             py::arg("render_outputs") = Manager::RenderOutputs::RGBD)
+             py::arg("render_outputs") = Manager::RenderOutputs::RGBD,
+             // world_lights = [(direction xyz, ambient, diffuse)] per world: the worlds' directional lights
+             py::arg("world_lights") = py::none())
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -510,6 +537,77 @@ PYBIND11_MODULE(madrona_renderer, m)
                      throw py::value_error(mrx_last_error());
              },
              py::arg("vfov"), py::arg("znear") = py::none(), py::arg("first_view") = 0)
+        // per-world light (worlds of the whole job from first_world on): direction is one triple (every world from
+        // first_world to the end) or an array [n, 3]; ambient / diffuse are None (each world keeps its own), scalars
+        // or sequences of n, broadcast as set_camera_projection does.  Stream-ordered: the next step renders with them.
+        .def("set_world_light",
+             [](Manager &self, py::object direction, py::object ambient, py::object diffuse, int64_t first_world) {
+                 const int64_t total = (int64_t)self.numWorlds();
+                 if (first_world < 0 || first_world > total)
+                     throw py::value_error("first_world out of range");
+                 const py::array_t<float, py::array::c_style | py::array::forcecast> dir(direction);
+                 const bool one = dir.ndim() == 1;
+                 if (!((one && dir.shape(0) == 3) || (dir.ndim() == 2 && dir.shape(1) == 3)))
+                     throw py::value_error("direction must be one (x, y, z) or an array of shape [n, 3]");
+                 auto asVec = [](py::object o, bool &scalar) {
+                     std::vector<float> v;
+                     scalar = !py::isinstance<py::sequence>(o) && !py::hasattr(o, "__len__");
+                     if (scalar)
+                         v.push_back(o.cast<float>());
+                     else
+                         v = py::array_t<float, py::array::c_style | py::array::forcecast>(o).cast<std::vector<float>>();
+                     return v;
+                 };
+                 bool as = true, ds = true;
+                 std::vector<float> av, dv;
+                 if (!ambient.is_none())
+                     av = asVec(ambient, as);
+                 if (!diffuse.is_none())
+                     dv = asVec(diffuse, ds);
+                 int64_t n = one ? -1 : (int64_t)dir.shape(0);
+                 for (const auto &sv : { std::make_pair(as, &av), std::make_pair(ds, &dv) })
+                     if (!sv.first) {
+                         if (n >= 0 && (int64_t)sv.second->size() != n)
+                             throw py::value_error("direction, ambient and diffuse differ in length");
+                         n = (int64_t)sv.second->size();
+                     }
+                 if (n < 0)
+                     n = total - first_world;
+                 if (first_world + n > total)
+                     throw py::value_error("more lights than worlds from first_world on");
+                 std::vector<Manager::Light> lights((size_t)n);
+                 if (n)
+                     self.worldLights((uint32_t)first_world, (uint32_t)n, lights.data());
+                 const float *d = dir.data();
+                 for (int64_t i = 0; i < n; ++i) {
+                     Manager::Light &l = lights[(size_t)i];
+                     for (int c = 0; c < 3; ++c)
+                         l.direction[c] = d[(one ? 0 : 3 * i) + c];
+                     if (!ambient.is_none())
+                         l.ambient = as ? av[0] : av[(size_t)i];
+                     if (!diffuse.is_none())
+                         l.diffuse = ds ? dv[0] : dv[(size_t)i];
+                     checkLight(l);
+                 }
+                 if (!self.setWorldLights((uint32_t)first_world, (uint32_t)n, lights.data()))
+                     throw py::value_error(mrx_last_error());
+             },
+             py::arg("direction"), py::arg("ambient") = py::none(), py::arg("diffuse") = py::none(),
+             py::arg("first_world") = 0)
+        .def("world_light",
+             [](Manager &self) {
+                 const uint32_t n = self.numWorlds();
+                 std::vector<Manager::Light> lights(n);
+                 self.worldLights(0, n, lights.data());
+                 py::array_t<float> d({ (py::ssize_t)n, (py::ssize_t)3 }), a(n), f(n);
+                 for (uint32_t i = 0; i < n; ++i) {
+                     for (int c = 0; c < 3; ++c)
+                         d.mutable_at(i, c) = lights[i].direction[c];
+                     a.mutable_at(i) = lights[i].ambient;
+                     f.mutable_at(i) = lights[i].diffuse;
+                 }
+                 return py::make_tuple(d, a, f);
+             })
         .def("camera_projection",
              [](Manager &self) {
                  const uint32_t n = self.numViews();

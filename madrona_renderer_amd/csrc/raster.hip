@@ -50,8 +50,11 @@ struct TileCtx {
     int lx, ly;
 };
 
+// PV: the per-view form -- `lt` receives the light of the view's world from its record, read
+// beside the camera rotation it is combined with; else the uniform light of the kernel arguments.
+template <bool PV>
 __device__ __forceinline__ bool tileSetup(const RasterParams &p, uint32_t item, int lane,
-                                          TileCtx &t, ViewConst &vc)
+                                          TileCtx &t, ViewConst &vc, ViewLight &lt)
 {
     const uint32_t tilesPerView = p.tilesFast * p.tilesSlow;
     if (item >= p.numViews * tilesPerView)
@@ -61,12 +64,18 @@ __device__ __forceinline__ bool tileSetup(const RasterParams &p, uint32_t item, 
     t.tileX0 = (tile % p.tilesFast) * 64u;
     t.tileY0 = (tile / p.tilesFast) * 64u;
     const float4 q = *reinterpret_cast<const float4 *>(p.camRot + 4 * t.view);
+    // (a wave renders tiles of one view: the index is wave-uniform, the record a scalar load)
+    if (PV)
+        lt = viewLightOf(p, true, __builtin_amdgcn_readfirstlane(t.view));
     quatToMat(q.x, q.y, q.z, q.w, vc.Rc);
 #pragma unroll
     for (int r = 0; r < 3; ++r) {
         vc.c[r] = p.camPos[3 * t.view + r];
-        vc.lv[r] = dot3(vc.Rc[0][r], vc.Rc[1][r], vc.Rc[2][r],
-                        p.toLight[0], p.toLight[1], p.toLight[2]);
+        if (PV)
+            vc.lv[r] = dot3(vc.Rc[0][r], vc.Rc[1][r], vc.Rc[2][r], lt.toLight[0], lt.toLight[1], lt.toLight[2]);
+        else
+            vc.lv[r] = dot3(vc.Rc[0][r], vc.Rc[1][r], vc.Rc[2][r],
+                            p.toLight[0], p.toLight[1], p.toLight[2]);
     }
     // wave-uniform: park the view constants in SGPRs
 #pragma unroll
@@ -96,23 +105,24 @@ struct GroupSetupArgs {
     int32_t transposed;
 };
 
-// setupTriangle under the projection constants `pr` of the view (per-view form)
-__device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const ViewProj &pr, const ViewConst &vc,
-                                                  WorldTri wt, int32_t kWorld, TriPlanes &out, float *shade, float *cold)
+// setupTriangle under the projection constants `pr` of the view and the light `lt` of its world (per-view form)
+__device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const ViewProj &pr, const ViewLight &lt,
+                                                  const ViewConst &vc, WorldTri wt, int32_t kWorld, TriPlanes &out,
+                                                  float *shade, float *cold)
 {
     const GroupSetupArgs sa = { p.tris, p.triMats, p.instPos, p.instRot, p.instScale,
-                                pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, p.ambient, p.diffuse, p.transposed };
+                                pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse, p.transposed };
     InstXform x;
     instanceTransform(sa, vc, wt.inst, x);
     return setupTriangleCore(sa, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold);
 }
 
 // S for one chunk of up to 64 world-triangles; returns the valid-lane mask.
-// PV: the per-view form, the view's projection constants in `pr`.
+// PV: the per-view form, the view's projection constants in `pr` and its world's light in `lt`.
 template <bool PV>
 __device__ __forceinline__ uint64_t setupChunk(const RasterParams &p, const ViewConst &vc,
                                                const TileCtx &t, uint32_t chunk, int lane,
-                                               WaveLds &L, const ViewProj &pr)
+                                               WaveLds &L, const ViewProj &pr, const ViewLight &lt)
 {
     bool valid = false;
     const uint32_t k = chunk + lane;
@@ -120,7 +130,7 @@ __device__ __forceinline__ uint64_t setupChunk(const RasterParams &p, const View
         const WorldTri wt = p.viewTris[t.triBegin + k];
         TriPlanes c;
         float *h = L.hot[lane];
-        valid = PV ? setupTriangleProj(p, pr, vc, wt, (int32_t)k, c, h + 12, L.cold[lane])
+        valid = PV ? setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, h + 12, L.cold[lane])
                    : setupTriangle(p, vc, wt, (int32_t)k, c, h + 12, L.cold[lane]);
         h[0] = c.A0; h[1] = c.B0; h[2] = c.C0;
         h[3] = c.A1; h[4] = c.B1; h[5] = c.C1;
@@ -198,7 +208,8 @@ __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
     const int lane = threadIdx.x % kWave;
     TileCtx t;
     ViewConst vc;
-    if (!tileSetup(p, blockIdx.x * kWavesPerBlock + wave, lane, t, vc))
+    ViewLight lt = {};
+    if (!tileSetup<PV>(p, blockIdx.x * kWavesPerBlock + wave, lane, t, vc, lt))
         return;
     WaveLds &L = lds[wave];
     const ViewProj pr = viewProjOf(p, PV, t.view);
@@ -211,7 +222,7 @@ __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
 
     uint64_t mask0 = 0;
     if (!MULTI)
-        mask0 = setupChunk<PV>(p, vc, t, 0, lane, L, pr);
+        mask0 = setupChunk<PV>(p, vc, t, 0, lane, L, pr, lt);
 
     for (int band = 0; band < 4; ++band) {
         float best[kBlocksPerBand];
@@ -237,7 +248,7 @@ __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
                                       (b >> 3) ? py1 : py0, outRgba[b], outId[b]);
         } else {
             for (uint32_t chunk = 0; chunk < t.numTris; chunk += kChunk) {
-                const uint64_t mask = setupChunk<PV>(p, vc, t, chunk, lane, L, pr);
+                const uint64_t mask = setupChunk<PV>(p, vc, t, chunk, lane, L, pr, lt);
                 rasterBandBrute(L, mask, pxf, py0, py1, invNear, best, bid);
                 // resolve this chunk's winners before its records are replaced
 #pragma unroll
@@ -475,7 +486,8 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
     const int lane = threadIdx.x % kWave;
     TileCtx t;
     ViewConst vc;
-    if (!tileSetup(p, blockIdx.x, lane, t, vc))
+    ViewLight lt = {};
+    if (!tileSetup<PV>(p, blockIdx.x, lane, t, vc, lt))
         return;                                   // whole workgroup leaves together
     // per-view projection: a wave-uniform runtime guard -- a workgroup renders one tile of one view
     const ViewProj pr = viewProjOf(p, PV, t.view);
@@ -513,7 +525,7 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
                 if (k < t.numTris && !(p.debugSkip & 8u)) {
                     const WorldTri wt = p.viewTris[t.triBegin + k];
                     if (PV)
-                        valid = setupTriangleProj(p, pr, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
+                        valid = setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
                     else
                         valid = setupTriangle(p, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
                 }
@@ -776,7 +788,9 @@ constexpr int groupWaves(bool tex) { return tex ? 4 : 8; }
 // OUT (raster.hpp OutSel): the output selection of the instantiation.
 // PV: per-view projection: the set-up lanes read their view's record, S2 and phase R the 1/znear of
 // each tile's view, which the last wave leaves in LDS beside the tile's place.
-template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT, bool PV = false>
+// LT (with PV): the worlds' lights differ too: the set-up lanes read their view's light record beside
+// the camera; without it the per-view form takes the uniform light of the kernel arguments.
+template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT, bool PV = false, bool LT = false>
 __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances,
                                                 uint32_t hPool, uint32_t hShape, uint32_t hGroups, uint32_t hPrefix,
                                                 uint32_t hFirst01, uint32_t hFirst23, const RasterParams p)
@@ -962,6 +976,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             numTris = viewOk ? p.viewTriCount[view] : 0u;
         }
         ViewConst vc;
+        // (LT: the light of the lane's view, a vector load beside the camera's -- the lanes span views)
+        const ViewLight lt = viewLightOf(p, PV && LT, view);
         {
             const float4 q = *reinterpret_cast<const float4 *>(aCamRot + 4 * view);
             quatToMat(q.x, q.y, q.z, q.w, vc.Rc);
@@ -969,7 +985,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             for (int r = 0; r < 3; ++r) {
                 vc.c[r] = aCamPos[3 * view + r];
                 vc.lv[r] = dot3(vc.Rc[0][r], vc.Rc[1][r], vc.Rc[2][r],
-                                p.toLight[0], p.toLight[1], p.toLight[2]);
+                                lt.toLight[0], lt.toLight[1], lt.toLight[2]);
             }
         }
         TriPlanes c;
@@ -989,7 +1005,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                     FAST ? reinterpret_cast<const float *>(hPose + lay.instPos) : p.instPos,
                     FAST ? reinterpret_cast<const float *>(hPose + lay.instRot) : p.instRot,
                     FAST ? reinterpret_cast<const float *>(hPose + lay.instScale) : p.instScale,
-                    pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, p.ambient, p.diffuse, p.transposed };
+                    pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse, p.transposed };
                 InstXform x;
                 instanceTransform(sa, vc, wt.inst, x);
                 valid = setupTriangleCore<true, OUT != kOutDepth>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
@@ -1261,6 +1277,28 @@ void rasterGroupKernelFastPV(const char *hPose, const char *hGeom, uint32_t hVie
                                                            hFirst01, hFirst23, p);
 }
 
+// The per-view form with the light table (p.lightTable): instantiations of their own, so that batches
+// whose projections alone differ keep the kernels above.  Untextured: six waves per SIMD -- three workgroups of eight
+// waves -- where the others have eight.  The set-up lanes span views, so the five words of the light are per lane, on
+// top of the five of the projection: with them the set-up wants 68 - 69 registers, and held to the 64 of eight waves
+// it spills five to fifteen of them to scratch wherever the loads are placed.
+template <bool IDS, int SLOTS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : 6)
+void rasterGroupKernelPVL(const RasterParams p)
+{
+    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
+}
+
+template <bool IDS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 6)
+void rasterGroupKernelFastPVL(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
+                              uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
+                              const RasterParams p)
+{
+    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, true, true>(hPose, hGeom, hViews, hInstances, hPool, hShape, hGroups,
+                                                                 hPrefix, hFirst01, hFirst23, p);
+}
+
 }  // namespace
 
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
@@ -1405,7 +1443,20 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
 #define MRX_GROUP_ARGS h.pose, h.geom, h.views, h.instances, h.poolTris, h.shape, h.groups, h.prefix, h.first01, h.first23, q
 #define MRX_GROUP_O(S, X, O, OP)                                               \
     do {                                                                       \
-        if (pv) {                                                              \
+        if (pv && p.lightTable) {                                              \
+            if (fast && S == 16) {                                             \
+                if (ids) { if (p.anyTextured) rasterGroupKernelFastPVL<true, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);    \
+                           else rasterGroupKernelFastPVL<true, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }               \
+                else     { if (p.anyTextured) rasterGroupKernelFastPVL<false, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
+                           else rasterGroupKernelFastPVL<false, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }              \
+            } else if (ids) {                                                  \
+                if (p.anyTextured) rasterGroupKernelPVL<true, S, true><<<grid, gblock, 0, stream>>>(q);                             \
+                else               rasterGroupKernelPVL<true, S, false><<<grid, gblock, 0, stream>>>(q);                            \
+            } else {                                                           \
+                if (p.anyTextured) rasterGroupKernelPVL<false, S, true><<<grid, gblock, 0, stream>>>(q);                            \
+                else               rasterGroupKernelPVL<false, S, false><<<grid, gblock, 0, stream>>>(q);                           \
+            }                                                                  \
+        } else if (pv) {                                                       \
             if (fast && S == 16) {                                             \
                 if (ids) { if (p.anyTextured) rasterGroupKernelFastPV<true, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);    \
                            else rasterGroupKernelFastPV<true, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }               \

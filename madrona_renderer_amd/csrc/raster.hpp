@@ -19,6 +19,17 @@ struct alignas(32) ViewProj {
 };
 static_assert(sizeof(ViewProj) == 32, "ViewProj is one 32-byte record");
 
+// Per-world light, expanded by the host to one record per view (DESIGN.md S4 / S7 per world, 4.12): the unit vector
+// towards the light and the two S7 constants as mrx_light_constants resolves them, in the device table
+// RasterParams::viewLight.  Per view and not per world: a kernel indexes it with the view it already has, beside
+// the camera rotation the direction is combined with, without a viewWorld[] load in front.
+struct alignas(32) ViewLight {
+    float toLight[3];
+    float ambient, diffuse;
+    float pad[3];
+};
+static_assert(sizeof(ViewLight) == 32, "ViewLight is one 32-byte record");
+
 // Object-space triangle: 16 dwords, one 64-byte line.
 struct alignas(16) ObjTri {
     float p[9];      // 3 vertices x xyz
@@ -176,6 +187,13 @@ struct RasterParams {
     // above, view by view; null = the uniform form (every view uses the kernel-argument constants).  The
     // launchers pick the kernels' per-view instantiations from it.
     const ViewProj *viewProj;
+    // Per-world light, one record per view: set together with viewProj -- the per-view
+    // instantiations read both tables, and the host fills the one that does not vary with the uniform values.
+    // Null with viewProj: the uniform form (toLight / ambient / diffuse above).
+    const ViewLight *viewLight;
+    // 1: the worlds' lights differ (the group kernels then launch the per-view instantiations that read viewLight;
+    // where only projections differ they keep the ones that take the uniform light above); 0 otherwise
+    uint32_t lightTable;
 };
 
 // ---- the argument header of the group kernel's fast prologue (raster.hip, FAST) -------------------------------------

@@ -321,6 +321,25 @@ __device__ __forceinline__ ViewProj viewProjOf(const PARAMS &p, bool perView, ui
     return r;
 }
 
+// The light of a view's world, as viewProjOf: the view's record of the per-view table when
+// `perView`, else the uniform light of the kernel arguments.  Scalar loads where the view is wave-uniform.
+typedef const __attribute__((address_space(4))) ViewLight *ConstViewLight;
+template <typename PARAMS>
+__device__ __forceinline__ ViewLight viewLightOf(const PARAMS &p, bool perView, uint32_t view)
+{
+    ViewLight r;
+    if (perView) {
+        const ConstViewLight t = (ConstViewLight)p.viewLight + view;
+        r.toLight[0] = t->toLight[0]; r.toLight[1] = t->toLight[1]; r.toLight[2] = t->toLight[2];
+        r.ambient = t->ambient; r.diffuse = t->diffuse;
+    } else {
+        r.toLight[0] = p.toLight[0]; r.toLight[1] = p.toLight[1]; r.toLight[2] = p.toLight[2];
+        r.ambient = p.ambient; r.diffuse = p.diffuse;
+    }
+    r.pad[0] = r.pad[1] = r.pad[2] = 0.0f;
+    return r;
+}
+
 // S8: nearest texel, repeat addressing, v up.
 __device__ __forceinline__ uint32_t shadeTextured(const RasterParams &p,
                                                   const float *cold, int32_t tex,

@@ -43,6 +43,9 @@ class SceneDesc:
     # per-camera projection, parallel to `cameras`: [(vfov_deg, znear or None)]; None = every camera (90, None),
     # znear None = the mode's default (a view takes its camera row's projection, as it takes its pose)
     camera_projections: list = None
+    # per-world directional light: [(direction xyz, ambient, diffuse)], one per world; None = every world the
+    # default ((1, -1, -0.05), 0.25, 0.75).  Every view of a world takes its world's light.
+    world_lights: list = None
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -248,6 +251,10 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
     extra = {}
     if device_ids is not None:
         extra["device_ids"] = [int(d) for d in device_ids]
+    if desc.world_lights is not None:
+        if len(desc.world_lights) != desc.num_worlds:
+            raise ValueError("world_lights needs one (direction, ambient, diffuse) per world")
+        extra["world_lights"] = [([float(x) for x in d], float(a), float(f)) for d, a, f in desc.world_lights]
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:
