@@ -90,6 +90,11 @@ public:
         const CameraProjection *cameraProjections = nullptr;
         // [numWorlds] lights (nullptr: every world the default light); every view of a world takes its world's.
         const Light *worldLights = nullptr;
+        // Per-instance colour override (MRX_FLAG_INSTANCE_COLORS): [numInstances][4] bytes (r, g, b, a) parallel to
+        // rcfg.importedInstances, the initial values of instanceColorTensor(); a == 0 = the material colour.
+        // nullptr with instanceColorColumn: a zero-filled column; nullptr without: no column.
+        const uint8_t *instanceColors = nullptr;
+        bool instanceColorColumn = false;
     };
 
     // Aborts (FATAL-style, like the reference) when construction fails.
@@ -122,6 +127,9 @@ public:
     // (the ObjectID column, src/sim.cpp:152-156; src/sim.inl:5-16)
     madrona::py::Tensor instanceObjectTensor(uint32_t shard = 0) const;
     madrona::py::Tensor instanceScaleTensor(uint32_t shard = 0) const;
+    // u8 [instances, 4], mutable: the colour override (r, g, b, a) of every row, a == 0 = none (upstream's
+    // per-renderable colour override; needs Config::instanceColors or instanceColorColumn)
+    madrona::py::Tensor instanceColorTensor(uint32_t shard = 0) const;
     // binds every row to the (non-negative) object id its ObjectID column now holds: a spare
     // row gets its geometry, an existing row swaps it (makeEntityRenderable at run time,
     // src/sim.inl:5-8); waits for the device

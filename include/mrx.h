@@ -116,7 +116,11 @@ enum {
      * mrx_buffer_shard / mrx_copy_to_host on it fail with MRX_E_UNSUPPORTED.  The segmask (Raytracer
      * mode) and the visibility ids are written under every setting.  Both bits together: MRX_E_INVALID. */
     MRX_FLAG_NO_RGB = 1u << 2,      /* depth only */
-    MRX_FLAG_NO_DEPTH = 1u << 3     /* rgb only   */
+    MRX_FLAG_NO_DEPTH = 1u << 3,    /* rgb only   */
+    /* per-instance colour override: allocates the MRX_BUF_INSTANCE_COLOR column, zero-filled, and selects the launch
+     * forms that read it.  Without it nothing is allocated, mrx_buffer / mrx_buffer_shard /
+     * mrx_copy_to_host on the column fail with MRX_E_UNSUPPORTED and every launch is the one it always was. */
+    MRX_FLAG_INSTANCE_COLORS = 1u << 4
 };
 
 /* Manager::Config + Config::RenderConfig, /root/reference/src/mgr.hpp:49-88.
@@ -174,10 +178,20 @@ typedef struct {
     /* -- per-world light (a caller that sets struct_size to one of the sizes below passes none): [num_worlds]
      * entries parallel to `worlds`, NULL = every world the default light.  Every view of a world takes its world's. */
     const mrx_light *world_lights;
+    /* -- per-instance colour override (a caller that sets struct_size to one of the sizes below passes none):
+     * [num_instances][4] bytes (r, g, b, a) parallel to `instances`, the initial values of MRX_BUF_INSTANCE_COLOR --
+     * expanded per world as the poses are, so worlds that alias rows get the same colours.  NULL = all zero;
+     * non-NULL implies MRX_FLAG_INSTANCE_COLORS. */
+    const uint8_t *instance_colors;
+    /* reserved, must be zero.  (It also keeps sizeof(mrx_config) away from MRX_CONFIG_V4_LIGHT_SIZE + 8: a caller built
+     * against the struct as it was before instance_colors that overstates its size by one pointer is still refused,
+     * not read past its end.) */
+    uint64_t reserved0;
 } mrx_config;
 #define MRX_CONFIG_V2_SIZE ((uint32_t)offsetof(mrx_config, device_ids))
 #define MRX_CONFIG_V4_SIZE ((uint32_t)offsetof(mrx_config, camera_projections))
 #define MRX_CONFIG_V4_PROJ_SIZE ((uint32_t)offsetof(mrx_config, world_lights))
+#define MRX_CONFIG_V4_LIGHT_SIZE ((uint32_t)offsetof(mrx_config, instance_colors))
 
 typedef struct mrx_renderer mrx_renderer;
 
@@ -203,7 +217,15 @@ enum {
      * writing a different non-negative id changes neither) -- until
      * mrx_refresh_objects() re-binds the rows to the ids the column holds. */
     MRX_BUF_INSTANCE_OBJECT = 9,
-    MRX_NUM_BUFFERS = 10
+    /* u8 [instances,4], mutable, needs MRX_FLAG_INSTANCE_COLORS: the colour override (r, g, b, a) of every row
+     * (upstream's per-renderable colour override column).  a == 0: the row's triangles shade with their material
+     * colour; a != 0: with (r, g, b) / 255 in its place (textured triangles are modulated by it).
+     * The value of a beyond zero / non-zero is not interpreted, output alpha stays 255.  It changes colour only --
+     * never which kernel runs, visibility, depth or the segmask -- and belongs to the row: it stays through hiding
+     * (a negative ObjectID) and through mrx_refresh_objects(); spare rows start at 0.  Written on the device, like a
+     * pose, on the renderer's stream; a depth-only renderer never reads it. */
+    MRX_BUF_INSTANCE_COLOR = 10,
+    MRX_NUM_BUFFERS = 11
 };
 
 enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2 };

@@ -912,7 +912,25 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     const SetupArgs sa = { pk->tris, pk->triMats, PV ? pr.sx : pk->sx, PV ? pr.ox : pk->ox, PV ? pr.sz : pk->sz,
                                            PV ? pr.oz : pk->oz, PV ? pr.s6bPad : pk->s6bPad, PV ? lr->ambient : pk->ambient,
                                            PV ? lr->diffuse : pk->diffuse, pk->transposed };
-                    const bool valid = setupTriangleCore<false>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold);
+                    // (PV, a renderer with the colour column -- a wave-uniform test: the override of the triangle's row,
+                    // DESIGN.md 4.13; e.x counts from the first row of the pass -- MULTI: of the world of `view`)
+                    uint32_t icol = 0u;
+                    if (PV) {
+                        const uint32_t *colors = pk->instColor;
+                        if (colors) {
+                            uint32_t rowBase = passBase;
+                            if (MULTI) {
+                                // (viewInstances of `view`, from the argument segment)
+                                const uint32_t uni = pk->bvhUniInst, cams = pk->bvhUniCams;
+                                if (uni)
+                                    rowBase = (cams != 1u ? view / cams : view) * uni;
+                                else
+                                    rowBase = pk->worldInstStart[pk->viewWorld[view]];
+                            }
+                            icol = colors[rowBase + e.x];
+                        }
+                    }
+                    const bool valid = setupTriangleCore<false, true, PV>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold, icol);
                     live = valid && c.bbX1 >= TX0 && c.bbX0 <= TX1 && c.bbY1 >= TY0 && c.bbY0 <= TY1;
                     // The planes at the tile's corners: fl(A x + fl(B y + C)) is monotone in x and in
                     // y, so its extreme over the tile's pixels is taken at a corner pixel, and a
@@ -1435,7 +1453,7 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
         const ViewLight lt = viewLightOf(p, PV, view);
         InstXform y;
         int32_t objL = -1;
-        uint32_t myTri = 0;
+        uint32_t myTri = 0, myRow = 0;
         bool hasT = false;
         if (p.uniInstances != 0) {
             // ---- uniform worlds (every world the same <= 4 objects in the same order: every BASELINE scene): which row
@@ -1451,6 +1469,7 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
             myTri = hasT ? ft + (k - pre) : 0u;
             const uint32_t row = world * p.uniInstances + i;
             objL = p.instObj[row];
+            myRow = row;
             instanceTransform(p, vc, row, y);
         } else {
         // ---- phase I, lane = instance row of the view's world
@@ -1500,6 +1519,7 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
             y.qo[0] = a3.x; y.qo[1] = a3.y; y.qo[2] = a3.z; y.det = a3.w;
             y.sc[0] = a4.x; y.sc[1] = a4.y; y.sc[2] = a4.z;
             objL = __float_as_int(a4.w);
+            myRow = i0 + myInst;
         }
         }
         TriPlanes c;
@@ -1511,7 +1531,10 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
             if (PV) {
                 const SetupArgs sa = { p.tris, p.triMats, pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse,
                                        p.transposed };
-                valid = setupTriangleCore<false, OUT != kOutDepth>(sa, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
+                // (a renderer with the colour column -- a wave-uniform test: the override of the triangle's row, 4.13)
+                const uint32_t icol = (OUT != kOutDepth && p.instColor) ? p.instColor[myRow] : 0u;
+                valid = setupTriangleCore<false, OUT != kOutDepth, true>(sa, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold,
+                                                                         icol);
             } else {
                 valid = setupTriangleCore<false, OUT != kOutDepth>(p, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
             }

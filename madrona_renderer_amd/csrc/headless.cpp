@@ -7,6 +7,7 @@
 //                     [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb]
 //                     [--vfov DEG] [--znear Z]   (every camera's projection; no counterpart upstream)
 //                     [--light X,Y,Z[,AMBIENT,DIFFUSE]]   (every world's directional light; no counterpart upstream)
+//                     [--instance-colors SEED]   (an opaque colour override per instance row, splitmix64(SEED, row))
 //
 // --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
 // renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
@@ -26,6 +27,7 @@
 // a scene (headless.cpp:48-55 passes no rcfg); here the scene is either the
 // synthetic cube+plane worlds of the benchmark or the reference's demo scene
 // (viewer.cpp:74-164 / scripts/test.py:11-130).
+#include <cerrno>
 #include <chrono>
 #include <cmath>
 #include <cstdio>
@@ -62,6 +64,9 @@ struct Args {
     // --light X,Y,Z[,AMBIENT,DIFFUSE]: the light of every world (the direction it travels; ambient, diffuse >= 0)
     bool hasLight = false;
     Manager::Light light = { { 1.0f, -1.0f, -0.05f }, 0.25f, 0.75f };
+    // --instance-colors SEED: every instance row overridden with an opaque colour drawn from the seed and the row
+    bool hasColors = false;
+    uint64_t colorSeed = 0;
 };
 
 // a number of the whole argument, finite
@@ -80,7 +85,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -138,6 +143,16 @@ Args parse(int argc, char **argv)
             }
             a.light = { { v[0], v[1], v[2] }, v[3], v[4] };
             a.hasLight = true;
+        } else if (!std::strcmp(argv[i], "--instance-colors") && i + 1 < argc) {
+            const char *s = argv[++i];
+            char *end = nullptr;
+            errno = 0;
+            a.colorSeed = std::strtoull(s, &end, 0);
+            if (!*s || *s == '-' || *s == '+' || *end || errno != 0) {
+                std::fprintf(stderr, "--instance-colors: not an unsigned integer seed: %s\n", s);
+                std::exit(EXIT_FAILURE);
+            }
+            a.hasColors = true;
         } else if (!std::strcmp(argv[i], "--znear") && i + 1 < argc) {
             a.znear = parseFloat("--znear", argv[++i]);
             if (!(a.znear > 0.0f)) {
@@ -165,6 +180,14 @@ Args parse(int argc, char **argv)
         std::exit(EXIT_FAILURE);
     }
     return a;
+}
+
+uint64_t splitmix64(uint64_t x)
+{
+    uint64_t z = x + 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
 }
 
 // u(k) = (splitmix64(seed ^ k) >> 40) * 2^-24
@@ -388,6 +411,16 @@ int main(int argc, char **argv)
     const std::vector<Manager::Light> lights(args.numWorlds, args.light);
     if (args.hasLight)
         cfg.worldLights = lights.data();
+    // --instance-colors: row i of the instance table gets (r, g, b) = the low bytes of splitmix64(splitmix64(SEED) ^ i)
+    std::vector<uint8_t> colors;
+    if (args.hasColors) {
+        const uint64_t base = splitmix64(args.colorSeed);
+        for (uint64_t i = 0; i < s.instances.size(); ++i) {
+            const uint64_t z = splitmix64(base ^ i);
+            colors.insert(colors.end(), { (uint8_t)z, (uint8_t)(z >> 8), (uint8_t)(z >> 16), (uint8_t)255 });
+        }
+        cfg.instanceColors = colors.data();
+    }
     rc.worlds = s.worlds.data();
     if (args.gpus > 1) {
         cfg.deviceIDs = devices.data();

@@ -98,6 +98,9 @@ Manager::Manager(const Config &cfg)
     c.camera_projections = reinterpret_cast<const mrx_projection *>(cfg.cameraProjections);
     static_assert(sizeof(mrx_light) == sizeof(Light), "light ABI");
     c.world_lights = reinterpret_cast<const mrx_light *>(cfg.worldLights);
+    c.instance_colors = cfg.instanceColors;
+    if (cfg.instanceColorColumn)
+        c.flags |= MRX_FLAG_INSTANCE_COLORS;
     if (cfg.renderOutputs == RenderOutputs::Depth)
         c.flags |= MRX_FLAG_NO_RGB;
     else if (cfg.renderOutputs == RenderOutputs::RGB)
@@ -145,6 +148,7 @@ Tensor Manager::visibilityTensor(uint32_t shard) const { return impl_->wrap(MRX_
 
 Tensor Manager::instanceObjectTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_OBJECT, shard); }
 Tensor Manager::instanceScaleTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_SCALE, shard); }
+Tensor Manager::instanceColorTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_COLOR, shard); }
 
 Tensor Manager::instancePositionTensor(uint32_t shard) const
 {

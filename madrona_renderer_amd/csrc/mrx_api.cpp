@@ -327,6 +327,9 @@ struct mrx_renderer {
     DevBuf<uint8_t> poseBlock, geomBlock;
     DevBuf<float> instPos, instRot, instScale, camPos, camRot;
     DevBuf<int32_t> instObj;
+    // the colour override column (MRX_FLAG_INSTANCE_COLORS): the slice of the pose block behind
+    // instObj; no pointer without the flag
+    DevBuf<uint32_t> instColor;
     DevBuf<uint32_t> rgb;
     DevBuf<float> depth;
     DevBuf<int32_t> ids;
@@ -412,7 +415,7 @@ struct mrx_renderer {
         tris.release(); triMats.release(); textures.release(); texels.release();
         viewTris.release(); viewTriCount.release();
         instPos.release(); instRot.release(); instScale.release();
-        camPos.release(); camRot.release(); instObj.release();
+        camPos.release(); camRot.release(); instObj.release(); instColor.release();
         projDev.release();
         lightDev.release();
         if (projStage)
@@ -1137,6 +1140,9 @@ int bindGeometry(mrx_renderer &r)
 // did).  Views or worlds that differ: both tables, one record per view, are copied to the device on the renderer's
 // stream, behind every render enqueued so far and ahead of every later one, and the kernels' per-view instantiations
 // read them; the table of whichever does not vary holds the uniform values.
+// A renderer that shades with the colour column (params.instColor) always launches with the tables:
+// the chunked, brute and BVH kernels read the column in their per-view instantiations.  params.tablesVary tells the
+// group kernels, which have a colour form over the uniform constants, whether the tables hold anything else.
 int applyViewTables(mrx_renderer &r)
 {
     mrx::RasterParams &p = r.params;
@@ -1166,13 +1172,14 @@ int applyViewTables(mrx_renderer &r)
         p.toLight[k] = lc.toLight[k];
     p.ambient = lc.ambient;
     p.diffuse = lc.diffuse;
-    if (uniform) {
+    const size_t n = r.proj.size();
+    p.tablesVary = uniform ? 0u : 1u;
+    if (uniform && !(p.instColor && n)) {
         p.viewProj = nullptr;
         p.viewLight = nullptr;
         p.lightTable = 0;
         return MRX_OK;
     }
-    const size_t n = r.proj.size();
     MRX_HIP(hipSetDevice(r.device));
     if (!r.projDev.ptr) {
         MRX_HIP(r.projDev.alloc(n, 256));
@@ -1392,6 +1399,9 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     //      an object by writing its id and calling mrx_refresh_objects.
     std::vector<float> instPos, instRot, instScale, camPos, camRot;
     std::vector<int32_t> instObj;
+    // (the colour column, with the flag: a row's four bytes, or zero for all of them and for spare rows)
+    const bool wantColors = (cfg.flags & MRX_FLAG_INSTANCE_COLORS) != 0;
+    std::vector<uint32_t> instColor;
     std::vector<uint32_t> &worldInstStart = r.worldInstStartHost, &viewWorld = r.viewWorldHost;
     worldInstStart.assign(1, 0u);
     viewWorld.clear();
@@ -1416,12 +1426,17 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
                 instRot.insert(instRot.end(), in.rotation, in.rotation + 4);
                 instScale.insert(instScale.end(), in.scale, in.scale + 3);
                 instObj.push_back(in.object_id);
+                uint32_t packed = 0;
+                if (cfg.instance_colors)
+                    std::memcpy(&packed, cfg.instance_colors + 4 * (size_t)(wi.instances_offset + i), 4);
+                instColor.push_back(packed);
             } else {
                 const float zero[3] = { 0.f, 0.f, 0.f }, ident[4] = { 1.f, 0.f, 0.f, 0.f }, one[3] = { 1.f, 1.f, 1.f };
                 instPos.insert(instPos.end(), zero, zero + 3);
                 instRot.insert(instRot.end(), ident, ident + 4);
                 instScale.insert(instScale.end(), one, one + 3);
                 instObj.push_back(-1);
+                instColor.push_back(0u);
             }
         }
         worldInstStart.push_back((uint32_t)instObj.size());
@@ -1478,8 +1493,10 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
         // pose block (the exported, user-mutable tensors are slices of it)
         const uint32_t nv = (uint32_t)viewWorld.size(), ni = (uint32_t)instObj.size();
         const PoseLayout lay = poseLayout(nv, ni);
-        MRX_HIP(r.poseBlock.alloc((size_t)lay.total + 256));
-        MRX_HIP(hipMemset(r.poseBlock.ptr, 0, (size_t)lay.total + 256));
+        // (the colour column, where there is one, behind the layout the FAST prologue relies on)
+        const size_t poseBytes = (size_t)lay.total + (wantColors ? mrxAlign256(ni * 4u) : 0u) + 256;
+        MRX_HIP(r.poseBlock.alloc(poseBytes));
+        MRX_HIP(hipMemset(r.poseBlock.ptr, 0, poseBytes));
         uint8_t *b = r.poseBlock.ptr;
         r.camRot.view(b + lay.camRot, camRot.size());
         r.camPos.view(b + lay.camPos, camPos.size());
@@ -1496,6 +1513,10 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
         MRX_HIP(up(r.instPos.ptr, instPos.data(), instPos.size() * 4));
         MRX_HIP(up(r.instScale.ptr, instScale.data(), instScale.size() * 4));
         MRX_HIP(up(r.instObj.ptr, instObj.data(), instObj.size() * 4));
+        if (wantColors) {
+            r.instColor.view(b + poseColorOffset(nv, ni), instColor.size());
+            MRX_HIP(up(r.instColor.ptr, instColor.data(), instColor.size() * 4));
+        }
     }
 
     const bool rt = cfg.render_mode == MRX_MODE_RAYTRACER;
@@ -1535,6 +1556,8 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     p.instRot = r.instRot.ptr;
     p.instScale = r.instScale.ptr;
     p.instObj = r.instObj.ptr;
+    // (a depth-only renderer never reads the column: it launches what a renderer without one does)
+    p.instColor = (cfg.flags & MRX_FLAG_NO_RGB) ? nullptr : r.instColor.ptr;
     p.camPos = r.camPos.ptr;
     p.camRot = r.camRot.ptr;
     p.rgb = r.rgb.ptr;
@@ -1683,7 +1706,7 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     inf.max_world_instances = maxWorldInst;
     inf.num_shards = 1;
     inf.bytes_per_step = (uint64_t)px * (4u * ((r.rgb.ptr ? 1u : 0u) + (r.depth.ptr ? 1u : 0u)) + (wantIds ? 4u : 0u)) +
-                         44ull * inf.num_instances + 28ull * nviews;
+                         (r.instColor.ptr ? 48ull : 44ull) * inf.num_instances + 28ull * nviews;
     return bindGeometry(r);
 }
 
@@ -2080,14 +2103,20 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
     *out = nullptr;
     // ABI 2 callers pass the struct without its trailing ABI 3 fields: those read as zero
     // (ABI 4 callers: the struct without camera_projections, MRX_CONFIG_V4_SIZE -- every camera the default -- or
-    // without world_lights, MRX_CONFIG_V4_PROJ_SIZE -- every world the default light)
+    // without world_lights, MRX_CONFIG_V4_PROJ_SIZE -- every world the default light -- or without instance_colors,
+    // MRX_CONFIG_V4_LIGHT_SIZE -- no initial colours)
     if (cfgIn->struct_size != sizeof(mrx_config) && cfgIn->struct_size != MRX_CONFIG_V2_SIZE &&
-        cfgIn->struct_size != MRX_CONFIG_V4_SIZE && cfgIn->struct_size != MRX_CONFIG_V4_PROJ_SIZE)
+        cfgIn->struct_size != MRX_CONFIG_V4_SIZE && cfgIn->struct_size != MRX_CONFIG_V4_PROJ_SIZE &&
+        cfgIn->struct_size != MRX_CONFIG_V4_LIGHT_SIZE)
         return fail(MRX_E_INVALID, "mrx_config size mismatch (ABI)");
     mrx_config full;
     std::memset(&full, 0, sizeof full);
     std::memcpy(&full, cfgIn, cfgIn->struct_size);
     full.struct_size = sizeof(mrx_config);
+    if (full.reserved0 != 0)
+        return fail(MRX_E_INVALID, "mrx_config.reserved0 must be zero");
+    if (full.instance_colors)
+        full.flags |= MRX_FLAG_INSTANCE_COLORS;
     const mrx_config *cfg = &full;
     if (cfg->render_mode != MRX_MODE_RASTERIZER && cfg->render_mode != MRX_MODE_RAYTRACER)
         return fail(MRX_E_INVALID, "bad render_mode");
@@ -2446,6 +2475,13 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
         break;
     case MRX_BUF_INSTANCE_OBJECT:     // ObjectID column (sim.cpp:152-156); negative = hidden
         dims[0] = I; *ndim = 1; *dtype = MRX_DTYPE_I32; ptr = r->instObj.ptr;
+        break;
+    case MRX_BUF_INSTANCE_COLOR:      // the colour override column; a == 0 = no override
+        dims[0] = I; dims[1] = 4; *ndim = 2; *dtype = MRX_DTYPE_U8; ptr = r->instColor.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED, "no instance colours: this renderer was created without MRX_FLAG_INSTANCE_COLORS");
+            return nullptr;
+        }
         break;
     // The reference sizes the camera tensors with totalNumInstances
     // (mgr.cpp:652,662); the rows that exist are one per camera, exported so.

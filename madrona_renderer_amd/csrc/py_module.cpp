@@ -170,6 +170,12 @@ PYBIND11_MODULE(madrona_renderer, m)
 {
     m.doc() = "MI355X-native batch renderer with the madrona_renderer API";
     madRender::detail::setThrowOnError(true);
+    // the C ABI's names of the colour override column (include/mrx.h), as the library was built with them
+    m.attr("MRX_FLAG_INSTANCE_COLORS") = (uint32_t)MRX_FLAG_INSTANCE_COLORS;
+    m.attr("MRX_BUF_INSTANCE_COLOR") = (int)MRX_BUF_INSTANCE_COLOR;
+    m.attr("MRX_NUM_BUFFERS") = (int)MRX_NUM_BUFFERS;
+    m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
+    m.attr("MRX_CONFIG_SIZE") = (uint32_t)sizeof(mrx_config);
 
     py::enum_<Manager::RenderMode>(m, "RenderMode")
         .value("Rasterizer", Manager::RenderMode::Rasterizer)
@@ -286,7 +292,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<PyCamera> &pycameras,
                          const std::vector<Sim::WorldInit> &worlds,
                          const std::vector<int> &device_ids, int max_instances_per_world,
-                         Manager::RenderOutputs render_outputs, py::object world_lights) {
+                         Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors) {
                  if (mesh_vertices.size() && (mesh_vertices.ndim() != 2 || mesh_vertices.shape(1) != 3))
                      throw py::value_error("mesh_vertices must have shape [N, 3]");
                  if (mesh_uvs.size() && (mesh_uvs.ndim() != 2 || mesh_uvs.shape(1) != 2))
@@ -378,6 +384,17 @@ PYBIND11_MODULE(madrona_renderer, m)
                      }
                      cfg.worldLights = lights.data();
                  }
+                 // instance_colors: None (no column), True (a zero-filled one) or [num_instances, 4] uint8
+                 py::array_t<uint8_t, py::array::c_style | py::array::forcecast> colors;
+                 if (py::isinstance<py::bool_>(instance_colors)) {
+                     cfg.instanceColorColumn = instance_colors.cast<bool>();
+                 } else if (!instance_colors.is_none()) {
+                     colors = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(instance_colors);
+                     if (!colors || colors.ndim() != 2 || (size_t)colors.shape(0) != instances.size() || colors.shape(1) != 4)
+                         throw py::value_error("instance_colors must be None, True or a uint8 array of shape [num_instances, 4]");
+                     cfg.instanceColors = colors.data();
+                     cfg.instanceColorColumn = true;
+                 }
                  return new Manager(cfg);
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -394,7 +411,9 @@ PYBIND11_MODULE(madrona_renderer, m)
              py::arg("device_ids") = std::vector<int>(), py::arg("max_instances_per_world") = 0,
              py::arg("render_outputs") = Manager::RenderOutputs::RGBD,
              // world_lights = [(direction xyz, ambient, diffuse)] per world: the worlds' directional lights
-             py::arg("world_lights") = py::none())
+             py::arg("world_lights") = py::none(),
+             // instance_colors = True or a [num_instances, 4] uint8 array (r, g, b, a): the colour override column
+             py::arg("instance_colors") = py::none())
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -433,6 +452,12 @@ PYBIND11_MODULE(madrona_renderer, m)
         .def("instance_object_tensor",
              [](py::object self, py::object shard) {
                  return wrapTensor(self, self.cast<Manager &>().instanceObjectTensor(shardOf(self, shard)));
+             },
+             py::arg("shard") = py::none())
+        // u8 [instances, 4]: the colour override of every row, a == 0 = none (needs instance_colors=)
+        .def("instance_color_tensor",
+             [](py::object self, py::object shard) {
+                 return wrapTensor(self, self.cast<Manager &>().instanceColorTensor(shardOf(self, shard)));
              },
              py::arg("shard") = py::none())
         .def("instance_rotation_tensor",

@@ -105,7 +105,8 @@ struct GroupSetupArgs {
     int32_t transposed;
 };
 
-// setupTriangle under the projection constants `pr` of the view and the light `lt` of its world (per-view form)
+// setupTriangle under the projection constants `pr` of the view and the light `lt` of its world (per-view form), and
+// under the colour override of the instance row where the renderer has the column (a wave-uniform test)
 __device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const ViewProj &pr, const ViewLight &lt,
                                                   const ViewConst &vc, WorldTri wt, int32_t kWorld, TriPlanes &out,
                                                   float *shade, float *cold)
@@ -114,7 +115,8 @@ __device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const V
                                 pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse, p.transposed };
     InstXform x;
     instanceTransform(sa, vc, wt.inst, x);
-    return setupTriangleCore(sa, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold);
+    const uint32_t icol = p.instColor ? p.instColor[wt.inst] : 0u;
+    return setupTriangleCore<true, true, true>(sa, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold, icol);
 }
 
 // S for one chunk of up to 64 world-triangles; returns the valid-lane mask.
@@ -790,7 +792,8 @@ constexpr int groupWaves(bool tex) { return tex ? 4 : 8; }
 // each tile's view, which the last wave leaves in LDS beside the tile's place.
 // LT (with PV): the worlds' lights differ too: the set-up lanes read their view's light record beside
 // the camera; without it the per-view form takes the uniform light of the kernel arguments.
-template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT, bool PV = false, bool LT = false>
+// COL: per-instance colour override: the set-up lanes read their row's packed colour beside its ObjectID.
+template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT, bool PV = false, bool LT = false, bool COL = false>
 __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances,
                                                 uint32_t hPool, uint32_t hShape, uint32_t hGroups, uint32_t hPrefix,
                                                 uint32_t hFirst01, uint32_t hFirst23, const RasterParams p)
@@ -819,6 +822,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     const float *aCamRot = FAST ? reinterpret_cast<const float *>(hPose + lay.camRot) : p.camRot;
     const float *aCamPos = FAST ? reinterpret_cast<const float *>(hPose + lay.camPos) : p.camPos;
     const int32_t *aInstObj = FAST ? reinterpret_cast<const int32_t *>(hPose + lay.instObj) : p.instObj;
+    const uint32_t *aInstColor = FAST ? reinterpret_cast<const uint32_t *>(hPose + lay.total) : p.instColor;
     const uint32_t tilesPerView = FAST ? 1u : p.tilesFast * p.tilesSlow;
     // FAST, untextured (16 slots, one-tile views): S2 hands phase R ready-made work items (GroupLds::items).
     // The plain entry and the textured kernels keep the per-tile masks: measured slower with the items
@@ -1008,8 +1012,9 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                     pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse, p.transposed };
                 InstXform x;
                 instanceTransform(sa, vc, wt.inst, x);
-                valid = setupTriangleCore<true, OUT != kOutDepth>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
-                                                                  lds.shade[rec], lds.cold[rec]);
+                valid = setupTriangleCore<true, OUT != kOutDepth, COL>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
+                                                                       lds.shade[rec], lds.cold[rec],
+                                                                       COL ? aInstColor[wt.inst] : 0u);
             }
             MRX_STAMP(2);
             float4 *dst = reinterpret_cast<float4 *>(lds.planes[rec]);
@@ -1299,6 +1304,46 @@ void rasterGroupKernelFastPVL(const char *hPose, const char *hGeom, uint32_t hVi
                                                                  hPrefix, hFirst01, hFirst23, p);
 }
 
+// The colour forms (p.instColor), instantiations of their own so that a renderer without the column
+// launches what it always did: C over the uniform projection and light of the kernel arguments, PVLC over both tables
+// (batches whose projections alone differ take it too).  Output selection by pointer; a depth-only renderer has no
+// colour form -- it never reads the column.
+template <bool IDS, int SLOTS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : (SLOTS > 128 ? 6 : 8))
+void rasterGroupKernelC(const RasterParams p)
+{
+    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, false, false, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u,
+                                                                                 0u, p);
+}
+
+template <bool IDS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 8)
+void rasterGroupKernelFastC(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
+                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
+                            const RasterParams p)
+{
+    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, false, false, true>(hPose, hGeom, hViews, hInstances, hPool, hShape,
+                                                                             hGroups, hPrefix, hFirst01, hFirst23, p);
+}
+
+template <bool IDS, int SLOTS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : 6)
+void rasterGroupKernelPVLC(const RasterParams p)
+{
+    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, true, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u,
+                                                                               p);
+}
+
+template <bool IDS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 6)
+void rasterGroupKernelFastPVLC(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
+                               uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
+                               const RasterParams p)
+{
+    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, true, true, true>(hPose, hGeom, hViews, hInstances, hPool, hShape,
+                                                                           hGroups, hPrefix, hFirst01, hFirst23, p);
+}
+
 }  // namespace
 
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
@@ -1441,34 +1486,32 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
             h.first23 = p.uniFirstTri[2] | (p.uniFirstTri[3] << 16);
         }
 #define MRX_GROUP_ARGS h.pose, h.geom, h.views, h.instances, h.poolTris, h.shape, h.groups, h.prefix, h.first01, h.first23, q
+// (the forms over tables and / or colours: FK<IDS, TEX> the FAST entry, K<IDS, S, TEX> the plain one)
+#define MRX_GROUP_FORM(S, FK, K)                                               \
+    do {                                                                       \
+        if (fast && S == 16) {                                                 \
+            if (ids) { if (p.anyTextured) FK<true, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);    \
+                       else FK<true, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }               \
+            else     { if (p.anyTextured) FK<false, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
+                       else FK<false, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }              \
+        } else if (ids) {                                                      \
+            if (p.anyTextured) K<true, S, true><<<grid, gblock, 0, stream>>>(q);                          \
+            else               K<true, S, false><<<grid, gblock, 0, stream>>>(q);                         \
+        } else {                                                               \
+            if (p.anyTextured) K<false, S, true><<<grid, gblock, 0, stream>>>(q);                         \
+            else               K<false, S, false><<<grid, gblock, 0, stream>>>(q);                        \
+        }                                                                      \
+    } while (0)
 #define MRX_GROUP_O(S, X, O, OP)                                               \
     do {                                                                       \
-        if (pv && p.lightTable) {                                              \
-            if (fast && S == 16) {                                             \
-                if (ids) { if (p.anyTextured) rasterGroupKernelFastPVL<true, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);    \
-                           else rasterGroupKernelFastPVL<true, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }               \
-                else     { if (p.anyTextured) rasterGroupKernelFastPVL<false, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
-                           else rasterGroupKernelFastPVL<false, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }              \
-            } else if (ids) {                                                  \
-                if (p.anyTextured) rasterGroupKernelPVL<true, S, true><<<grid, gblock, 0, stream>>>(q);                             \
-                else               rasterGroupKernelPVL<true, S, false><<<grid, gblock, 0, stream>>>(q);                            \
-            } else {                                                           \
-                if (p.anyTextured) rasterGroupKernelPVL<false, S, true><<<grid, gblock, 0, stream>>>(q);                            \
-                else               rasterGroupKernelPVL<false, S, false><<<grid, gblock, 0, stream>>>(q);                           \
-            }                                                                  \
+        if (p.instColor && pv && p.tablesVary) {                               \
+            MRX_GROUP_FORM(S, rasterGroupKernelFastPVLC, rasterGroupKernelPVLC);                          \
+        } else if (p.instColor) {                                              \
+            MRX_GROUP_FORM(S, rasterGroupKernelFastC, rasterGroupKernelC);     \
+        } else if (pv && p.lightTable) {                                       \
+            MRX_GROUP_FORM(S, rasterGroupKernelFastPVL, rasterGroupKernelPVL); \
         } else if (pv) {                                                       \
-            if (fast && S == 16) {                                             \
-                if (ids) { if (p.anyTextured) rasterGroupKernelFastPV<true, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);    \
-                           else rasterGroupKernelFastPV<true, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }               \
-                else     { if (p.anyTextured) rasterGroupKernelFastPV<false, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
-                           else rasterGroupKernelFastPV<false, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }              \
-            } else if (ids) {                                                  \
-                if (p.anyTextured) rasterGroupKernelPV<true, S, true><<<grid, gblock, 0, stream>>>(q);                             \
-                else               rasterGroupKernelPV<true, S, false><<<grid, gblock, 0, stream>>>(q);                            \
-            } else {                                                           \
-                if (p.anyTextured) rasterGroupKernelPV<false, S, true><<<grid, gblock, 0, stream>>>(q);                            \
-                else               rasterGroupKernelPV<false, S, false><<<grid, gblock, 0, stream>>>(q);                           \
-            }                                                                  \
+            MRX_GROUP_FORM(S, rasterGroupKernelFastPV, rasterGroupKernelPV);   \
         } else if (fast && S == 16) {                                          \
             if (p.anyTextured) {                                               \
                 if (ids) rasterGroupKernelFast<true, true, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
@@ -1509,6 +1552,7 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
 #undef MRX_GROUP_ARGS
 #undef MRX_GROUP_X
 #undef MRX_GROUP_O
+#undef MRX_GROUP_FORM
 #undef MRX_GROUP
     }
     return hipGetLastError();

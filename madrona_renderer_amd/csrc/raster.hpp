@@ -194,6 +194,15 @@ struct RasterParams {
     // 1: the worlds' lights differ (the group kernels then launch the per-view instantiations that read viewLight;
     // where only projections differ they keep the ones that take the uniform light above); 0 otherwise
     uint32_t lightTable;
+    // 1: the projections or the lights above differ between views; 0 with viewProj set: the tables repeat the uniform
+    // values and are there for the instance colours alone (the group kernels then launch their uniform colour form)
+    uint32_t tablesVary;
+    // Per-instance colour override: [I] packed bytes (r, g, b, a), r lowest; a != 0 replaces
+    // material.rgb of the row's triangles by (r, g, b) / 255.  The slice of the pose block behind instObj
+    // (poseColorOffset); null = no column, or a depth-only renderer, which never reads it.  Set together with
+    // viewProj: the per-view instantiations of the chunked, brute and BVH kernels read it behind a null check, the
+    // group kernels have colour instantiations of their own.
+    const uint32_t *instColor;
 };
 
 // ---- the argument header of the group kernel's fast prologue (raster.hip, FAST) -------------------------------------
@@ -224,6 +233,9 @@ MRX_HD inline PoseLayout poseLayout(uint32_t views, uint32_t instances)
     l.total = l.instObj + mrxAlign256(instances * 4u);
     return l;
 }
+// the colour column of a renderer that has one (RasterParams::instColor): [instances] dwords behind the layout above,
+// whose offsets therefore do not move
+MRX_HD inline uint32_t poseColorOffset(uint32_t views, uint32_t instances) { return poseLayout(views, instances).total; }
 // geometry block: ObjTri[pool] at 0, TriMat[pool] at geomMatsOffset(pool)
 MRX_HD inline uint32_t geomMatsOffset(uint32_t poolTris) { return mrxAlign256(poolTris * 64u); }
 

@@ -130,14 +130,17 @@ __device__ __forceinline__ void instanceTransform(const PARAMS &p, const ViewCon
 // slot allocation.
 // COLOR = false (depth-only kernels): no colour work at all -- neither u/v planes nor the S7 lit
 // colour; shade[0] and cold[] are left unwritten, the rest of the record is as with COLOR = true.
+// ICOL: `icol` is the packed colour override (r, g, b, a bytes, r lowest) of the instance row: a
+// non-zero a replaces the material's rgb by (r, g, b) * (1 / 255) -- S8's texel constant, one multiply per channel --
+// in S7, hence in S8 too; the alpha slot (the segmask label) and everything but colour are untouched.
 // PARAMS: RasterParams, or any struct with the members read here (tris, triMats, s6bPad, sx, sz,
 // ox, oz, transposed, diffuse, ambient) -- the BVH kernel passes a copy it reads from the
 // kernel-argument segment batch by batch instead of holding the values in scalar registers.
-template <bool UVPLANES = true, bool COLOR = true, typename PARAMS = RasterParams>
+template <bool UVPLANES = true, bool COLOR = true, bool ICOL = false, typename PARAMS = RasterParams>
 __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (&lv)[3],
                                                   const InstXform &x, uint32_t tri, int32_t obj,
                                                   int32_t kWorld, TriPlanes &out,
-                                                  float *shade, float *cold)
+                                                  float *shade, float *cold, uint32_t icol = 0u)
 {
     const float (&MV)[3][3] = x.MV;
     const float (&tv)[3] = x.tv;
@@ -267,7 +270,13 @@ __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (
     if (d > 0.0f)
         ndl = -ndl;
     const float lit = __builtin_fmaf(p.diffuse, fmaxf(ndl, 0.0f), p.ambient);
-    const float l0 = lit * mc.x, l1 = lit * mc.y, l2 = lit * mc.z;
+    float mr = mc.x, mg = mc.y, mb = mc.z;
+    if (ICOL && (icol >> 24) != 0u) {
+        mr = (float)(icol & 255u) * (1.0f / 255.0f);
+        mg = (float)((icol >> 8) & 255u) * (1.0f / 255.0f);
+        mb = (float)((icol >> 16) & 255u) * (1.0f / 255.0f);
+    }
+    const float l0 = lit * mr, l1 = lit * mg, l2 = lit * mb;
     cold[6] = l0; cold[7] = l1; cold[8] = l2;
     const uint32_t rgba = toU8(l0) | (toU8(l1) << 8) | (toU8(l2) << 16) | 0xFF000000u;
     shade[0] = __uint_as_float(rgba);

@@ -46,6 +46,10 @@ class SceneDesc:
     # per-world directional light: [(direction xyz, ambient, diffuse)], one per world; None = every world the
     # default ((1, -1, -0.05), 0.25, 0.75).  Every view of a world takes its world's light.
     world_lights: list = None
+    # per-instance colour override, parallel to `instances`: [N, 4] uint8 (r, g, b, a); a == 0 leaves the row its
+    # material colour, any other a shades it with (r, g, b) / 255 instead.  None = no column; True = a zero-filled
+    # one (written later through instance_color_tensor()).  Worlds that alias rows share their colours.
+    instance_colors: object = None
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -255,6 +259,14 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
         if len(desc.world_lights) != desc.num_worlds:
             raise ValueError("world_lights needs one (direction, ambient, diffuse) per world")
         extra["world_lights"] = [([float(x) for x in d], float(a), float(f)) for d, a, f in desc.world_lights]
+    if desc.instance_colors is not None:
+        if desc.instance_colors is True:
+            extra["instance_colors"] = True
+        else:
+            colors = np.ascontiguousarray(desc.instance_colors, np.uint8)
+            if colors.shape != (len(desc.instances), 4):
+                raise ValueError("instance_colors needs one (r, g, b, a) per instance")
+            extra["instance_colors"] = colors
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:
