@@ -95,6 +95,12 @@ public:
         // nullptr with instanceColorColumn: a zero-filled column; nullptr without: no column.
         const uint8_t *instanceColors = nullptr;
         bool instanceColorColumn = false;
+        // Per-instance material override (MRX_FLAG_INSTANCE_MATERIALS): [numInstances] material ids parallel to
+        // rcfg.importedInstances, the initial values of instanceMaterialTensor(); an id outside the material table
+        // (-1, say) = the triangles' own materials.  Expanded per world as the poses are: worlds that alias rows
+        // share ids, spare rows get -1.  nullptr with instanceMaterialColumn: a column of -1; nullptr without: none.
+        const int32_t *instanceMaterials = nullptr;
+        bool instanceMaterialColumn = false;
     };
 
     // Aborts (FATAL-style, like the reference) when construction fails.
@@ -130,6 +136,9 @@ public:
     // u8 [instances, 4], mutable: the colour override (r, g, b, a) of every row, a == 0 = none (upstream's
     // per-renderable colour override; needs Config::instanceColors or instanceColorColumn)
     madrona::py::Tensor instanceColorTensor(uint32_t shard = 0) const;
+    // i32 [instances], mutable: the material override of every row, outside the material table = none (upstream's
+    // per-renderable material override; needs Config::instanceMaterials or instanceMaterialColumn)
+    madrona::py::Tensor instanceMaterialTensor(uint32_t shard = 0) const;
     // binds every row to the (non-negative) object id its ObjectID column now holds: a spare
     // row gets its geometry, an existing row swaps it (makeEntityRenderable at run time,
     // src/sim.inl:5-8); waits for the device
@@ -161,6 +170,12 @@ public:
     bool setWorldLights(uint32_t first, uint32_t count, const Light *lights);
     void worldLights(uint32_t first, uint32_t count, Light *out) const;
     uint32_t numWorlds() const;
+    // per-instance material override (rows of the whole job, world-major, spare rows included): write rows
+    // [first, first + count) of the column from host memory -- stream-ordered, the next step renders with them; false
+    // when the range is outside the renderer -- and read them back (waits for the stream)
+    bool setInstanceMaterials(uint32_t first, uint32_t count, const int32_t *materials);
+    void instanceMaterials(uint32_t first, uint32_t count, int32_t *out) const;
+    uint32_t numInstanceRows() const;
 
     uint32_t numAgents;
 

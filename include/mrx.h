@@ -120,7 +120,13 @@ enum {
     /* per-instance colour override: allocates the MRX_BUF_INSTANCE_COLOR column, zero-filled, and selects the launch
      * forms that read it.  Without it nothing is allocated, mrx_buffer / mrx_buffer_shard /
      * mrx_copy_to_host on the column fail with MRX_E_UNSUPPORTED and every launch is the one it always was. */
-    MRX_FLAG_INSTANCE_COLORS = 1u << 4
+    MRX_FLAG_INSTANCE_COLORS = 1u << 4,
+    /* per-instance material override: allocates the MRX_BUF_INSTANCE_MATERIAL column, filled with -1, and selects the
+     * launch forms that read it.  Without it nothing is allocated, mrx_buffer / mrx_buffer_shard /
+     * mrx_copy_to_host on the column fail with MRX_E_UNSUPPORTED and every launch is the one it always was.  With it
+     * (and rgb rendered) the textured kernels are chosen when some material of the table is textured, whether or not
+     * a drawn triangle is: a caller who wants the untextured kernels passes a table without textured materials. */
+    MRX_FLAG_INSTANCE_MATERIALS = 1u << 5
 };
 
 /* Manager::Config + Config::RenderConfig, /root/reference/src/mgr.hpp:49-88.
@@ -225,7 +231,18 @@ enum {
      * (a negative ObjectID) and through mrx_refresh_objects(); spare rows start at 0.  Written on the device, like a
      * pose, on the renderer's stream; a depth-only renderer never reads it. */
     MRX_BUF_INSTANCE_COLOR = 10,
-    MRX_NUM_BUFFERS = 11
+    /* the ids of ABI 4 as first shipped end here; MRX_NUM_BUFFERS_EXT counts the ones added since as well */
+    MRX_NUM_BUFFERS = 11,
+    /* i32 [instances], mutable, needs MRX_FLAG_INSTANCE_MATERIALS: the material override of every row (upstream's
+     * per-renderable material override column).  m < 0 or m >= mrx_info_t.num_materials: none, the row's triangles
+     * shade as their own materials say; otherwise every triangle of the row shades with material m of the renderer's
+     * table (the API materials, then the ones of MTL files: what mesh_materials / mat_assignments index) -- its rgb
+     * in S7, its texture, or none, in S8.  A colour override (MRX_BUF_INSTANCE_COLOR, a != 0) then
+     * replaces that material's rgb.  It changes colour only -- never which kernel runs, visibility, depth or the
+     * segmask -- and belongs to the row: it stays through hiding and through mrx_refresh_objects(); spare rows start
+     * at -1.  Written on the device, like a pose, on the renderer's stream; a depth-only renderer never reads it. */
+    MRX_BUF_INSTANCE_MATERIAL = 11,
+    MRX_NUM_BUFFERS_EXT = 12
 };
 
 enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2 };
@@ -448,6 +465,16 @@ int mrx_world_light(mrx_renderer *r, uint32_t first_world, uint32_t count, mrx_l
  *    the light (x, y, z: -direction / |direction|, worked out in double and rounded once), ambient, diffuse.
  *    Both launch forms (uniform and per-view) take their constants from here. */
 int mrx_light_constants(mrx_light light, float out[5]);
+
+/* -- per-instance material override (MRX_FLAG_INSTANCE_MATERIALS).  Rows are the rows of MRX_BUF_INSTANCE_MATERIAL
+ *    over the whole job: world-major, spare rows included (a renderer of several shards splits the range at its world
+ *    boundaries).  mrx_set_instance_materials writes rows [first_row, first_row + count) and is stream-ordered as
+ *    mrx_set_view_projection is: renders enqueued before it keep the old ids, the next render has the new ones.  Any
+ *    int32 is accepted -- values outside the material table mean "no override", as on the device.  MRX_E_INVALID: a
+ *    null pointer or rows outside the renderer; MRX_E_UNSUPPORTED: no column.  mrx_instance_materials reads the
+ *    column back (it waits for the stream). */
+int mrx_set_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, const int32_t *materials);
+int mrx_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, int32_t *out);
 
 int mrx_device_count(void);
 int mrx_abi_version(void);

@@ -537,7 +537,9 @@ __device__ __forceinline__ void tlasChunks(const PARAMS &p, const PROJ &pj, cons
 // without it, 26.5 us with the state compiled in).
 // PV: per-view projection: the view constants come from the table's record of the tile's view (MULTI:
 // of each view of the group in turn; phase I: of the wave's view); PV = false is the kernel as it always was.
-template <int IDS, bool TEX, int TW, int TH, bool CLS, bool MULTI, bool PV>
+// MAT (with PV): the renderer has the material override column; a flag of this family alone -- several
+// of its per-view instantiations sit at 127 - 128 registers and spilled when they read the column behind a null check.
+template <int IDS, bool TEX, int TW, int TH, bool CLS, bool MULTI, bool PV, bool MAT = false>
 __device__ __forceinline__ void tileKernelBody(const RasterParams p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -930,7 +932,29 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                             icol = colors[rowBase + e.x];
                         }
                     }
-                    const bool valid = setupTriangleCore<false, true, PV>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold, icol);
+                    bool valid;
+                    // (MAT, DESIGN.md 4.14: the material override of the row, fetched where the set-up turns to colour
+                    // -- the queue entry from LDS, the pointers from the argument segment again: nothing of it is held
+                    // through the plane arithmetic, where the kernel has no register left)
+                    if constexpr (MAT) {
+                        const auto matOf = [&]() -> MatOverride {
+                            KernargParams pm = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
+                            asm volatile("" : "+s"(pm));
+                            uint32_t rowBase = passBase;
+                            if (MULTI) {
+                                const uint32_t uni = pm->bvhUniInst, cams = pm->bvhUniCams;
+                                if (uni)
+                                    rowBase = (cams != 1u ? view / cams : view) * uni;
+                                else
+                                    rowBase = pm->worldInstStart[pm->viewWorld[view]];
+                            }
+                            return MatOverride { pm->instMat[rowBase + ws->queue[lane].x], pm->numMaterials, pm->matTable };
+                        };
+                        valid = setupTriangleCore<false, true, PV, true>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold, icol,
+                                                                         matOf);
+                    } else {
+                        valid = setupTriangleCore<false, true, PV>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold, icol);
+                    }
                     live = valid && c.bbX1 >= TX0 && c.bbX0 <= TX1 && c.bbY1 >= TY0 && c.bbY0 <= TY1;
                     // The planes at the tile's corners: fl(A x + fl(B y + C)) is monotone in x and in
                     // y, so its extreme over the tile's pixels is taken at a corner pixel, and a
@@ -988,7 +1012,10 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                         asm volatile("" : "+s"(pk));
                         const float4 *tsrc = reinterpret_cast<const float4 *>(pk->tris + triL);
                         const float4 t2 = tsrc[2], t3 = tsrc[3];
-                        const float4 texDesc = reinterpret_cast<const float4 *>(pk->triMats + triL)[3];
+                        // (a renderer with the material column: the record's texture may be an overriding material's,
+                        // so its descriptor comes from the texture table -- the same words where nothing overrides)
+                        const float4 texDesc = MAT ? reinterpret_cast<const float4 *>(pk->textures)[__float_as_int(shade[1])]
+                                                   : reinterpret_cast<const float4 *>(pk->triMats + triL)[3];
                         const float uv[6] = { t2.y, t2.z, t2.w, t3.x, t3.y, t3.z };
                         float uvp[6];
                         uvPlanes(c, cold[0], uv, uvp);
@@ -1339,6 +1366,14 @@ void bvhTileKernelPV(const RasterParams p)
     tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, true>(p);
 }
 
+// the per-view form of a renderer with the material override column (p.instMat)
+template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
+__global__ __launch_bounds__(kWave *(TH / 8), 4)
+void bvhTileKernelPVM(const RasterParams p)
+{
+    tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, true, true>(p);
+}
+
 
 // ---------------------------------------------------------------------------
 // Worlds of at most 64 triangles in at most 64 instance rows (every BASELINE scene: cube + plane
@@ -1532,9 +1567,11 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
                 const SetupArgs sa = { p.tris, p.triMats, pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse,
                                        p.transposed };
                 // (a renderer with the colour column -- a wave-uniform test: the override of the triangle's row, 4.13)
+                // (and with the material column, 4.14)
                 const uint32_t icol = (OUT != kOutDepth && p.instColor) ? p.instColor[myRow] : 0u;
-                valid = setupTriangleCore<false, OUT != kOutDepth, true>(sa, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold,
-                                                                         icol);
+                const MatOverride mo = { (OUT != kOutDepth && p.instMat) ? p.instMat[myRow] : -1, p.numMaterials, p.matTable };
+                valid = setupTriangleCore<false, OUT != kOutDepth, true, true>(sa, vc.lv, y, myTri, objL, (int32_t)lane, c, shade,
+                                                                               cold, icol, mo);
             } else {
                 valid = setupTriangleCore<false, OUT != kOutDepth>(p, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
             }
@@ -1550,7 +1587,9 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
                 // (u/v planes as the general kernel derives them: uvPlanes() from the edge planes and |1/d|)
                 const float4 *tsrc = reinterpret_cast<const float4 *>(p.tris + myTri);
                 const float4 t2 = tsrc[2], t3 = tsrc[3];
-                const float4 texDesc = reinterpret_cast<const float4 *>(p.triMats + myTri)[3];
+                // (a renderer with the material column: the descriptor of the texture in effect, as in the tile kernel)
+                const float4 texDesc = (PV && p.instMat) ? reinterpret_cast<const float4 *>(p.textures)[__float_as_int(shade[1])]
+                                                         : reinterpret_cast<const float4 *>(p.triMats + myTri)[3];
                 const float uv[6] = { t2.y, t2.z, t2.w, t3.x, t3.y, t3.z };
                 float uvp[6];
                 uvPlanes(c, cold[0], uv, uvp);
@@ -1941,7 +1980,8 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
     // the per-view form (p.viewProj): the same shape, its per-view instantiation
 #define MRX_BVH(I, T, W, H, C, M)                                                               \
     do {                                                                                       \
-        if (p.viewProj) MRX_BVH_K((bvhTileKernelPV<I, T, W, H, C, M>));                        \
+        if (p.viewProj && p.instMat) MRX_BVH_K((bvhTileKernelPVM<I, T, W, H, C, M>));          \
+        else if (p.viewProj) MRX_BVH_K((bvhTileKernelPV<I, T, W, H, C, M>));                   \
         else            MRX_BVH_K((bvhTileKernel<I, T, W, H, C, M>));                          \
     } while (0)
 #define MRX_BVH_SHAPE(I, T)                                                                    \

@@ -8,6 +8,7 @@
 //                     [--vfov DEG] [--znear Z]   (every camera's projection; no counterpart upstream)
 //                     [--light X,Y,Z[,AMBIENT,DIFFUSE]]   (every world's directional light; no counterpart upstream)
 //                     [--instance-colors SEED]   (an opaque colour override per instance row, splitmix64(SEED, row))
+//                     [--instance-materials SEED]   (a material override per instance row, rows 1::4 left without)
 //
 // --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
 // renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
@@ -67,6 +68,9 @@ struct Args {
     // --instance-colors SEED: every instance row overridden with an opaque colour drawn from the seed and the row
     bool hasColors = false;
     uint64_t colorSeed = 0;
+    // --instance-materials SEED: every instance row but rows 1::4 overridden with a material drawn from the seed and the row
+    bool hasMaterials = false;
+    uint64_t materialSeed = 0;
 };
 
 // a number of the whole argument, finite
@@ -85,7 +89,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -153,6 +157,16 @@ Args parse(int argc, char **argv)
                 std::exit(EXIT_FAILURE);
             }
             a.hasColors = true;
+        } else if (!std::strcmp(argv[i], "--instance-materials") && i + 1 < argc) {
+            const char *s = argv[++i];
+            char *end = nullptr;
+            errno = 0;
+            a.materialSeed = std::strtoull(s, &end, 0);
+            if (!*s || *s == '-' || *s == '+' || *end || errno != 0) {
+                std::fprintf(stderr, "--instance-materials: not an unsigned integer seed: %s\n", s);
+                std::exit(EXIT_FAILURE);
+            }
+            a.hasMaterials = true;
         } else if (!std::strcmp(argv[i], "--znear") && i + 1 < argc) {
             a.znear = parseFloat("--znear", argv[++i]);
             if (!(a.znear > 0.0f)) {
@@ -420,6 +434,16 @@ int main(int argc, char **argv)
             colors.insert(colors.end(), { (uint8_t)z, (uint8_t)(z >> 8), (uint8_t)(z >> 16), (uint8_t)255 });
         }
         cfg.instanceColors = colors.data();
+    }
+    // --instance-materials: row i gets material splitmix64(splitmix64(SEED) ^ i) % (the scene's API materials); rows
+    // 1::4 -- and every row of a scene without materials -- keep -1, no override
+    std::vector<int32_t> matIds;
+    if (args.hasMaterials) {
+        const uint64_t base = splitmix64(args.materialSeed), nm = s.mats.size();
+        for (uint64_t i = 0; i < s.instances.size(); ++i)
+            matIds.push_back(nm && i % 4 != 1 ? (int32_t)(splitmix64(base ^ i) % nm) : -1);
+        cfg.instanceMaterials = matIds.data();
+        cfg.instanceMaterialColumn = true;
     }
     rc.worlds = s.worlds.data();
     if (args.gpus > 1) {

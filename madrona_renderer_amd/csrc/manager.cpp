@@ -5,6 +5,7 @@
 #include "../../include/madrona_mi355/manager.hpp"
 #include "../../include/mrx.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <stdexcept>
@@ -101,6 +102,8 @@ Manager::Manager(const Config &cfg)
     c.instance_colors = cfg.instanceColors;
     if (cfg.instanceColorColumn)
         c.flags |= MRX_FLAG_INSTANCE_COLORS;
+    if (cfg.instanceMaterialColumn || cfg.instanceMaterials)
+        c.flags |= MRX_FLAG_INSTANCE_MATERIALS;
     if (cfg.renderOutputs == RenderOutputs::Depth)
         c.flags |= MRX_FLAG_NO_RGB;
     else if (cfg.renderOutputs == RenderOutputs::RGB)
@@ -114,6 +117,22 @@ Manager::Manager(const Config &cfg)
 
     if (mrx_create(&c, &impl_->r) != MRX_OK)
         detail::fatal(mrx_last_error());
+    if (cfg.instanceMaterials) {
+        // the initial ids, world-major as mrx_create lays the rows out (spare rows -1), then the first frame again:
+        // what a caller reads before its first step() already shows them
+        std::vector<int32_t> ids;
+        for (uint32_t w = 0; w < cfg.numWorlds; ++w) {
+            const Sim::WorldInit &wi = rc.worlds[w];
+            const uint32_t rows = std::max(wi.numInstances, cfg.maxInstancesPerWorld);
+            for (uint32_t i = 0; i < rows; ++i)
+                ids.push_back(i < wi.numInstances ? cfg.instanceMaterials[wi.instancesOffset + i] : -1);
+        }
+        if (!ids.empty() &&
+            mrx_set_instance_materials(impl_->r, 0, (uint32_t)ids.size(), ids.data()) != MRX_OK)
+            detail::fatal(mrx_last_error());
+        if (mrx_render(impl_->r) != MRX_OK)
+            detail::fatal(mrx_last_error());
+    }
 
     // vestigial in the reference too (mgr.cpp:516-522)
     const char *num_agents_str = std::getenv("HIDESEEK_NUM_AGENTS");
@@ -149,6 +168,7 @@ Tensor Manager::visibilityTensor(uint32_t shard) const { return impl_->wrap(MRX_
 Tensor Manager::instanceObjectTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_OBJECT, shard); }
 Tensor Manager::instanceScaleTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_SCALE, shard); }
 Tensor Manager::instanceColorTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_COLOR, shard); }
+Tensor Manager::instanceMaterialTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_MATERIAL, shard); }
 
 Tensor Manager::instancePositionTensor(uint32_t shard) const
 {
@@ -273,6 +293,30 @@ uint32_t Manager::numWorlds() const
     if (mrx_info(impl_->r, &inf) != MRX_OK)
         detail::fatal(mrx_last_error());
     return inf.num_worlds;
+}
+
+bool Manager::setInstanceMaterials(uint32_t first, uint32_t count, const int32_t *materials)
+{
+    const int rc = mrx_set_instance_materials(impl_->r, first, count, materials);
+    if (rc == MRX_E_INVALID)
+        return false;
+    if (rc != MRX_OK)
+        detail::fatal(mrx_last_error());
+    return true;
+}
+
+void Manager::instanceMaterials(uint32_t first, uint32_t count, int32_t *out) const
+{
+    if (mrx_instance_materials(impl_->r, first, count, out) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+uint32_t Manager::numInstanceRows() const
+{
+    mrx_info_t inf {};
+    if (mrx_info(impl_->r, &inf) != MRX_OK)
+        detail::fatal(mrx_last_error());
+    return inf.num_instances;
 }
 
 int Manager::placement(float *candUs, int capacity, float *keptUs) const

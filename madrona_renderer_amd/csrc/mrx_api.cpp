@@ -330,6 +330,16 @@ struct mrx_renderer {
     // the colour override column (MRX_FLAG_INSTANCE_COLORS): the slice of the pose block behind
     // instObj; no pointer without the flag
     DevBuf<uint32_t> instColor;
+    // the material override column (MRX_FLAG_INSTANCE_MATERIALS): the slice of the pose block behind
+    // the colour column's slot; no pointer without the flag.  matTable: the renderer's material table as the kernels
+    // read it, one spare record past its end; anyMatTextured: some material of it has a texture
+    DevBuf<int32_t> instMat;
+    DevBuf<mrx::MatRec> matTable;
+    bool anyMatTextured = false;
+    // pinned staging of mrx_set_instance_materials, one word per row, and the event behind its last copy
+    int32_t *matStage = nullptr;
+    hipEvent_t matEv = nullptr;
+    bool matCopyPending = false;
     DevBuf<uint32_t> rgb;
     DevBuf<float> depth;
     DevBuf<int32_t> ids;
@@ -415,7 +425,8 @@ struct mrx_renderer {
         tris.release(); triMats.release(); textures.release(); texels.release();
         viewTris.release(); viewTriCount.release();
         instPos.release(); instRot.release(); instScale.release();
-        camPos.release(); camRot.release(); instObj.release(); instColor.release();
+        camPos.release(); camRot.release(); instObj.release(); instColor.release(); instMat.release();
+        matTable.release();
         projDev.release();
         lightDev.release();
         if (projStage)
@@ -424,6 +435,10 @@ struct mrx_renderer {
             (void)hipHostFree(lightStage);
         if (projEv)
             (void)hipEventDestroy(projEv);
+        if (matStage)
+            (void)hipHostFree(matStage);
+        if (matEv)
+            (void)hipEventDestroy(matEv);
         poseBlock.release(); geomBlock.release();
         rgb.release(); depth.release(); ids.release(); stamps.release();
         if (xccHost) (void)hipHostFree(xccHost);
@@ -1034,7 +1049,8 @@ int bindGeometry(mrx_renderer &r)
     // 18.0 against 18.6; 2048 views and more cross at 122 ... 129).
     uint32_t minTris = r.bvhMinTris;
     {
-        bool anyTex = false;
+        // (a renderer that shades with the material column: a textured material of the table may come to be drawn)
+        bool anyTex = r.params.instMat && r.anyMatTextured;
         for (const WorldTri &wt : worldTris)
             if (r.triMatsHost[wt.tri].tex >= 0) {
                 anyTex = true;
@@ -1088,7 +1104,8 @@ int bindGeometry(mrx_renderer &r)
     MRX_HIP(r.instKBase.reupload(instKBase));
 
     RasterParams &p = r.params;
-    p.anyTextured = 0;
+    // (the material column, DESIGN.md 4.14: decided here, never by what the column holds)
+    p.anyTextured = (p.instMat && r.anyMatTextured) ? 1 : 0;
     for (const mrx::WorldTri &wt : worldTris)
         if (r.triMatsHost[wt.tri].tex >= 0) {
             p.anyTextured = 1;
@@ -1140,8 +1157,9 @@ int bindGeometry(mrx_renderer &r)
 // did).  Views or worlds that differ: both tables, one record per view, are copied to the device on the renderer's
 // stream, behind every render enqueued so far and ahead of every later one, and the kernels' per-view instantiations
 // read them; the table of whichever does not vary holds the uniform values.
-// A renderer that shades with the colour column (params.instColor) always launches with the tables:
-// the chunked, brute and BVH kernels read the column in their per-view instantiations.  params.tablesVary tells the
+// A renderer that shades with the colour column (params.instColor) or the material column
+// (params.instMat, 4.14) always launches with the tables: the chunked, brute and BVH kernels read the columns in their
+// per-view instantiations.  params.tablesVary tells the
 // group kernels, which have a colour form over the uniform constants, whether the tables hold anything else.
 int applyViewTables(mrx_renderer &r)
 {
@@ -1174,7 +1192,7 @@ int applyViewTables(mrx_renderer &r)
     p.diffuse = lc.diffuse;
     const size_t n = r.proj.size();
     p.tablesVary = uniform ? 0u : 1u;
-    if (uniform && !(p.instColor && n)) {
+    if (uniform && !((p.instColor || p.instMat) && n)) {
         p.viewProj = nullptr;
         p.viewLight = nullptr;
         p.lightTable = 0;
@@ -1380,6 +1398,21 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
             tm.texDesc[2] = (int32_t)texDescs[tm.tex].height;
         }
     }
+    // the table the material override reads: rgb and the texture index validated the same way, and
+    // one spare record past the end in a colour no test material has -- a missing range guard shows, it does not stray
+    std::vector<MatRec> matRecs;
+    const bool wantMats = (cfg.flags & MRX_FLAG_INSTANCE_MATERIALS) != 0;
+    r.anyMatTextured = false;
+    if (wantMats) {
+        for (const mrx_material &m : allMats) {
+            MatRec rec = { m.color[0], m.color[1], m.color[2], m.texture_idx };
+            if (rec.tex < 0 || (uint32_t)rec.tex >= (uint32_t)texDescs.size())
+                rec.tex = -1;
+            r.anyMatTextured = r.anyMatTextured || rec.tex >= 0;
+            matRecs.push_back(rec);
+        }
+        matRecs.push_back(MatRec { 0.8125f, 0.0625f, 0.6875f, -1 });
+    }
     // the object a triangle belongs to rides in the alpha slot (segmask label, raster.hpp)
     for (size_t o = 0; o < r.objFirst.size(); ++o)
         for (int32_t t = 0; t < r.objCount[o]; ++t) {
@@ -1402,6 +1435,8 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     // (the colour column, with the flag: a row's four bytes, or zero for all of them and for spare rows)
     const bool wantColors = (cfg.flags & MRX_FLAG_INSTANCE_COLORS) != 0;
     std::vector<uint32_t> instColor;
+    // (the material column, with its flag: spare rows -1; the initial ids come through mrx_set_instance_materials)
+    std::vector<int32_t> instMat;
     std::vector<uint32_t> &worldInstStart = r.worldInstStartHost, &viewWorld = r.viewWorldHost;
     worldInstStart.assign(1, 0u);
     viewWorld.clear();
@@ -1493,8 +1528,9 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
         // pose block (the exported, user-mutable tensors are slices of it)
         const uint32_t nv = (uint32_t)viewWorld.size(), ni = (uint32_t)instObj.size();
         const PoseLayout lay = poseLayout(nv, ni);
-        // (the colour column, where there is one, behind the layout the FAST prologue relies on)
-        const size_t poseBytes = (size_t)lay.total + (wantColors ? mrxAlign256(ni * 4u) : 0u) + 256;
+        // (the colour column, where there is one, behind the layout the FAST prologue relies on; the material column
+        // behind the colour column's slot, which a renderer with the material column alone has zero-filled)
+        const size_t poseBytes = (size_t)lay.total + (wantMats ? 2u * mrxAlign256(ni * 4u) : wantColors ? mrxAlign256(ni * 4u) : 0u) + 256;
         MRX_HIP(r.poseBlock.alloc(poseBytes));
         MRX_HIP(hipMemset(r.poseBlock.ptr, 0, poseBytes));
         uint8_t *b = r.poseBlock.ptr;
@@ -1516,6 +1552,14 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
         if (wantColors) {
             r.instColor.view(b + poseColorOffset(nv, ni), instColor.size());
             MRX_HIP(up(r.instColor.ptr, instColor.data(), instColor.size() * 4));
+        }
+        if (wantMats) {
+            instMat.assign(ni, -1);
+            r.instMat.view(b + poseMaterialOffset(nv, ni), instMat.size());
+            MRX_HIP(up(r.instMat.ptr, instMat.data(), instMat.size() * 4));
+            MRX_HIP(r.matTable.upload(matRecs));
+            MRX_HIP(hipHostMalloc((void **)&r.matStage, (size_t)(ni ? ni : 1u) * sizeof(int32_t), hipHostMallocDefault));
+            MRX_HIP(hipEventCreateWithFlags(&r.matEv, hipEventDisableTiming));
         }
     }
 
@@ -1558,6 +1602,9 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     p.instObj = r.instObj.ptr;
     // (a depth-only renderer never reads the column: it launches what a renderer without one does)
     p.instColor = (cfg.flags & MRX_FLAG_NO_RGB) ? nullptr : r.instColor.ptr;
+    p.instMat = (cfg.flags & MRX_FLAG_NO_RGB) ? nullptr : r.instMat.ptr;
+    p.matTable = r.matTable.ptr;
+    p.numMaterials = wantMats ? (uint32_t)allMats.size() : 0u;
     p.camPos = r.camPos.ptr;
     p.camRot = r.camRot.ptr;
     p.rgb = r.rgb.ptr;
@@ -1706,7 +1753,8 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     inf.max_world_instances = maxWorldInst;
     inf.num_shards = 1;
     inf.bytes_per_step = (uint64_t)px * (4u * ((r.rgb.ptr ? 1u : 0u) + (r.depth.ptr ? 1u : 0u)) + (wantIds ? 4u : 0u)) +
-                         (r.instColor.ptr ? 48ull : 44ull) * inf.num_instances + 28ull * nviews;
+                         (44ull + (r.instColor.ptr ? 4ull : 0ull) + (r.instMat.ptr ? 4ull : 0ull)) * inf.num_instances +
+                         28ull * nviews;
     return bindGeometry(r);
 }
 
@@ -1907,6 +1955,100 @@ int mrx_light_constants(mrx_light light, float out[5])
     if (rc != MRX_OK)
         return rc;
     out[0] = c.toLight[0]; out[1] = c.toLight[1]; out[2] = c.toLight[2]; out[3] = c.ambient; out[4] = c.diffuse;
+    return MRX_OK;
+}
+
+// the renderers that hold the instance rows of the job, with the first job row of each
+static std::vector<std::pair<mrx_renderer *, uint64_t>> rowOwners(mrx_renderer *r)
+{
+    std::vector<std::pair<mrx_renderer *, uint64_t>> out;
+    uint64_t base = 0;
+    if (r->shards.empty()) {
+        out.emplace_back(r, 0u);
+        return out;
+    }
+    for (mrx_renderer *sh : r->shards) {
+        out.emplace_back(sh, base);
+        base += sh->info.num_instances;
+    }
+    return out;
+}
+
+static int rowRange(mrx_renderer *r, uint32_t first, uint32_t count, const void *ptr)
+{
+    uint64_t total = 0;
+    bool column = true;
+    for (const auto &o : rowOwners(r)) {
+        total += o.first->info.num_instances;
+        column = column && o.first->instMat.ptr;
+    }
+    if (!ptr)
+        return fail(MRX_E_INVALID, "null material array");
+    if ((uint64_t)first + count > total)
+        return fail(MRX_E_INVALID, "rows [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
+                                       ") outside the renderer's " + std::to_string(total));
+    if (!column)
+        return fail(MRX_E_UNSUPPORTED,
+                    "no instance materials: this renderer was created without MRX_FLAG_INSTANCE_MATERIALS");
+    return MRX_OK;
+}
+
+int mrx_set_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, const int32_t *materials)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    const int rc = rowRange(r, first_row, count, materials);
+    if (rc != MRX_OK)
+        return rc;
+    for (const auto &o : rowOwners(r)) {
+        mrx_renderer &sh = *o.first;
+        const uint64_t lo = std::max<uint64_t>(first_row, o.second);
+        const uint64_t hi = std::min<uint64_t>((uint64_t)first_row + count, o.second + sh.info.num_instances);
+        if (lo >= hi)
+            continue;
+        // (through the pinned staging: the copy runs on the stream behind every render enqueued so far, and the caller's
+        // array is free when the call returns; the staging is overwritten only once the last copy from it has run)
+        MRX_HIP(hipSetDevice(sh.device));
+        if (sh.matCopyPending)
+            MRX_HIP(hipEventSynchronize(sh.matEv));
+        int32_t *stage = sh.matStage + (lo - o.second);
+        std::memcpy(stage, materials + (lo - first_row), (hi - lo) * sizeof(int32_t));
+        MRX_HIP(hipMemcpyAsync(sh.instMat.ptr + (lo - o.second), stage, (hi - lo) * sizeof(int32_t), hipMemcpyHostToDevice,
+                               sh.stream));
+        MRX_HIP(hipEventRecord(sh.matEv, sh.stream));
+        sh.matCopyPending = true;
+    }
+    return MRX_OK;
+}
+
+int mrx_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, int32_t *out)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    const int rc = rowRange(r, first_row, count, out);
+    if (rc != MRX_OK)
+        return rc;
+    for (const auto &o : rowOwners(r)) {
+        mrx_renderer &sh = *o.first;
+        const uint64_t lo = std::max<uint64_t>(first_row, o.second);
+        const uint64_t hi = std::min<uint64_t>((uint64_t)first_row + count, o.second + sh.info.num_instances);
+        if (lo >= hi)
+            continue;
+        MRX_HIP(hipSetDevice(sh.device));
+        MRX_HIP(hipStreamSynchronize(sh.stream));
+        MRX_HIP(hipMemcpy(out + (lo - first_row), sh.instMat.ptr + (lo - o.second), (hi - lo) * sizeof(int32_t),
+                          hipMemcpyDeviceToHost));
+    }
     return MRX_OK;
 }
 
@@ -2475,6 +2617,14 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
         break;
     case MRX_BUF_INSTANCE_OBJECT:     // ObjectID column (sim.cpp:152-156); negative = hidden
         dims[0] = I; *ndim = 1; *dtype = MRX_DTYPE_I32; ptr = r->instObj.ptr;
+        break;
+    case MRX_BUF_INSTANCE_MATERIAL:   // the material override column; outside the table = no override
+        dims[0] = I; *ndim = 1; *dtype = MRX_DTYPE_I32; ptr = r->instMat.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED,
+                 "no instance materials: this renderer was created without MRX_FLAG_INSTANCE_MATERIALS");
+            return nullptr;
+        }
         break;
     case MRX_BUF_INSTANCE_COLOR:      // the colour override column; a == 0 = no override
         dims[0] = I; dims[1] = 4; *ndim = 2; *dtype = MRX_DTYPE_U8; ptr = r->instColor.ptr;

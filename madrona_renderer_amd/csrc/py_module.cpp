@@ -174,6 +174,10 @@ PYBIND11_MODULE(madrona_renderer, m)
     m.attr("MRX_FLAG_INSTANCE_COLORS") = (uint32_t)MRX_FLAG_INSTANCE_COLORS;
     m.attr("MRX_BUF_INSTANCE_COLOR") = (int)MRX_BUF_INSTANCE_COLOR;
     m.attr("MRX_NUM_BUFFERS") = (int)MRX_NUM_BUFFERS;
+    // ... and of the material override column
+    m.attr("MRX_FLAG_INSTANCE_MATERIALS") = (uint32_t)MRX_FLAG_INSTANCE_MATERIALS;
+    m.attr("MRX_BUF_INSTANCE_MATERIAL") = (int)MRX_BUF_INSTANCE_MATERIAL;
+    m.attr("MRX_NUM_BUFFERS_EXT") = (int)MRX_NUM_BUFFERS_EXT;
     m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
     m.attr("MRX_CONFIG_SIZE") = (uint32_t)sizeof(mrx_config);
 
@@ -292,7 +296,8 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<PyCamera> &pycameras,
                          const std::vector<Sim::WorldInit> &worlds,
                          const std::vector<int> &device_ids, int max_instances_per_world,
-                         Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors) {
+                         Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors,
+                         py::object instance_materials) {
                  if (mesh_vertices.size() && (mesh_vertices.ndim() != 2 || mesh_vertices.shape(1) != 3))
                      throw py::value_error("mesh_vertices must have shape [N, 3]");
                  if (mesh_uvs.size() && (mesh_uvs.ndim() != 2 || mesh_uvs.shape(1) != 2))
@@ -395,6 +400,17 @@ PYBIND11_MODULE(madrona_renderer, m)
                      cfg.instanceColors = colors.data();
                      cfg.instanceColorColumn = true;
                  }
+                 // instance_materials: None (no column), True (a column of -1) or [num_instances] int32
+                 py::array_t<int32_t, py::array::c_style | py::array::forcecast> matIds;
+                 if (py::isinstance<py::bool_>(instance_materials)) {
+                     cfg.instanceMaterialColumn = instance_materials.cast<bool>();
+                 } else if (!instance_materials.is_none()) {
+                     matIds = py::array_t<int32_t, py::array::c_style | py::array::forcecast>::ensure(instance_materials);
+                     if (!matIds || matIds.ndim() != 1 || (size_t)matIds.shape(0) != instances.size())
+                         throw py::value_error("instance_materials must be None, True or an int32 array of shape [num_instances]");
+                     cfg.instanceMaterials = matIds.data();
+                     cfg.instanceMaterialColumn = true;
+                 }
                  return new Manager(cfg);
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -413,7 +429,9 @@ PYBIND11_MODULE(madrona_renderer, m)
              // world_lights = [(direction xyz, ambient, diffuse)] per world: the worlds' directional lights
              py::arg("world_lights") = py::none(),
              // instance_colors = True or a [num_instances, 4] uint8 array (r, g, b, a): the colour override column
-             py::arg("instance_colors") = py::none())
+             py::arg("instance_colors") = py::none(),
+             // instance_materials = True or a [num_instances] int32 array: the material override column
+             py::arg("instance_materials") = py::none())
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -458,6 +476,12 @@ PYBIND11_MODULE(madrona_renderer, m)
         .def("instance_color_tensor",
              [](py::object self, py::object shard) {
                  return wrapTensor(self, self.cast<Manager &>().instanceColorTensor(shardOf(self, shard)));
+             },
+             py::arg("shard") = py::none())
+        // i32 [instances]: the material override of every row, outside the table = none (needs instance_materials=)
+        .def("instance_material_tensor",
+             [](py::object self, py::object shard) {
+                 return wrapTensor(self, self.cast<Manager &>().instanceMaterialTensor(shardOf(self, shard)));
              },
              py::arg("shard") = py::none())
         .def("instance_rotation_tensor",
@@ -632,6 +656,27 @@ PYBIND11_MODULE(madrona_renderer, m)
                      f.mutable_at(i) = lights[i].diffuse;
                  }
                  return py::make_tuple(d, a, f);
+             })
+        // per-instance material override from host memory (rows of the whole job from first_row on; a renderer of
+        // several shards splits them).  Stream-ordered: renders enqueued before keep the old ids.
+        .def("set_instance_materials",
+             [](Manager &self, py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids, int64_t first_row) {
+                 if (ids.ndim() != 1)
+                     throw py::value_error("materials must be a one-dimensional int32 array");
+                 if (first_row < 0 || first_row + (int64_t)ids.shape(0) > (int64_t)self.numInstanceRows())
+                     throw py::value_error("more material ids than instance rows from first_row on");
+                 const int32_t none = -1;
+                 if (!self.setInstanceMaterials((uint32_t)first_row, (uint32_t)ids.shape(0), ids.shape(0) ? ids.data() : &none))
+                     throw py::value_error(mrx_last_error());
+             },
+             py::arg("materials"), py::arg("first_row") = 0)
+        .def("instance_materials",
+             [](Manager &self) {
+                 const uint32_t n = self.numInstanceRows();
+                 py::array_t<int32_t> out(n);
+                 int32_t none = -1;
+                 self.instanceMaterials(0, n, n ? out.mutable_data() : &none);
+                 return out;
              })
         .def("camera_projection",
              [](Manager &self) {

@@ -106,7 +106,8 @@ struct GroupSetupArgs {
 };
 
 // setupTriangle under the projection constants `pr` of the view and the light `lt` of its world (per-view form), and
-// under the colour override of the instance row where the renderer has the column (a wave-uniform test)
+// under the colour and material overrides of the instance row where the renderer has the columns (DESIGN.md 4.13,
+// 4.14; wave-uniform tests)
 __device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const ViewProj &pr, const ViewLight &lt,
                                                   const ViewConst &vc, WorldTri wt, int32_t kWorld, TriPlanes &out,
                                                   float *shade, float *cold)
@@ -116,7 +117,12 @@ __device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const V
     InstXform x;
     instanceTransform(sa, vc, wt.inst, x);
     const uint32_t icol = p.instColor ? p.instColor[wt.inst] : 0u;
-    return setupTriangleCore<true, true, true>(sa, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold, icol);
+    // (read where the set-up turns to colour: raster_dev.hpp)
+    const auto matOf = [&]() -> MatOverride {
+        return MatOverride { p.instMat ? p.instMat[wt.inst] : -1, p.numMaterials, p.matTable };
+    };
+    return setupTriangleCore<true, true, true, true>(sa, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold, icol,
+                                                     matOf);
 }
 
 // S for one chunk of up to 64 world-triangles; returns the valid-lane mask.
@@ -793,7 +799,10 @@ constexpr int groupWaves(bool tex) { return tex ? 4 : 8; }
 // LT (with PV): the worlds' lights differ too: the set-up lanes read their view's light record beside
 // the camera; without it the per-view form takes the uniform light of the kernel arguments.
 // COL: per-instance colour override: the set-up lanes read their row's packed colour beside its ObjectID.
-template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT, bool PV = false, bool LT = false, bool COL = false>
+// MAT (with COL): per-instance material override: they read the row's material id too; the colour
+// column is then the slot of the pose block -- zero-filled in a renderer that has the material column alone.
+template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT, bool PV = false, bool LT = false, bool COL = false,
+          bool MAT = false>
 __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances,
                                                 uint32_t hPool, uint32_t hShape, uint32_t hGroups, uint32_t hPrefix,
                                                 uint32_t hFirst01, uint32_t hFirst23, const RasterParams p)
@@ -822,7 +831,11 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     const float *aCamRot = FAST ? reinterpret_cast<const float *>(hPose + lay.camRot) : p.camRot;
     const float *aCamPos = FAST ? reinterpret_cast<const float *>(hPose + lay.camPos) : p.camPos;
     const int32_t *aInstObj = FAST ? reinterpret_cast<const int32_t *>(hPose + lay.instObj) : p.instObj;
-    const uint32_t *aInstColor = FAST ? reinterpret_cast<const uint32_t *>(hPose + lay.total) : p.instColor;
+    const uint32_t *aInstColor = FAST ? reinterpret_cast<const uint32_t *>(hPose + lay.total)
+                                 : MAT ? reinterpret_cast<const uint32_t *>(p.poseBlock + poseColorOffset(p.numViews, p.numInstances))
+                                       : p.instColor;
+    const int32_t *aInstMat = FAST ? reinterpret_cast<const int32_t *>(hPose + lay.total + mrxAlign256(hInstances * 4u))
+                                   : p.instMat;
     const uint32_t tilesPerView = FAST ? 1u : p.tilesFast * p.tilesSlow;
     // FAST, untextured (16 slots, one-tile views): S2 hands phase R ready-made work items (GroupLds::items).
     // The plain entry and the textured kernels keep the per-tile masks: measured slower with the items
@@ -1012,9 +1025,10 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                     pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse, p.transposed };
                 InstXform x;
                 instanceTransform(sa, vc, wt.inst, x);
-                valid = setupTriangleCore<true, OUT != kOutDepth, COL>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
-                                                                       lds.shade[rec], lds.cold[rec],
-                                                                       COL ? aInstColor[wt.inst] : 0u);
+                const MatOverride mo = { MAT ? aInstMat[wt.inst] : -1, p.numMaterials, p.matTable };
+                valid = setupTriangleCore<true, OUT != kOutDepth, COL, MAT>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
+                                                                            lds.shade[rec], lds.cold[rec],
+                                                                            COL ? aInstColor[wt.inst] : 0u, mo);
             }
             MRX_STAMP(2);
             float4 *dst = reinterpret_cast<float4 *>(lds.planes[rec]);
@@ -1344,6 +1358,45 @@ void rasterGroupKernelFastPVLC(const char *hPose, const char *hGeom, uint32_t hV
                                                                            hGroups, hPrefix, hFirst01, hFirst23, p);
 }
 
+// The material forms (p.instMat), as the colour forms are: M over the uniform projection and light,
+// PVLM over both tables.  They read both columns -- a renderer with the material column has the colour column's slot,
+// zero-filled where it has no colour column -- so two forms cover every renderer with this column.
+template <bool IDS, int SLOTS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : (SLOTS > 128 ? 6 : 8))
+void rasterGroupKernelM(const RasterParams p)
+{
+    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, false, false, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u,
+                                                                                       0u, 0u, p);
+}
+
+template <bool IDS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 8)
+void rasterGroupKernelFastM(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
+                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
+                            const RasterParams p)
+{
+    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, false, false, true, true>(hPose, hGeom, hViews, hInstances, hPool,
+                                                                                   hShape, hGroups, hPrefix, hFirst01, hFirst23, p);
+}
+
+template <bool IDS, int SLOTS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : 6)
+void rasterGroupKernelPVLM(const RasterParams p)
+{
+    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, true, true, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u,
+                                                                                     0u, p);
+}
+
+template <bool IDS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 6)
+void rasterGroupKernelFastPVLM(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
+                               uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
+                               const RasterParams p)
+{
+    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, true, true, true, true>(hPose, hGeom, hViews, hInstances, hPool, hShape,
+                                                                                 hGroups, hPrefix, hFirst01, hFirst23, p);
+}
+
 }  // namespace
 
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
@@ -1504,7 +1557,11 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
     } while (0)
 #define MRX_GROUP_O(S, X, O, OP)                                               \
     do {                                                                       \
-        if (p.instColor && pv && p.tablesVary) {                               \
+        if (p.instMat && pv && p.tablesVary) {                                 \
+            MRX_GROUP_FORM(S, rasterGroupKernelFastPVLM, rasterGroupKernelPVLM);                          \
+        } else if (p.instMat) {                                                \
+            MRX_GROUP_FORM(S, rasterGroupKernelFastM, rasterGroupKernelM);     \
+        } else if (p.instColor && pv && p.tablesVary) {                        \
             MRX_GROUP_FORM(S, rasterGroupKernelFastPVLC, rasterGroupKernelPVLC);                          \
         } else if (p.instColor) {                                              \
             MRX_GROUP_FORM(S, rasterGroupKernelFastC, rasterGroupKernelC);     \

@@ -63,6 +63,14 @@ struct TexDesc {
     uint32_t pad;
 };
 
+// One material of the renderer's table as the override reads it (RasterParams::matTable): rgb and the validated
+// texture index (-1 = untextured; its TexDesc is RasterParams::textures[tex]).
+struct alignas(16) MatRec {
+    float r, g, b;
+    int32_t tex;
+};
+static_assert(sizeof(MatRec) == 16, "MatRec is one 16-byte record");
+
 // One world-triangle slot: which instance row draws which object triangle.
 struct WorldTri {
     uint32_t inst;   // row of the world-major instance tables
@@ -203,6 +211,15 @@ struct RasterParams {
     // viewProj: the per-view instantiations of the chunked, brute and BVH kernels read it behind a null check, the
     // group kernels have colour instantiations of their own.
     const uint32_t *instColor;
+    // Per-instance material override: [I] material ids; an id below numMaterials (one unsigned
+    // compare: negative ids fail it) replaces the rgb and the texture index of the row's triangles by those of
+    // matTable[id].  The slice of the pose block behind the colour column's slot (poseMaterialOffset); null = no
+    // column, or a depth-only renderer.  Set together with viewProj, as instColor is: the per-view instantiations of
+    // the chunked, brute and BVH kernels read it behind a null check, the group kernels have instantiations of their own.
+    const int32_t *instMat;
+    // [numMaterials + 1] records of the renderer's material table (the last one a spare nothing may select)
+    const MatRec *matTable;
+    uint32_t numMaterials;
 };
 
 // ---- the argument header of the group kernel's fast prologue (raster.hip, FAST) -------------------------------------
@@ -236,6 +253,12 @@ MRX_HD inline PoseLayout poseLayout(uint32_t views, uint32_t instances)
 // the colour column of a renderer that has one (RasterParams::instColor): [instances] dwords behind the layout above,
 // whose offsets therefore do not move
 MRX_HD inline uint32_t poseColorOffset(uint32_t views, uint32_t instances) { return poseLayout(views, instances).total; }
+// the material column of a renderer that has one (RasterParams::instMat): [instances] dwords behind the colour column's
+// slot, which a renderer with this column always has (zero-filled where it has no colour column)
+MRX_HD inline uint32_t poseMaterialOffset(uint32_t views, uint32_t instances)
+{
+    return poseColorOffset(views, instances) + mrxAlign256(instances * 4u);
+}
 // geometry block: ObjTri[pool] at 0, TriMat[pool] at geomMatsOffset(pool)
 MRX_HD inline uint32_t geomMatsOffset(uint32_t poolTris) { return mrxAlign256(poolTris * 64u); }
 

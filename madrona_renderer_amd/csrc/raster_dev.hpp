@@ -133,22 +133,39 @@ __device__ __forceinline__ void instanceTransform(const PARAMS &p, const ViewCon
 // ICOL: `icol` is the packed colour override (r, g, b, a bytes, r lowest) of the instance row: a
 // non-zero a replaces the material's rgb by (r, g, b) * (1 / 255) -- S8's texel constant, one multiply per channel --
 // in S7, hence in S8 too; the alpha slot (the segmask label) and everything but colour are untouched.
+// IMAT: `matOf()` gives the material override of the instance row: an id inside the table (one
+// unsigned compare) replaces the material's rgb and its texture index by the table record's, ahead of everything that
+// reads them (the u/v planes, S7, the record's texture slot) -- the colour override then applies to that material.
+// It is a callable, called where the colour work begins and not before: the BVH tile kernel has no register to carry
+// the id through the plane arithmetic in, and reads it there.
 // PARAMS: RasterParams, or any struct with the members read here (tris, triMats, s6bPad, sx, sz,
 // ox, oz, transposed, diffuse, ambient) -- the BVH kernel passes a copy it reads from the
 // kernel-argument segment batch by batch instead of holding the values in scalar registers.
-template <bool UVPLANES = true, bool COLOR = true, bool ICOL = false, typename PARAMS = RasterParams>
+struct MatOverride {
+    int32_t id;
+    uint32_t count;           // materials of the table
+    const MatRec *table;
+    __device__ __forceinline__ MatOverride operator()() const { return *this; }
+};
+struct NoMatOverride {
+    __device__ __forceinline__ MatOverride operator()() const { return MatOverride { -1, 0u, nullptr }; }
+};
+template <bool UVPLANES = true, bool COLOR = true, bool ICOL = false, bool IMAT = false, typename PARAMS = RasterParams,
+          typename MATFN = NoMatOverride>
 __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (&lv)[3],
                                                   const InstXform &x, uint32_t tri, int32_t obj,
                                                   int32_t kWorld, TriPlanes &out,
-                                                  float *shade, float *cold, uint32_t icol = 0u)
+                                                  float *shade, float *cold, uint32_t icol = 0u,
+                                                  const MATFN matOf = MATFN())
 {
     const float (&MV)[3][3] = x.MV;
     const float (&tv)[3] = x.tv;
     const float4 *src = reinterpret_cast<const float4 *>(p.tris + tri);
     const float4 t0 = src[0], t1 = src[1], t2 = src[2], t3 = src[3];
     const float4 *msrc = reinterpret_cast<const float4 *>(p.triMats + tri);
-    const float4 mc = msrc[0], m1 = msrc[1], m2 = msrc[2];
-    const int32_t tex = __float_as_int(m1.x);
+    float4 mc = msrc[0];
+    const float4 m1 = msrc[1], m2 = msrc[2];
+    int32_t tex = __float_as_int(m1.x);
     // S6b: is the eye outside the (padded) bounding box of the triangle's shell,
     // by more than the reach of the near plane?  The eye in the instance's
     // unscaled frame, q = Ri^T (c - t), against the box scaled by s (no division).
@@ -250,6 +267,14 @@ __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (
         shade[2] = obj >= 0 ? mc.w : __int_as_float(obj);
         shade[3] = __int_as_float(kWorld);
         return valid;
+    }
+    if (IMAT) {
+        const MatOverride mo = matOf();
+        if ((uint32_t)mo.id < mo.count) {
+            const float4 m = *reinterpret_cast<const float4 *>(mo.table + mo.id);
+            mc.x = m.x; mc.y = m.y; mc.z = m.z;
+            tex = __float_as_int(m.w);
+        }
     }
     // u/v planes (S8) are only ever read for textured triangles
     if (!UVPLANES) {

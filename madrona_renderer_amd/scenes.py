@@ -50,6 +50,10 @@ class SceneDesc:
     # material colour, any other a shades it with (r, g, b) / 255 instead.  None = no column; True = a zero-filled
     # one (written later through instance_color_tensor()).  Worlds that alias rows share their colours.
     instance_colors: object = None
+    # per-instance material override, parallel to `instances`: [N] int32 ids into the material table (`materials`,
+    # then the ones of MTL files); an id outside it (-1) leaves the row its own materials.  None = no column; True = a
+    # column of -1 (written later through instance_material_tensor()).  Worlds that alias rows share their ids.
+    instance_materials: object = None
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -267,6 +271,14 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
             if colors.shape != (len(desc.instances), 4):
                 raise ValueError("instance_colors needs one (r, g, b, a) per instance")
             extra["instance_colors"] = colors
+    if desc.instance_materials is not None:
+        if desc.instance_materials is True:
+            extra["instance_materials"] = True
+        else:
+            mats = np.ascontiguousarray(desc.instance_materials, np.int32)
+            if mats.shape != (len(desc.instances),):
+                raise ValueError("instance_materials needs one material id per instance")
+            extra["instance_materials"] = mats
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:
