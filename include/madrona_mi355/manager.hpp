@@ -101,6 +101,9 @@ public:
         // share ids, spare rows get -1.  nullptr with instanceMaterialColumn: a column of -1; nullptr without: none.
         const int32_t *instanceMaterials = nullptr;
         bool instanceMaterialColumn = false;
+        // Surface-normal output (MRX_FLAG_NORMALS): normalTensor() holds the view-space normal of every pixel's
+        // winning triangle, RGBA8-encoded; combines with every renderOutputs setting.
+        bool normals = false;
     };
 
     // Aborts (FATAL-style, like the reference) when construction fails.
@@ -139,6 +142,10 @@ public:
     // i32 [instances], mutable: the material override of every row, outside the material table = none (upstream's
     // per-renderable material override; needs Config::instanceMaterials or instanceMaterialColumn)
     madrona::py::Tensor instanceMaterialTensor(uint32_t shard = 0) const;
+    // u8 [views, H, W, 4] (Raytracer: [views, res, res, 4] transposed, as rgb): the flat view-space normal of the
+    // pixel's winning triangle turned towards the eye, byte = 128 + 127 * component, alpha 255; background
+    // (128, 128, 128, 0).  Needs Config::normals.
+    madrona::py::Tensor normalTensor(uint32_t shard = 0) const;
     // binds every row to the (non-negative) object id its ObjectID column now holds: a spare
     // row gets its geometry, an existing row swaps it (makeEntityRenderable at run time,
     // src/sim.inl:5-8); waits for the device

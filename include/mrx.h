@@ -126,7 +126,13 @@ enum {
      * mrx_copy_to_host on the column fail with MRX_E_UNSUPPORTED and every launch is the one it always was.  With it
      * (and rgb rendered) the textured kernels are chosen when some material of the table is textured, whether or not
      * a drawn triangle is: a caller who wants the untextured kernels passes a table without textured materials. */
-    MRX_FLAG_INSTANCE_MATERIALS = 1u << 5
+    MRX_FLAG_INSTANCE_MATERIALS = 1u << 5,
+    /* surface-normal output: allocates the MRX_BUF_NORMAL tensor and selects the launch forms that store it (DESIGN.md
+     * S10, 4.15).  It changes no other output and never which kernel family renders; it combines with MRX_FLAG_NO_RGB
+     * (normals + depth) and with MRX_FLAG_NO_DEPTH (normals + rgb).  Without it nothing is allocated, mrx_buffer /
+     * mrx_buffer_shard / mrx_copy_to_host on the tensor fail with MRX_E_UNSUPPORTED and every launch is the one it
+     * always was. */
+    MRX_FLAG_NORMALS = 1u << 6
 };
 
 /* Manager::Config + Config::RenderConfig, /root/reference/src/mgr.hpp:49-88.
@@ -242,7 +248,15 @@ enum {
      * segmask -- and belongs to the row: it stays through hiding and through mrx_refresh_objects(); spare rows start
      * at -1.  Written on the device, like a pose, on the renderer's stream; a depth-only renderer never reads it. */
     MRX_BUF_INSTANCE_MATERIAL = 11,
-    MRX_NUM_BUFFERS_EXT = 12
+    MRX_NUM_BUFFERS_EXT = 12,
+    /* u8 [views,H,W,4] (Raytracer: [views,res,res,4], transposed like rgb), needs MRX_FLAG_NORMALS: the flat geometric
+     * normal of the triangle that wins the pixel, in VIEW space (+X right, +Y forward, +Z up), unit length, turned
+     * towards the eye, one byte per axis: b = (uint) fma(clamp(c, -1, 1), 127, 128.5), so 1 ... 255 with 128 = 0, and
+     * a caller decodes (b - 128) / 127.  Alpha is 255 on a hit; background pixels hold (128, 128, 128, 0) -- the zero
+     * vector, alpha 0 marks the miss.  Independent of winding, mirroring scales, light, material, colour override and
+     * texture.  One tensor per shard, like rgb. */
+    MRX_BUF_NORMAL = 12,
+    MRX_NUM_BUFFERS_EXT2 = 13
 };
 
 enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2 };

@@ -276,6 +276,7 @@ struct ResolveArgs {
     int32_t *ids;
     const uint32_t *texels;
     uint32_t nfast, nslow, writeThrough;
+    uint32_t *normal;           // the normals forms only
 };
 typedef const __attribute__((address_space(4))) RasterParams *KernargParams;
 // the same for the triangle set-up of a batch (setupTriangleCore)
@@ -288,10 +289,16 @@ struct SetupArgs {
 
 // OUT: output selection (raster.hpp OutSel) -- fixed in the flat kernel, kOutByPointer (a null output is skipped
 // at run time) in the tile kernel.  Depth only: no colour is looked up or stashed, no texel is loaded.
-template <int IDS, bool TEX, int TW, int TH, bool FINAL, int ZS = TW, int OUT = kOutByPointer>
+// NRM: the normals form: the winner's packed normal is looked up where its colour is -- in the
+// texture slot of the untextured 16-byte record, which nothing reads there, or, TEX, in `nrmTab`, a dword per record
+// slot behind everything else in LDS -- stashed and taken back like the colour, and stored like it.
+// LATE (with NRM): the normals are looked up after the other tensors' stores (the tile kernel, which has no register
+// for them beside the colours); LATE = false (the flat kernel, whose textured segmask instantiations spilled that way
+// at their 80 registers): beside the colours, in the same pass over the depth-buffer words.
+template <int IDS, bool TEX, int TW, int TH, bool FINAL, int ZS = TW, int OUT = kOutByPointer, bool NRM = false, bool LATE = true>
 __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long long *zbuf, const float4 *shadeTab,
                                              const float (*coldTab)[kCold], uint32_t view, uint32_t tileX0,
-                                             uint32_t tileY0, int wave, int lane)
+                                             uint32_t tileY0, int wave, int lane, const uint32_t *nrmTab = nullptr)
 {
     constexpr int kHalves = TW / 32;
     {
@@ -314,6 +321,7 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
         const size_t o = tileBase + (size_t)(8u * wave + ly) * p.nfast + hf * 32 + 4 * lx;
         uint32_t rgba[kRegionBlocks], low[kRegionBlocks], itBits[kRegionBlocks], texSlot[kRegionBlocks];
         int32_t seg[kRegionBlocks];
+        uint32_t nrmEarly[kRegionBlocks];
         bool mine[kRegionBlocks], texOn[kRegionBlocks], anyTexOn = false, anyStashed = false;
 #pragma unroll
         for (int b = 0; b < kRegionBlocks; ++b) {
@@ -333,15 +341,71 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
                 rgba[b] = mine[b] ? __float_as_uint(recT[0]) : 0xFF000000u;
                 seg[b] = mine[b] ? __float_as_int(tail.w) : -1;
                 texOn[b] = mine[b] && __float_as_uint(tail.z) != 0u;
+                if (NRM && !LATE)
+                    nrmEarly[b] = mine[b] ? nrmTab[slot] : kNormalBackground;
             } else {
                 const float4 rec = shadeTab[mine[b] ? slot : 0u];
                 rgba[b] = mine[b] ? __float_as_uint(rec.x) : 0xFF000000u;
                 seg[b] = mine[b] ? __float_as_int(rec.z) : -1;
                 texOn[b] = false;
+                if (NRM && !LATE)
+                    nrmEarly[b] = mine[b] ? __float_as_uint(rec.y) : kNormalBackground;
             }
             texSlot[b] = texOn[b] ? slot : 0u;
             anyTexOn = anyTexOn || texOn[b];
         }
+        // NRM: the normals of the half's four pixels, worked out from the depth-buffer words alone and after the other
+        // tensors' stores have been issued -- nothing of it is live beside the colours (the kernel has no register for
+        // it there).  This round's winners from their records; FINAL: pixels stashed in an earlier round from the
+        // tensor; pixels without a hit the background.  !FINAL: this round's winners go to the tensor, as the colour.
+        const auto normalsOut = [&]() {
+            uint32_t nrm[kRegionBlocks];
+            // (the pixel classes are worked out from low[] again wherever they are needed: held as lane masks they
+            // cost scalar registers through the loads below, and the kernel has none)
+            const auto isMine = [&](int b) { return low[b] != 0u && (low[b] & kStashed) != kStashed; };
+            const auto isStashed = [&](int b) { return low[b] != 0u && (low[b] & kStashed) == kStashed; };
+#pragma unroll
+            for (int b = 0; b < kRegionBlocks; ++b) {
+                const uint32_t slot = isMine(b) ? (low[b] & kStashed) : 0u;
+                const uint32_t v = TEX ? nrmTab[slot] : __float_as_uint(reinterpret_cast<const float *>(shadeTab + slot)[1]);
+                nrm[b] = isMine(b) ? v : kNormalBackground;
+            }
+            const bool anyS = isStashed(0) || isStashed(1) || isStashed(2) || isStashed(3);
+            if (!FINAL) {
+                if (full && !anyS) {
+                    if (isMine(0) || isMine(1) || isMine(2) || isMine(3))
+                        streamStore16(p.writeThrough, p.normal + o, nrm[0], nrm[1], nrm[2], nrm[3]);
+                } else {
+#pragma unroll
+                    for (int b = 0; b < kRegionBlocks; ++b)
+                        if (isMine(b) && fx0 + b < p.nfast && fy < p.nslow)
+                            streamStore4(p.writeThrough, p.normal + o + b, nrm[b]);
+                }
+                return;
+            }
+            if (__ballot(anyS) != 0) {
+                if (anyS && full) {
+                    const u32x4 pn = streamLoad16(p.normal + o);
+#pragma unroll
+                    for (int b = 0; b < kRegionBlocks; ++b)
+                        if (isStashed(b))
+                            nrm[b] = pn[b];
+                } else if (anyS) {
+#pragma unroll
+                    for (int b = 0; b < kRegionBlocks; ++b)
+                        if (isStashed(b) && fx0 + b < p.nfast && fy < p.nslow)
+                            nrm[b] = streamLoad4(p.normal + o + b);
+                }
+            }
+            if (full) {
+                streamStore16(p.writeThrough, p.normal + o, nrm[0], nrm[1], nrm[2], nrm[3]);
+            } else if (fy < p.nslow) {
+#pragma unroll
+                for (int b = 0; b < kRegionBlocks; ++b)
+                    if (fx0 + b < p.nfast)
+                        streamStore4(p.writeThrough, p.normal + o + b, nrm[b]);
+            }
+        };
         // Textured winners: the texel loads of the half's four pixels are all issued before any
         // is used (addresses of untextured pixels point at texel 0) -- under per-pixel branches
         // every load waited for the one before it.
@@ -407,6 +471,8 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
                             streamStore4(p.writeThrough, p.ids + o + b, (uint32_t)seg[b]);
                     }
             }
+            if (NRM)
+                normalsOut();
 #pragma unroll
             for (int b = 0; b < kRegionBlocks; ++b)
                 if (mine[b])
@@ -465,6 +531,19 @@ __device__ __forceinline__ void resolveStrip(const ResolveArgs p, unsigned long 
                     if (IDS)
                         streamStore4(p.writeThrough, p.ids + o + b, id[b]);
                 }
+        }
+        if (NRM && LATE)
+            normalsOut();
+        if (NRM && !LATE) {
+            static_assert(!NRM || LATE || FINAL, "the early form is the flat kernel's: one round, nothing stashed");
+            if (full) {
+                streamStore16(p.writeThrough, p.normal + o, nrmEarly[0], nrmEarly[1], nrmEarly[2], nrmEarly[3]);
+            } else if (fy < p.nslow) {
+#pragma unroll
+                for (int b = 0; b < kRegionBlocks; ++b)
+                    if (fx0 + b < p.nfast)
+                        streamStore4(p.writeThrough, p.normal + o + b, nrmEarly[b]);
+            }
         }
     }
 }
@@ -539,7 +618,28 @@ __device__ __forceinline__ void tlasChunks(const PARAMS &p, const PROJ &pj, cons
 // of each view of the group in turn; phase I: of the wave's view); PV = false is the kernel as it always was.
 // MAT (with PV): the renderer has the material override column; a flag of this family alone -- several
 // of its per-view instantiations sit at 127 - 128 registers and spilled when they read the column behind a null check.
-template <int IDS, bool TEX, int TW, int TH, bool CLS, bool MULTI, bool PV, bool MAT = false>
+// NRM: the normals form: the set-up packs the triangle's normal, which rides in the texture slot
+// of the untextured record or, TEX, in a dword per record slot behind everything else in LDS (tileNormalTab below);
+// the resolves stash, take back and store it like the colour.  With PV it is instantiated with MAT and reads the
+// material and colour columns, where the renderer has them, behind scalar selects.  The view constants take the
+// placement of the textured kernels (kLvInLds below).
+//
+// LDS of the textured normals forms, behind everything else: a dword per record slot
+template <bool TEX, int TW, int TH, bool CLS, bool MULTI>
+__device__ __forceinline__ uint32_t *tileNormalTab(unsigned char *smem)
+{
+    // (from the argument segment where it is needed, as ResolveArgs is: nothing of it lives through the traversal)
+    KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(pk));
+    const uint32_t cap = TEX ? pk->bvhTexCap : (uint32_t)tabCap(false, TW, TH, CLS);
+    const uint32_t blocks = MULTI ? (pk->bvhGroupViews & 0xFFFFu) : 1u;
+    const size_t off = (size_t)(TW + kZPad) * TH * 8 + (TEX ? (size_t)cap * 48u : (size_t)cap * 16u) + 64 +
+                       (size_t)bigCap(TW, TH, CLS, TEX) * 64 + sizeof(WaveScratch) * (size_t)(TH / 8) +
+                       ((size_t)pk->bvhPassInst * (kInstRecDw + 4) * 4 + 16) * blocks;
+    return reinterpret_cast<uint32_t *>(smem + off);
+}
+
+template <int IDS, bool TEX, int TW, int TH, bool CLS, bool MULTI, bool PV, bool MAT = false, bool NRM = false>
 __device__ __forceinline__ void tileKernelBody(const RasterParams p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -647,7 +747,8 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
     //      the plain untextured instantiations work them out in every wave, here; the others
     //      only in the waves that transform instances, inside the pass loop, with the light
     //      direction handed to the set-up of all waves through LDS.
-    constexpr bool kLvInLds = TEX || MULTI;
+    // (the normals forms take the second: the first costs the 64x64 untextured ones the register they need for the normal)
+    constexpr bool kLvInLds = TEX || MULTI || NRM;
     ViewConst vcAll = {};
     if (!kLvInLds)
         loadViewConst<PV>(p, view, vcAll);
@@ -884,7 +985,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                 int32_t objL = -1;
                 // cold: [0] = |1/d| (the u/v planes are derived once the triangle has a slot), [6..8] lit colour
                 float shade[4] = { 0.f, 0.f, 0.f, 0.f }, cold[kCold];
-                uint32_t triL = 0;
+                uint32_t triL = 0, nrmv = kNormalBackground;
                 if ((uint32_t)lane < nb && !(dskip & 8u)) {
                     const uint2 e = ws->queue[lane];
                     triL = e.y;
@@ -917,7 +1018,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     // (PV, a renderer with the colour column -- a wave-uniform test: the override of the triangle's row,
                     // DESIGN.md 4.13; e.x counts from the first row of the pass -- MULTI: of the world of `view`)
                     uint32_t icol = 0u;
-                    if (PV) {
+                    if (PV && !(NRM && MAT)) {
                         const uint32_t *colors = pk->instColor;
                         if (colors) {
                             uint32_t rowBase = passBase;
@@ -948,10 +1049,32 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                                 else
                                     rowBase = pm->worldInstStart[pm->viewWorld[view]];
                             }
-                            return MatOverride { pm->instMat[rowBase + ws->queue[lane].x], pm->numMaterials, pm->matTable };
+                            const int32_t *ids = pm->instMat;
+                            uint32_t numMats = pm->numMaterials;
+                            if (NRM) {
+                                // (the normals form takes renderers without the column too: scalar selects instead of a
+                                // branch -- it then reads the ObjectID column against an empty table, which no id passes)
+                                numMats = ids ? numMats : 0u;
+                                ids = ids ? ids : pm->instObj;
+                            }
+                            if (NRM) {
+                                // (... and the colour override with it, behind the same kind of select)
+                                const uint32_t *colors = pm->instColor;
+                                const uint32_t row = rowBase + ws->queue[lane].x;
+                                const uint32_t cv = (colors ? colors : reinterpret_cast<const uint32_t *>(pm->instObj))[row];
+                                return MatOverride { ids[row], numMats, pm->matTable, colors ? cv : 0u };
+                            }
+                            return MatOverride { ids[rowBase + ws->queue[lane].x], numMats, pm->matTable };
                         };
-                        valid = setupTriangleCore<false, true, PV, true>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold, icol,
-                                                                         matOf);
+                        if constexpr (NRM)
+                            valid = setupTriangleCore<false, true, PV, true>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold,
+                                                                             icol, matOf, NormalOut { &nrmv });
+                        else
+                            valid = setupTriangleCore<false, true, PV, true>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold,
+                                                                             icol, matOf);
+                    } else if constexpr (NRM) {
+                        valid = setupTriangleCore<false, true, PV>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold, icol,
+                                                                   NoMatOverride(), NormalOut { &nrmv });
                     } else {
                         valid = setupTriangleCore<false, true, PV>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold, icol);
                     }
@@ -997,8 +1120,13 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                 const uint32_t slot = slotBase + liveRank;
                 const uint32_t lowKey = ((~kTri & kKeyMask) << kSlotBits) | slot;
                 if (live) {
+                    if (TEX && NRM)
+                        tileNormalTab<TEX, TW, TH, CLS, MULTI>(smem)[slot] = nrmv;
                     if (!TEX)
-                        shadeTab[slot] = make_float4(shade[0], shade[1], shade[2], __uint_as_float(kTri));   // [2]: the triangle's object id
+                        shadeTab[slot] = make_float4(shade[0],
+                                                     NRM ? __uint_as_float(nrmv)
+                                                         : shade[1],
+                                                     shade[2], __uint_as_float(kTri));   // [2]: the triangle's object id
                     else if (__float_as_int(shade[1]) < 0) {
                         // an untextured triangle of a textured scene: packed colour, "no texture", object id
                         float *dst = coldTab[slot];
@@ -1281,8 +1409,11 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                 // (the kernel's only argument sits at offset 0 of the kernel-argument segment)
                 KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
                 asm volatile("" : "+s"(pk));
-                const ResolveArgs ra = { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough };
-                resolveStrip<IDS, TEX, TW, TH, false, ZS>(ra, zbuf, shadeTab, coldTab, view, tileX0, tileY0, wave, lane);
+                const ResolveArgs ra = { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough,
+                                         NRM ? pk->normal : nullptr };
+                resolveStrip<IDS, TEX, TW, TH, false, ZS, kOutByPointer, NRM>(
+                    ra, zbuf, shadeTab, coldTab, view, tileX0, tileY0, wave, lane,
+                    (TEX && NRM) ? tileNormalTab<TEX, TW, TH, CLS, MULTI>(smem) : nullptr);
             }
             if (!(dskip & 128u)) MRX_STAMP(5);
             if (allDone) {
@@ -1299,8 +1430,11 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
             if (!(dskip & 128u)) MRX_STAMP(5);
             KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(pk));
-            const ResolveArgs ra = { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough };
-            resolveStrip<IDS, TEX, TW, TH, true, ZS>(ra, zbuf, shadeTab, coldTab, view, tileX0, tileY0, wave, lane);
+            const ResolveArgs ra = { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough,
+                                     NRM ? pk->normal : nullptr };
+            resolveStrip<IDS, TEX, TW, TH, true, ZS, kOutByPointer, NRM>(
+                ra, zbuf, shadeTab, coldTab, view, tileX0, tileY0, wave, lane,
+                (TEX && NRM) ? tileNormalTab<TEX, TW, TH, CLS, MULTI>(smem) : nullptr);
         }
         if (--left == 0)
             break;
@@ -1373,7 +1507,21 @@ void bvhTileKernelPVM(const RasterParams p)
 {
     tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, true, true>(p);
 }
+// the normals forms (p.normal): N over the uniform constants, NPV over the per-view tables and the
+// colour / material columns (null tests)
+template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
+__global__ __launch_bounds__(kWave *(TH / 8), 4)
+void bvhTileKernelN(const RasterParams p)
+{
+    tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, false, false, true>(p);
+}
 
+template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
+__global__ __launch_bounds__(kWave *(TH / 8), 4)
+void bvhTileKernelNPV(const RasterParams p)
+{
+    tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, true, true, true>(p);
+}
 
 // ---------------------------------------------------------------------------
 // Worlds of at most 64 triangles in at most 64 instance rows (every BASELINE scene: cube + plane
@@ -1442,7 +1590,9 @@ constexpr size_t flatLdsBytes(bool tex)
 // the set-up does no colour work and writes every record in the untextured form (object id only), the resolve loads
 // no texel and stores no rgb; rgb only: no depth reciprocal, no depth store.
 // PV: per-view projection -- a workgroup renders tiles of one view: its record is workgroup-uniform
-template <int IDS, bool TEX, int OUT, bool PV>
+// NRM: the normals form: the normal of triangle k rides in the texture slot of its untextured
+// record or, TEX, in a table of kFlatTris + 2 dwords behind everything else in LDS (flatLdsBytes).
+template <int IDS, bool TEX, int OUT, bool PV, bool NRM = false>
 __device__ __forceinline__ void flatKernelBody(const RasterParams p)
 {
     extern __shared__ __align__(16) unsigned char smem[];
@@ -1467,6 +1617,7 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
     float (*coldTab)[kCold] = reinterpret_cast<float (*)[kCold]>(shadeTab);                     // unified 48-byte records)
     float *hdr = reinterpret_cast<float *>(reinterpret_cast<unsigned char *>(shadeTab) + tabBytes(TEX, kFlatTris + 2));
     float *instRec = hdr + 4;                                                                    // [64][24]
+    uint32_t *const nrmTab = reinterpret_cast<uint32_t *>(instRec + (size_t)kFlatTris * kInstRecDw);   // (TEX && NRM) [66]
 
     unsigned long long *stamps = (MRX_BVH_DIAG && p.debugStamps && wave < 4)
         ? p.debugStamps + ((size_t)blockIdx.x * 4 + wave) * 8 : nullptr;
@@ -1563,6 +1714,7 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
         bool valid = false;
         if (hasT) {
             float shade[4] = { 0.f, 0.f, 0.f, 0.f }, cold[kCold];
+            uint32_t nrmv = kNormalBackground;
             if (PV) {
                 const SetupArgs sa = { p.tris, p.triMats, pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse,
                                        p.transposed };
@@ -1570,14 +1722,23 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
                 // (and with the material column, 4.14)
                 const uint32_t icol = (OUT != kOutDepth && p.instColor) ? p.instColor[myRow] : 0u;
                 const MatOverride mo = { (OUT != kOutDepth && p.instMat) ? p.instMat[myRow] : -1, p.numMaterials, p.matTable };
-                valid = setupTriangleCore<false, OUT != kOutDepth, true, true>(sa, vc.lv, y, myTri, objL, (int32_t)lane, c, shade,
-                                                                               cold, icol, mo);
+                if constexpr (NRM)
+                    valid = setupTriangleCore<false, OUT != kOutDepth, true, true>(sa, vc.lv, y, myTri, objL, (int32_t)lane, c,
+                                                                                   shade, cold, icol, mo, NormalOut { &nrmv });
+                else
+                    valid = setupTriangleCore<false, OUT != kOutDepth, true, true>(sa, vc.lv, y, myTri, objL, (int32_t)lane, c,
+                                                                                   shade, cold, icol, mo);
+            } else if constexpr (NRM) {
+                valid = setupTriangleCore<false, OUT != kOutDepth>(p, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold, 0u,
+                                                                   NoMatOverride(), NormalOut { &nrmv });
             } else {
                 valid = setupTriangleCore<false, OUT != kOutDepth>(p, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
             }
+            if (TEX && NRM)
+                nrmTab[lane + 1] = nrmv;
             const bool texRec = OUT != kOutDepth && valid && __float_as_int(shade[1]) >= 0;
             if (!TEX)
-                shadeTab[lane + 1] = make_float4(shade[0], shade[1], shade[2], __int_as_float(lane));
+                shadeTab[lane + 1] = make_float4(shade[0], NRM ? __uint_as_float(nrmv) : shade[1], shade[2], __int_as_float(lane));
             else if (!texRec) {
                 float *dst = coldTab[lane + 1];
                 dst[0] = shade[0];
@@ -1775,8 +1936,10 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
         {
             KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
             asm volatile("" : "+s"(pk));
-            const ResolveArgs ra = { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough };
-            resolveStrip<IDS, TEX, TW, TH, true, kFlatZS, OUT>(ra, zb, shadeTab, coldTab, view, tileX0, tileY0, wave, lane);
+            const ResolveArgs ra = { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough,
+                                     NRM ? pk->normal : nullptr };
+            resolveStrip<IDS, TEX, TW, TH, true, kFlatZS, OUT, NRM, false>(ra, zb, shadeTab, coldTab, view, tileX0, tileY0, wave, lane,
+                                                                    (TEX && NRM) ? nrmTab : nullptr);
         }
         MRX_STAMP(5);
         if (--left == 0)
@@ -1810,6 +1973,21 @@ void bvhFlatKernelPV(const RasterParams p)
     flatKernelBody<IDS, TEX, kOutByPointer, true>(p);
 }
 
+// the normals forms (p.normal): output selection by pointer in both
+template <int IDS, bool TEX>
+__global__ __launch_bounds__(kWave * 8, MRX_FLAT_ZBUFS == 2 ? 4 : 6)
+void bvhFlatKernelN(const RasterParams p)
+{
+    flatKernelBody<IDS, TEX, kOutByPointer, false, true>(p);
+}
+
+template <int IDS, bool TEX>
+__global__ __launch_bounds__(kWave * 8, MRX_FLAT_ZBUFS == 2 ? 4 : 6)
+void bvhFlatKernelNPV(const RasterParams p)
+{
+    flatKernelBody<IDS, TEX, kOutByPointer, true, true>(p);
+}
+
 }  // namespace
 
 namespace {
@@ -1827,6 +2005,14 @@ size_t ldsFor(uint32_t passInst, bool textured, int tw, int th, bool cls, uint32
 size_t bvhLdsBytes(uint32_t passInst, bool textured, bool classify, uint32_t groupViews, uint32_t texCap)
 {
     return ldsFor(passInst, textured, 64, 64, classify, groupViews, texCap);
+}
+
+// Does a launch take the instantiations that classify the listed large triangles per strip (CLS)?  Not the per-view
+// normals form of a textured scene: its classifying instantiations want 130 registers and spilled; it
+// renders with the plain ones, to the same pixels.
+static bool classifiesPerStrip(const RasterParams &p)
+{
+    return p.bvhTile == 0 && p.bvhClassify && !(p.normal && p.viewProj && p.anyTextured);
 }
 
 BvhLaunchShape bvhLaunchShape(const RasterParams &p)
@@ -1849,7 +2035,7 @@ BvhLaunchShape bvhLaunchShape(const RasterParams &p)
     }
     // as launchBvh and bvhTileKernel work them out
     const int tw = p.bvhTile == 2 ? 32 : 64, th = p.bvhTile == 0 ? 64 : 32;
-    const bool cls = p.bvhTile == 0 && p.bvhClassify;
+    const bool cls = classifiesPerStrip(p);
     const uint32_t tilesPerView = ((p.nfast + tw - 1) / tw) * ((p.nslow + th - 1) / th);
     const uint32_t groupViews = p.bvhGroupViews & 0xFFFFu;
     const bool multi = groupViews > 1;
@@ -1891,6 +2077,8 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
             return ge;
         if (dev < 0 || dev >= kMaxDevices)
             return hipErrorInvalidDevice;
+        // (the normals forms of textured scenes: a dword per record slot behind everything else)
+        const size_t flatLds = flatLdsBytes(tex) + ((p.normal && tex) ? (size_t)(kFlatTris + 2) * 4u : 0u);
 #define MRX_FLAT_K(K)                                                                           \
     do {                                                                                       \
         static bool allowed[kMaxDevices] = {};                                                 \
@@ -1898,13 +2086,13 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
             std::lock_guard<std::mutex> guard(attrMutex);                                      \
             if (!allowed[dev]) {                                                               \
                 const hipError_t e = hipFuncSetAttribute((const void *)K,                     \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)flatLdsBytes(tex)); \
+                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)flatLds); \
                 if (e != hipSuccess)                                                           \
                     return e;                                                                  \
                 allowed[dev] = true;                                                           \
             }                                                                                  \
         }                                                                                      \
-        K<<<grid, block, flatLdsBytes(tex), stream>>>(p);                                      \
+        K<<<grid, block, flatLds, stream>>>(p);                                                \
     } while (0)
 #define MRX_FLAT_O(I, T, O) MRX_FLAT_K((bvhFlatKernel<I, T, O>))
         // output selection: one instantiation per setting (kOutRGBD = the kernel as it always was); the per-view
@@ -1912,7 +2100,9 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
         const OutSel out = outSelOf(p.rgb, p.depth);
 #define MRX_FLAT(I, T)                                                                          \
     do {                                                                                       \
-        if (p.viewProj)          MRX_FLAT_K((bvhFlatKernelPV<I, T>));                          \
+        if (p.normal && p.viewProj) MRX_FLAT_K((bvhFlatKernelNPV<I, T>));                      \
+        else if (p.normal)       MRX_FLAT_K((bvhFlatKernelN<I, T>));                           \
+        else if (p.viewProj)     MRX_FLAT_K((bvhFlatKernelPV<I, T>));                          \
         else if (out == kOutDepth) MRX_FLAT_O(I, T, kOutDepth);                                \
         else if (out == kOutRGB) MRX_FLAT_O(I, T, kOutRGB);                                    \
         else                     MRX_FLAT_O(I, T, kOutRGBD);                                   \
@@ -1947,7 +2137,10 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
     }
     if (tex && (p.bvhTexCap < 64u || p.bvhTexCap > 1023u))
         return hipErrorInvalidValue;
-    const size_t lds = ldsFor(p.bvhPassInst, tex, tw, th, p.bvhTile == 0 && p.bvhClassify, groupViews, p.bvhTexCap);
+    // (the normals forms of textured scenes: a dword per record slot behind everything else, tileNormalTab)
+    const bool cls = classifiesPerStrip(p);
+    const size_t lds = ldsFor(p.bvhPassInst, tex, tw, th, cls, groupViews, p.bvhTexCap) +
+                       ((p.normal && tex) ? (size_t)p.bvhTexCap * 4u : 0u);
     const dim3 grid(items), block(kWave * (th / 8));
     // The kernel needs more dynamic LDS than the 64 KB a launch may ask for by default.  The
     // opt-in is a property of (function, device) -- a renderer per device in one process
@@ -1980,15 +2173,17 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
     // the per-view form (p.viewProj): the same shape, its per-view instantiation
 #define MRX_BVH(I, T, W, H, C, M)                                                               \
     do {                                                                                       \
-        if (p.viewProj && p.instMat) MRX_BVH_K((bvhTileKernelPVM<I, T, W, H, C, M>));          \
+        if (p.normal && p.viewProj) MRX_BVH_K((bvhTileKernelNPV<I, T, W, H, (C) && !(T), M>)); \
+        else if (p.normal) MRX_BVH_K((bvhTileKernelN<I, T, W, H, C, M>));                      \
+        else if (p.viewProj && p.instMat) MRX_BVH_K((bvhTileKernelPVM<I, T, W, H, C, M>));     \
         else if (p.viewProj) MRX_BVH_K((bvhTileKernelPV<I, T, W, H, C, M>));                   \
         else            MRX_BVH_K((bvhTileKernel<I, T, W, H, C, M>));                          \
     } while (0)
 #define MRX_BVH_SHAPE(I, T)                                                                    \
     do {                                                                                       \
-        if (p.bvhTile == 0 && multi && p.bvhClassify) MRX_BVH(I, T, 64, 64, true, true);       \
+        if (p.bvhTile == 0 && multi && cls) MRX_BVH(I, T, 64, 64, true, true);                 \
         else if (p.bvhTile == 0 && multi) MRX_BVH(I, T, 64, 64, false, true);                  \
-        else if (p.bvhTile == 0 && p.bvhClassify) MRX_BVH(I, T, 64, 64, true, false);          \
+        else if (p.bvhTile == 0 && cls) MRX_BVH(I, T, 64, 64, true, false);                    \
         else if (p.bvhTile == 0) MRX_BVH(I, T, 64, 64, false, false);                          \
         else if (p.bvhTile == 1) MRX_BVH(I, T, 64, 32, false, false);                          \
         else MRX_BVH(I, T, 32, 32, false, false);                                              \

@@ -9,6 +9,7 @@
 //                     [--light X,Y,Z[,AMBIENT,DIFFUSE]]   (every world's directional light; no counterpart upstream)
 //                     [--instance-colors SEED]   (an opaque colour override per instance row, splitmix64(SEED, row))
 //                     [--instance-materials SEED]   (a material override per instance row, rows 1::4 left without)
+//                     [--normals]   (the surface-normal output; --dump-last-frame also writes NAME.normals.png)
 //
 // --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
 // renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
@@ -71,6 +72,8 @@ struct Args {
     // --instance-materials SEED: every instance row but rows 1::4 overridden with a material drawn from the seed and the row
     bool hasMaterials = false;
     uint64_t materialSeed = 0;
+    // --normals: render the surface-normal output too; --dump-last-frame then also writes NAME.normals.png
+    bool normals = false;
 };
 
 // a number of the whole argument, finite
@@ -89,7 +92,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -114,6 +117,8 @@ Args parse(int argc, char **argv)
             a.demo = !std::strcmp(argv[++i], "demo");
         } else if (!std::strcmp(argv[i], "--depth")) {
             a.dumpDepth = true;
+        } else if (!std::strcmp(argv[i], "--normals")) {
+            a.normals = true;
         } else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) {
             a.gpus = (uint32_t)std::atoi(argv[++i]);
         } else if (!std::strcmp(argv[i], "--vfov") && i + 1 < argc) {
@@ -316,14 +321,15 @@ void buildDemo(Scene &s, uint32_t n, const std::string &dataDir)
 // and is transposed back (dump.cpp:9-21); rasterizer storage is row-major.
 // DumpWhat::InvDepth (a depth-only renderer's default): grey 255 * dmin / d, dmin = the
 // nearest depth of the frame, 0 for background.
-enum class DumpWhat { Rgb, Depth, InvDepth };
+// DumpWhat::Normal: the surface-normal tensor, in rgb's format (its bytes as they are, alpha included).
+enum class DumpWhat { Rgb, Depth, InvDepth, Normal };
 bool dumpTiled(const std::string &name, mrx_renderer *shard, uint32_t numImages, uint32_t resX,
                uint32_t resY, DumpWhat what, bool transpose)
 {
-    const bool depth = what != DumpWhat::Rgb;
+    const bool depth = what != DumpWhat::Rgb && what != DumpWhat::Normal;
     const size_t bytesPerImage = (size_t)4 * resX * resY;
     std::vector<uint8_t> host(bytesPerImage * numImages);
-    if (mrx_copy_to_host(shard, depth ? MRX_BUF_DEPTH : MRX_BUF_RGB,
+    if (mrx_copy_to_host(shard, depth ? MRX_BUF_DEPTH : what == DumpWhat::Normal ? MRX_BUF_NORMAL : MRX_BUF_RGB,
                          host.data(), host.size()) != MRX_OK) {
         std::fprintf(stderr, "%s\n", mrx_last_error());
         return false;
@@ -451,6 +457,7 @@ int main(int argc, char **argv)
         cfg.numDevices = args.gpus;
     }
     cfg.renderOutputs = args.outputs;
+    cfg.normals = args.normals;
 
     Manager mgr(cfg);              // aborts (FATAL) on failure, like the reference
     mgr.sync();
@@ -483,6 +490,8 @@ int main(int argc, char **argv)
             const DumpWhat what = args.dumpDepth ? DumpWhat::Depth
                                   : args.outputs == Manager::RenderOutputs::Depth ? DumpWhat::InvDepth : DumpWhat::Rgb;
             ok = dumpTiled(name, sh, hi - lo, args.width, resY, what, rt) && ok;
+            if (args.normals)
+                ok = dumpTiled(name + ".normals", sh, hi - lo, args.width, resY, DumpWhat::Normal, rt) && ok;
         }
     }
     if (!ok)

@@ -104,6 +104,8 @@ Manager::Manager(const Config &cfg)
         c.flags |= MRX_FLAG_INSTANCE_COLORS;
     if (cfg.instanceMaterialColumn || cfg.instanceMaterials)
         c.flags |= MRX_FLAG_INSTANCE_MATERIALS;
+    if (cfg.normals)
+        c.flags |= MRX_FLAG_NORMALS;
     if (cfg.renderOutputs == RenderOutputs::Depth)
         c.flags |= MRX_FLAG_NO_RGB;
     else if (cfg.renderOutputs == RenderOutputs::RGB)
@@ -169,6 +171,8 @@ Tensor Manager::instanceObjectTensor(uint32_t shard) const { return impl_->wrap(
 Tensor Manager::instanceScaleTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_SCALE, shard); }
 Tensor Manager::instanceColorTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_COLOR, shard); }
 Tensor Manager::instanceMaterialTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_MATERIAL, shard); }
+
+Tensor Manager::normalTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_NORMAL, shard); }
 
 Tensor Manager::instancePositionTensor(uint32_t shard) const
 {

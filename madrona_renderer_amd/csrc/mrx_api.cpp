@@ -235,11 +235,17 @@ bool firstKindIsOneBlock(size_t px)
 
 // Output selection (MRX_FLAG_NO_RGB / MRX_FLAG_NO_DEPTH): a tensor that is not selected is
 // not allocated, and its slab drops out of the layout -- the first tensor present owns the block.
+// Normals (MRX_FLAG_NORMALS): one more slab behind everything above -- every other tensor keeps its
+// offset and phase -- at a phase of its own (MRX_OUT_SKEW_NORMAL_KB, 384 KiB: neither rgb's 0, depth's 256 nor the
+// ids' 64; measured against 128 KiB, profiles/r12_normals_placement.txt: level on 64 MiB and 256 MiB tensors, and on
+// 1 GiB ones the four tensors reach a faster placement mode from it more often).
 hipError_t allocOutputs(size_t px, bool wantRgb, bool wantDepth, bool wantIds, bool oneAllocation,
-                        DevBuf<uint32_t> &rgb, DevBuf<float> &depth, DevBuf<int32_t> &ids)
+                        DevBuf<uint32_t> &rgb, DevBuf<float> &depth, DevBuf<int32_t> &ids,
+                        bool wantNormal, DevBuf<uint32_t> &normal)
 {
     const size_t depthPhase = outPhase("MRX_OUT_SKEW_DEPTH_KB", 256u << 10);
     const size_t idsPhase = outPhase("MRX_OUT_SKEW_IDS_KB", 64u << 10);
+    const size_t normalPhase = outPhase("MRX_OUT_SKEW_NORMAL_KB", 384u << 10);
     if (!oneAllocation) {
         // One allocation per tensor, made back to back, the phases applied
         // inside the (2 MiB-aligned) blocks.  Whether that yields the intended
@@ -267,8 +273,13 @@ hipError_t allocOutputs(size_t px, bool wantRgb, bool wantDepth, bool wantIds, b
             e = ids.alloc(px, idsPhase);
             ids.ptr = reinterpret_cast<int32_t *>(static_cast<char *>(ids.base) + idsPhase);
         }
+        if (e == hipSuccess && wantNormal) {
+            gap();
+            e = normal.alloc(px, normalPhase);
+            normal.ptr = reinterpret_cast<uint32_t *>(static_cast<char *>(normal.base) + normalPhase);
+        }
         if (e != hipSuccess) {
-            rgb.release(); depth.release(); ids.release();
+            rgb.release(); depth.release(); ids.release(); normal.release();
         }
         return e;
     }
@@ -279,7 +290,9 @@ hipError_t allocOutputs(size_t px, bool wantRgb, bool wantDepth, bool wantIds, b
     const size_t idsOff = wantDepth ? depthOff + tb + kOutPeriod - (depthOff % kOutPeriod) + idsPhase
                                     : wantRgb ? tb + idsPhase : 0;
     const size_t end = (wantIds ? idsOff : wantDepth ? depthOff : 0) + px * 4;
-    const size_t total = end;
+    // normals: at their phase of the first period that starts behind the last slab
+    const size_t normalOff = (end + kOutPeriod - 1) / kOutPeriod * kOutPeriod + normalPhase;
+    const size_t total = wantNormal ? normalOff + px * 4 : end;
     const char *how = std::getenv("MRX_OUT_ALLOC");
     int dev = 0;
     (void)hipGetDevice(&dev);
@@ -294,6 +307,8 @@ hipError_t allocOutputs(size_t px, bool wantRgb, bool wantDepth, bool wantIds, b
         depth.view(base + depthOff, px);
     if (wantIds && (wantRgb || wantDepth))
         ids.view(base + idsOff, px);
+    if (wantNormal)
+        normal.view(base + normalOff, px);
     return hipSuccess;
 }
 
@@ -343,6 +358,7 @@ struct mrx_renderer {
     DevBuf<uint32_t> rgb;
     DevBuf<float> depth;
     DevBuf<int32_t> ids;
+    DevBuf<uint32_t> normal;                    // MRX_FLAG_NORMALS; no pointer without the flag
     DevBuf<unsigned long long> stamps;
     // XCD phase feedback (raster.hip): a host-mapped word workgroup 0 reports its XCC id to
     uint32_t *xccHost = nullptr, *xccDev = nullptr;
@@ -440,7 +456,7 @@ struct mrx_renderer {
         if (matEv)
             (void)hipEventDestroy(matEv);
         poseBlock.release(); geomBlock.release();
-        rgb.release(); depth.release(); ids.release(); stamps.release();
+        rgb.release(); depth.release(); ids.release(); normal.release(); stamps.release();
         if (xccHost) (void)hipHostFree(xccHost);
         bvhNodes.release(); bvhLeafTris.release(); worldInstStart.release();
         viewWorld.release(); instKBase.release(); objInfo.release();
@@ -966,7 +982,9 @@ int chooseBvhGroups(mrx_renderer &r)
                            (maxWorldInst <= 64u || 2u * nviews >= 3u * resident);
         const bool pairsPay = mixed || nviews >= 4u * resident;
         // (textured: pairs as long as two TLAS blocks leave room for 256 records)
-        p.bvhGroupViews = pairsPay && bvhLdsBytes(p.bvhPassInst, tex, p.bvhClassify != 0, 2u, 256u) <= 80u * 1024u ? 2u : 1u;
+        // (a textured renderer with the normals output: its dword per record slot counts, as below)
+        p.bvhGroupViews = pairsPay && bvhLdsBytes(p.bvhPassInst, tex, p.bvhClassify != 0, 2u, 256u) +
+                                          ((tex && p.normal) ? 256u * 4u : 0u) <= 80u * 1024u ? 2u : 1u;
         if (p.bvhGroupViews == 2u && mixed && !std::getenv("MRX_BVH_NO_MIXED"))
             p.bvhGroupViews |= 0x10000u;
         if (const char *dbg = std::getenv("MRX_BVH_GROUP_VIEWS")) {
@@ -991,11 +1009,14 @@ int chooseBvhGroups(mrx_renderer &r)
     const uint32_t wgs = (p.bvhGroupViews & 0x10000u) ? resident
                          : gv > 1 ? (nviews + gv - 1) / gv : nviews * ((tiles + groupTiles - 1) / groupTiles);
     // textured worlds: as many 48-byte shading records per round as fit the half CU beside the TLAS block(s), in 32s
-    // (profiles/r04_bvh_textured.txt; MRX_BVH_TEX_CAP overrides)
+    // (profiles/r04_bvh_textured.txt; MRX_BVH_TEX_CAP overrides).  With the normals output a record
+    // costs 52 bytes -- the normals forms keep a dword per record slot behind everything else -- so the cap is smaller
+    // and the workgroup stays within the half CU: two per CU, as the launch shape and the priority scheme assume.
     {
+        const uint32_t perSlot = p.normal ? 4u : 0u;
         uint32_t cap = 64;
         while (cap + 32u <= 1008u &&
-               bvhLdsBytes(p.bvhPassInst, true, p.bvhClassify != 0, gv, cap + 32u) <= 80u * 1024u)
+               bvhLdsBytes(p.bvhPassInst, true, p.bvhClassify != 0, gv, cap + 32u) + perSlot * (cap + 32u) <= 80u * 1024u)
             cap += 32u;
         if (const char *dbg = std::getenv("MRX_BVH_TEX_CAP"))
             cap = (uint32_t)std::max(64, std::min((int)cap, std::atoi(dbg)));
@@ -1580,7 +1601,8 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
             if (pre.alloc((size_t)std::atoll(dbg) << 20) != hipSuccess)
                 (void)hipGetLastError();
         MRX_HIP(allocOutputs(px, !(cfg.flags & MRX_FLAG_NO_RGB), !(cfg.flags & MRX_FLAG_NO_DEPTH),
-                             rt || (cfg.flags & MRX_FLAG_VISIBILITY_IDS), firstKindIsOneBlock(px), r.rgb, r.depth, r.ids));
+                             rt || (cfg.flags & MRX_FLAG_VISIBILITY_IDS), firstKindIsOneBlock(px), r.rgb, r.depth, r.ids,
+                             (cfg.flags & MRX_FLAG_NORMALS) != 0, r.normal));
         const char *hold = std::getenv("MRX_OUT_PRE_HOLD");
         if (!(hold && hold[0] == '1'))
             pre.release();
@@ -1610,6 +1632,7 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     p.rgb = r.rgb.ptr;
     p.depth = r.depth.ptr;
     p.ids = wantIds ? r.ids.ptr : nullptr;
+    p.normal = r.normal.ptr;
     p.numViews = nviews;
     {
         int cus = 0;
@@ -1752,7 +1775,8 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     inf.bvh_depth = blas.maxDepth;
     inf.max_world_instances = maxWorldInst;
     inf.num_shards = 1;
-    inf.bytes_per_step = (uint64_t)px * (4u * ((r.rgb.ptr ? 1u : 0u) + (r.depth.ptr ? 1u : 0u)) + (wantIds ? 4u : 0u)) +
+    inf.bytes_per_step = (uint64_t)px * (4u * ((r.rgb.ptr ? 1u : 0u) + (r.depth.ptr ? 1u : 0u) + (r.normal.ptr ? 1u : 0u)) +
+                                         (wantIds ? 4u : 0u)) +
                          (44ull + (r.instColor.ptr ? 4ull : 0ull) + (r.instMat.ptr ? 4ull : 0ull)) * inf.num_instances +
                          28ull * nviews;
     return bindGeometry(r);
@@ -2082,10 +2106,10 @@ int mrx_device_count(void)
 static int choosePlacement(mrx_renderer *r)
 {
     const bool wantRgb = r->rgb.ptr != nullptr, wantDepth = r->depth.ptr != nullptr;
-    const bool wantIds = r->ids.ptr != nullptr;
+    const bool wantIds = r->ids.ptr != nullptr, wantNormal = r->normal.ptr != nullptr;
     const size_t px = wantRgb ? r->rgb.count : r->depth.count;
     // (keyed on the bytes actually allocated: an output that is not selected has no tensor)
-    const size_t bytes = px * 4 * ((wantRgb ? 1 : 0) + (wantDepth ? 1 : 0) + (wantIds ? 1 : 0));
+    const size_t bytes = px * 4 * ((wantRgb ? 1 : 0) + (wantDepth ? 1 : 0) + (wantIds ? 1 : 0) + (wantNormal ? 1 : 0));
     int maxTries = (bytes >= (256ull << 20) && bytes <= (16ull << 30)) ? 2 : 1;
     if (const char *dbg = std::getenv("MRX_PLACEMENT_TRIES"))
         maxTries = std::max(1, std::min(16, std::atoi(dbg)));
@@ -2099,13 +2123,14 @@ static int choosePlacement(mrx_renderer *r)
     if (maxTries <= 1)
         return MRX_OK;
     const bool trace = std::getenv("MRX_PLACEMENT_TRACE") != nullptr;
-    struct Cand { DevBuf<uint32_t> rgb; DevBuf<float> depth; DevBuf<int32_t> ids; float us = 0.0f; };
+    struct Cand { DevBuf<uint32_t> rgb; DevBuf<float> depth; DevBuf<int32_t> ids; DevBuf<uint32_t> normal; float us = 0.0f; };
     auto bind = [&](const Cand &c) {
         r->params.rgb = c.rgb.ptr;
         r->params.depth = c.depth.ptr;
         r->params.ids = wantIds ? c.ids.ptr : nullptr;
+        r->params.normal = c.normal.ptr;
     };
-    auto freeCand = [](Cand &c) { c.rgb.release(); c.depth.release(); c.ids.release(); };
+    auto freeCand = [](Cand &c) { c.rgb.release(); c.depth.release(); c.ids.release(); c.normal.release(); };
     auto launch = [&]() { return r->launch(); };
     auto timeBatch = [&](int n, float &ms) -> hipError_t {
         hipError_t e = hipEventRecord(r->ev0, r->stream);
@@ -2117,7 +2142,7 @@ static int choosePlacement(mrx_renderer *r)
         return e;
     };
     Cand best;
-    best.rgb = r->rgb; best.depth = r->depth; best.ids = r->ids;   // what buildScene allocated
+    best.rgb = r->rgb; best.depth = r->depth; best.ids = r->ids; best.normal = r->normal;   // what buildScene allocated
     // a render takes ~0.1 - 1 ms here: batches of ~0.5 ms, ~40 ms of warm-up (clocks)
     hipError_t st = hipSuccess;                   // first error; the cleanup below always runs
     bind(best);
@@ -2154,7 +2179,7 @@ static int choosePlacement(mrx_renderer *r)
             (void)hipGetLastError();
         Cand c;
         const hipError_t ae = allocOutputs(px, wantRgb, wantDepth, wantIds, ((k & 1) == 0) == firstKindIsOneBlock(px),
-                                           c.rgb, c.depth, c.ids);
+                                           c.rgb, c.depth, c.ids, wantNormal, c.normal);
         sp.release();
         if (ae != hipSuccess) {
             (void)hipGetLastError();                  // out of memory: make do with what there is
@@ -2183,7 +2208,7 @@ static int choosePlacement(mrx_renderer *r)
     if (trace)
         std::fprintf(stderr, "mrx: output placement, us/render:%s -> %.2f (rgb %p depth %p)\n", log.c_str(),
                      best.us, (void *)best.rgb.ptr, (void *)best.depth.ptr);
-    r->rgb = best.rgb; r->depth = best.depth; r->ids = best.ids;
+    r->rgb = best.rgb; r->depth = best.depth; r->ids = best.ids; r->normal = best.normal;
     r->placementKeptUs = best.us;
     bind(best);
     if (st != hipSuccess)
@@ -2575,6 +2600,14 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
         *ndim = 4; *dtype = MRX_DTYPE_U8; ptr = r->rgb.ptr;
         if (!ptr) {
             fail(MRX_E_UNSUPPORTED, "rgb not rendered: this renderer was created depth-only (MRX_FLAG_NO_RGB)");
+            return nullptr;
+        }
+        break;
+    case MRX_BUF_NORMAL:    // the surface-normal output: storage as rgb's
+        dims[0] = V; dims[1] = S; dims[2] = F; dims[3] = 4;
+        *ndim = 4; *dtype = MRX_DTYPE_U8; ptr = r->normal.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED, "normals not rendered: this renderer was created without MRX_FLAG_NORMALS");
             return nullptr;
         }
         break;

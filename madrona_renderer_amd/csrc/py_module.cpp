@@ -178,6 +178,10 @@ PYBIND11_MODULE(madrona_renderer, m)
     m.attr("MRX_FLAG_INSTANCE_MATERIALS") = (uint32_t)MRX_FLAG_INSTANCE_MATERIALS;
     m.attr("MRX_BUF_INSTANCE_MATERIAL") = (int)MRX_BUF_INSTANCE_MATERIAL;
     m.attr("MRX_NUM_BUFFERS_EXT") = (int)MRX_NUM_BUFFERS_EXT;
+    // ... and of the surface-normal output
+    m.attr("MRX_FLAG_NORMALS") = (uint32_t)MRX_FLAG_NORMALS;
+    m.attr("MRX_BUF_NORMAL") = (int)MRX_BUF_NORMAL;
+    m.attr("MRX_NUM_BUFFERS_EXT2") = (int)MRX_NUM_BUFFERS_EXT2;
     m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
     m.attr("MRX_CONFIG_SIZE") = (uint32_t)sizeof(mrx_config);
 
@@ -297,7 +301,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<Sim::WorldInit> &worlds,
                          const std::vector<int> &device_ids, int max_instances_per_world,
                          Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors,
-                         py::object instance_materials) {
+                         py::object instance_materials, bool normals) {
                  if (mesh_vertices.size() && (mesh_vertices.ndim() != 2 || mesh_vertices.shape(1) != 3))
                      throw py::value_error("mesh_vertices must have shape [N, 3]");
                  if (mesh_uvs.size() && (mesh_uvs.ndim() != 2 || mesh_uvs.shape(1) != 2))
@@ -411,6 +415,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                      cfg.instanceMaterials = matIds.data();
                      cfg.instanceMaterialColumn = true;
                  }
+                 cfg.normals = normals;
                  return new Manager(cfg);
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -431,7 +436,9 @@ PYBIND11_MODULE(madrona_renderer, m)
              // instance_colors = True or a [num_instances, 4] uint8 array (r, g, b, a): the colour override column
              py::arg("instance_colors") = py::none(),
              // instance_materials = True or a [num_instances] int32 array: the material override column
-             py::arg("instance_materials") = py::none())
+             py::arg("instance_materials") = py::none(),
+             // normals = True: the surface-normal output, normal_tensor()
+             py::arg("normals") = false)
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -440,6 +447,10 @@ PYBIND11_MODULE(madrona_renderer, m)
              py::arg("shard") = py::none())
         .def("depth_tensor",
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().depthTensor(shardOf(self, shard))); },
+             py::arg("shard") = py::none())
+        // u8 [views, H, W, 4], storage as rgb's: the view-space normal of every pixel's winning triangle (needs normals=True)
+        .def("normal_tensor",
+             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().normalTensor(shardOf(self, shard))); },
              py::arg("shard") = py::none())
         .def("segmask_tensor",
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().segmaskTensor(shardOf(self, shard))); },

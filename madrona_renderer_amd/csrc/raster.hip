@@ -108,9 +108,10 @@ struct GroupSetupArgs {
 // setupTriangle under the projection constants `pr` of the view and the light `lt` of its world (per-view form), and
 // under the colour and material overrides of the instance row where the renderer has the columns (DESIGN.md 4.13,
 // 4.14; wave-uniform tests)
+template <typename NRMOUT = NoNormalOut>
 __device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const ViewProj &pr, const ViewLight &lt,
                                                   const ViewConst &vc, WorldTri wt, int32_t kWorld, TriPlanes &out,
-                                                  float *shade, float *cold)
+                                                  float *shade, float *cold, const NRMOUT nrm = NRMOUT())
 {
     const GroupSetupArgs sa = { p.tris, p.triMats, p.instPos, p.instRot, p.instScale,
                                 pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse, p.transposed };
@@ -122,15 +123,17 @@ __device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const V
         return MatOverride { p.instMat ? p.instMat[wt.inst] : -1, p.numMaterials, p.matTable };
     };
     return setupTriangleCore<true, true, true, true>(sa, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold, icol,
-                                                     matOf);
+                                                     matOf, nrm);
 }
 
 // S for one chunk of up to 64 world-triangles; returns the valid-lane mask.
 // PV: the per-view form, the view's projection constants in `pr` and its world's light in `lt`.
-template <bool PV>
+// NRM: the normals form: the packed normal of the lane's triangle goes to nrmTab[lane].
+template <bool PV, bool NRM = false>
 __device__ __forceinline__ uint64_t setupChunk(const RasterParams &p, const ViewConst &vc,
                                                const TileCtx &t, uint32_t chunk, int lane,
-                                               WaveLds &L, const ViewProj &pr, const ViewLight &lt)
+                                               WaveLds &L, const ViewProj &pr, const ViewLight &lt,
+                                               uint32_t *nrmTab = nullptr)
 {
     bool valid = false;
     const uint32_t k = chunk + lane;
@@ -138,8 +141,12 @@ __device__ __forceinline__ uint64_t setupChunk(const RasterParams &p, const View
         const WorldTri wt = p.viewTris[t.triBegin + k];
         TriPlanes c;
         float *h = L.hot[lane];
-        valid = PV ? setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, h + 12, L.cold[lane])
-                   : setupTriangle(p, vc, wt, (int32_t)k, c, h + 12, L.cold[lane]);
+        if (NRM)
+            valid = PV ? setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, h + 12, L.cold[lane], NormalOut { nrmTab + lane })
+                       : setupTriangle(p, vc, wt, (int32_t)k, c, h + 12, L.cold[lane], NormalOut { nrmTab + lane });
+        else
+            valid = PV ? setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, h + 12, L.cold[lane])
+                       : setupTriangle(p, vc, wt, (int32_t)k, c, h + 12, L.cold[lane]);
         h[0] = c.A0; h[1] = c.B0; h[2] = c.C0;
         h[3] = c.A1; h[4] = c.B1; h[5] = c.C1;
         h[6] = c.A2; h[7] = c.B2; h[8] = c.C2;
@@ -207,10 +214,13 @@ __device__ __forceinline__ void rasterBandBrute(const WaveLds &L, uint64_t valid
 
 // OUT: output selection (raster.hpp OutSel: kOutRGBD, kOutDepth or kOutRGB; kOutByPointer in the per-view form)
 // PV: per-view projection -- a wave renders one tile, so the view's record is wave-uniform
-template <bool IDS, bool MULTI, int OUT, bool PV>
+// NRM: the normals form: the chunk's packed normals in an LDS array of their own, one more
+// resolved dword per pixel, one more store
+template <bool IDS, bool MULTI, int OUT, bool PV, bool NRM = false>
 __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
 {
     __shared__ WaveLds lds[kWavesPerBlock];
+    __shared__ uint32_t nrmLds[NRM ? kWavesPerBlock : 1][NRM ? kChunk : 1];
     touchKernelArguments();
     const int wave = threadIdx.x / kWave;
     const int lane = threadIdx.x % kWave;
@@ -220,6 +230,7 @@ __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
     if (!tileSetup<PV>(p, blockIdx.x * kWavesPerBlock + wave, lane, t, vc, lt))
         return;
     WaveLds &L = lds[wave];
+    uint32_t *const nrmTab = NRM ? nrmLds[wave] : nullptr;
     const ViewProj pr = viewProjOf(p, PV, t.view);
 
     float pxf[8];
@@ -230,19 +241,22 @@ __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
 
     uint64_t mask0 = 0;
     if (!MULTI)
-        mask0 = setupChunk<PV>(p, vc, t, 0, lane, L, pr, lt);
+        mask0 = setupChunk<PV, NRM>(p, vc, t, 0, lane, L, pr, lt, nrmTab);
 
     for (int band = 0; band < 4; ++band) {
         float best[kBlocksPerBand];
         int32_t bid[kBlocksPerBand];
         uint32_t outRgba[kBlocksPerBand];
         int32_t outId[kBlocksPerBand];
+        uint32_t outNrm[kBlocksPerBand];
 #pragma unroll
         for (int b = 0; b < kBlocksPerBand; ++b) {
             best[b] = p.invFar;
             bid[b] = -1;
             outRgba[b] = 0xFF000000u;
             outId[b] = -1;
+            if (NRM)
+                outNrm[b] = kNormalBackground;
         }
         const float py0 = (float)(t.tileY0 + band * kBandRows + t.ly);
         const float py1 = (float)(t.tileY0 + band * kBandRows + 8 + t.ly);
@@ -251,19 +265,25 @@ __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
             rasterBandBrute(L, mask0, pxf, py0, py1, invNear, best, bid);
 #pragma unroll
             for (int b = 0; b < kBlocksPerBand; ++b)
-                if (bid[b] >= 0)
+                if (bid[b] >= 0) {
                     resolvePixel<IDS>(p, L, bid[b], best[b], pxf[b & 7],
                                       (b >> 3) ? py1 : py0, outRgba[b], outId[b]);
+                    if (NRM)
+                        outNrm[b] = nrmTab[bid[b]];
+                }
         } else {
             for (uint32_t chunk = 0; chunk < t.numTris; chunk += kChunk) {
-                const uint64_t mask = setupChunk<PV>(p, vc, t, chunk, lane, L, pr, lt);
+                const uint64_t mask = setupChunk<PV, NRM>(p, vc, t, chunk, lane, L, pr, lt, nrmTab);
                 rasterBandBrute(L, mask, pxf, py0, py1, invNear, best, bid);
                 // resolve this chunk's winners before its records are replaced
 #pragma unroll
                 for (int b = 0; b < kBlocksPerBand; ++b) {
-                    if (bid[b] >= 0)
+                    if (bid[b] >= 0) {
                         resolvePixel<IDS>(p, L, bid[b], best[b], pxf[b & 7],
                                           (b >> 3) ? py1 : py0, outRgba[b], outId[b]);
+                        if (NRM)
+                            outNrm[b] = nrmTab[bid[b]];
+                    }
                     bid[b] = -1;
                 }
                 waveLdsSync();
@@ -286,6 +306,8 @@ __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
                     p.depth[o] = dep;
                 if (IDS)
                     p.ids[o] = outId[b];
+                if (NRM)
+                    p.normal[o] = outNrm[b];
             }
         }
     }
@@ -304,6 +326,22 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock)
 void rasterBruteKernelPV(const RasterParams p)
 {
     bruteKernelBody<IDS, MULTI, kOutByPointer, true>(p);
+}
+
+// the normals forms (p.normal): N over the uniform constants, NPV over the per-view tables (and the
+// colour / material columns behind their null checks); output selection by pointer in both
+template <bool IDS, bool MULTI>
+__global__ __launch_bounds__(kWave *kWavesPerBlock)
+void rasterBruteKernelN(const RasterParams p)
+{
+    bruteKernelBody<IDS, MULTI, kOutByPointer, false, true>(p);
+}
+
+template <bool IDS, bool MULTI>
+__global__ __launch_bounds__(kWave *kWavesPerBlock)
+void rasterBruteKernelNPV(const RasterParams p)
+{
+    bruteKernelBody<IDS, MULTI, kOutByPointer, true, true>(p);
 }
 
 // Bits 0..15: the tile's 32x8 regions (bit 2*strip + half) the lane's triangle
@@ -425,12 +463,14 @@ __device__ __forceinline__ void rasterRegion(const float (*planes)[16], uint64_t
 // Store a region whose pixels are already shaded (chunked kernel).  A lane owns
 // four consecutive pixels of one row (pixel b of the lane is x = fx0 + b), so
 // the common case is one 16-byte store per output tensor per lane.
-template <bool IDS>
+// NRM: the normals form -- `nrm` holds the pixels' packed normals, one more store of the same shape
+template <bool IDS, bool NRM = false>
 __device__ __forceinline__ void outputRegion(const RasterParams &p, const TileCtx &t,
                                              uint32_t fx0, uint32_t fy, float invFar,
                                              const float (&best)[kRegionBlocks],
                                              const uint32_t (&rgba)[kRegionBlocks],
-                                             const int32_t (&id)[kRegionBlocks])
+                                             const int32_t (&id)[kRegionBlocks],
+                                             const uint32_t *nrm = nullptr)
 {
     float dep[kRegionBlocks];
 #pragma unroll
@@ -449,6 +489,8 @@ __device__ __forceinline__ void outputRegion(const RasterParams &p, const TileCt
                           __float_as_uint(dep[2]), __float_as_uint(dep[3]));
         if (IDS)
             streamStore16(p.writeThrough, p.ids + o, (uint32_t)id[0], (uint32_t)id[1], (uint32_t)id[2], (uint32_t)id[3]);
+        if (NRM)
+            streamStore16(p.writeThrough, p.normal + o, nrm[0], nrm[1], nrm[2], nrm[3]);
     } else {
 #pragma unroll
         for (int b = 0; b < kRegionBlocks; ++b) {
@@ -459,6 +501,8 @@ __device__ __forceinline__ void outputRegion(const RasterParams &p, const TileCt
                     streamStore4(p.writeThrough, p.depth + o + b, __float_as_uint(dep[b]));
                 if (IDS)
                     streamStore4(p.writeThrough, p.ids + o + b, (uint32_t)id[b]);
+                if (NRM)
+                    streamStore4(p.writeThrough, p.normal + o + b, nrm[b]);
             }
         }
     }
@@ -485,10 +529,12 @@ struct TileLds {
 __device__ __forceinline__ const float *shadeRec(const PassRecs &L, int32_t w) { return L.shade[w]; }
 
 // PV: per-view projection -- a workgroup renders one tile of one view: its record is uniform
-template <bool IDS, bool PV>
+// NRM: the normals form: the pass's packed normals in an LDS array of their own
+template <bool IDS, bool PV, bool NRM = false>
 __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
 {
     __shared__ TileLds lds;
+    __shared__ uint32_t nrmLds[NRM ? kPass : 1];
     touchKernelArguments();
     const int wave = threadIdx.x / kWave;
     const int lane = threadIdx.x % kWave;
@@ -506,6 +552,7 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
     int32_t bid[4][kRegionBlocks];
     uint32_t outRgba[4][kRegionBlocks];
     int32_t outId[4][kRegionBlocks];
+    uint32_t outNrm[4][kRegionBlocks];
 #pragma unroll
     for (int g = 0; g < 4; ++g)
 #pragma unroll
@@ -514,6 +561,8 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
             bid[g][b] = -1;
             outRgba[g][b] = 0xFF000000u;
             outId[g][b] = -1;
+            if (NRM)
+                outNrm[g][b] = kNormalBackground;
         }
 
     for (uint32_t pass = 0; pass < t.numTris; pass += kPass) {
@@ -532,7 +581,13 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
                 bool valid = false;
                 if (k < t.numTris && !(p.debugSkip & 8u)) {
                     const WorldTri wt = p.viewTris[t.triBegin + k];
-                    if (PV)
+                    if (NRM && PV)
+                        valid = setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec],
+                                                  NormalOut { nrmLds + rec });
+                    else if (NRM)
+                        valid = setupTriangle(p, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec],
+                                              NormalOut { nrmLds + rec });
+                    else if (PV)
                         valid = setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
                     else
                         valid = setupTriangle(p, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
@@ -571,9 +626,12 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
             // shade this pass's winners before its records are replaced
 #pragma unroll
             for (int b = 0; b < kRegionBlocks; ++b) {
-                if (bid[g][b] >= 0)
+                if (bid[g][b] >= 0) {
                     resolvePixel<IDS>(p, lds.rec, bid[g][b], best[g][b], px[b], py,
                                       outRgba[g][b], outId[g][b]);
+                    if (NRM)
+                        outNrm[g][b] = nrmLds[bid[g][b]];
+                }
                 bid[g][b] = -1;
             }
         }
@@ -584,7 +642,10 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
         const int strip = 2 * wave + (g >> 1), hf = g & 1;
         const uint32_t fy = t.tileY0 + strip * 8 + t.ly;
         const uint32_t fx0 = t.tileX0 + hf * 32 + 4 * t.lx;
-        outputRegion<IDS>(p, t, fx0, fy, invFar, best[g], outRgba[g], outId[g]);
+        if (NRM)
+            outputRegion<IDS, true>(p, t, fx0, fy, invFar, best[g], outRgba[g], outId[g], outNrm[g]);
+        else
+            outputRegion<IDS>(p, t, fx0, fy, invFar, best[g], outRgba[g], outId[g]);
     }
 }
 
@@ -601,6 +662,21 @@ __global__ __launch_bounds__(kWave *kWavesPerBlock, 3)
 void rasterChunkedKernelPV(const RasterParams p)
 {
     chunkedKernelBody<IDS, true>(p);
+}
+
+// the normals forms (p.normal), as the brute kernel's
+template <bool IDS>
+__global__ __launch_bounds__(kWave *kWavesPerBlock, 3)
+void rasterChunkedKernelN(const RasterParams p)
+{
+    chunkedKernelBody<IDS, false, true>(p);
+}
+
+template <bool IDS>
+__global__ __launch_bounds__(kWave *kWavesPerBlock, 3)
+void rasterChunkedKernelNPV(const RasterParams p)
+{
+    chunkedKernelBody<IDS, true, true>(p);
 }
 
 // ---------------------------------------------------------------------------
@@ -654,14 +730,23 @@ constexpr uint32_t kItemAnyTex = 1u << 10;    // a surviving slot of the strip i
 // of the winner's shading record (the background has its own record, so the
 // lookup is unconditional); base pointers are wave-uniform.
 // OUT: output selection (raster.hpp OutSel); doRgb / doDepth = storesRgb / storesDepth of the kernel.
-template <bool IDS, bool FULL, bool TEX, int OUT, typename LDS>
+// NRM: the normals form: the winner's packed normal is one more dword found through the same
+// offset, in the array `nrmTab` parallel to the records (the background's entry included), and one more store.
+template <bool IDS, bool FULL, bool TEX, int OUT, bool NRM = false, typename LDS>
 __device__ __forceinline__ void storeRegion(const RasterParams &p, const LDS &L, bool doRgb, bool doDepth,
                                             uint32_t *rgbTile, float *depthTile, int32_t *idsTile,
                                             uint32_t pixOff, uint32_t fx0, uint32_t fy,
                                             bool anyTex, const float (&px)[kRegionBlocks], float py,
                                             const float (&best)[kRegionBlocks],
-                                            const int32_t (&bid)[kRegionBlocks])
+                                            const int32_t (&bid)[kRegionBlocks],
+                                            const uint32_t *nrmTab = nullptr, uint32_t *nrmTile = nullptr)
 {
+    uint32_t nrm[kRegionBlocks];
+    if (NRM) {
+#pragma unroll
+        for (int b = 0; b < kRegionBlocks; ++b)
+            nrm[b] = *reinterpret_cast<const uint32_t *>(reinterpret_cast<const char *>(nrmTab) + (bid[b] >> 2));
+    }
     uint32_t rgba[kRegionBlocks];
     int32_t id[kRegionBlocks];
     float dep[kRegionBlocks];
@@ -701,6 +786,8 @@ __device__ __forceinline__ void storeRegion(const RasterParams &p, const LDS &L,
                           __float_as_uint(dep[2]), __float_as_uint(dep[3]));
         if (IDS)
             streamStore16(p.writeThrough, idsTile + pixOff, (uint32_t)id[0], (uint32_t)id[1], (uint32_t)id[2], (uint32_t)id[3]);
+        if (NRM)
+            streamStore16(p.writeThrough, nrmTile + pixOff, nrm[0], nrm[1], nrm[2], nrm[3]);
     } else if (fy < p.nslow) {
 #pragma unroll
         for (int b = 0; b < kRegionBlocks; ++b) {
@@ -711,16 +798,18 @@ __device__ __forceinline__ void storeRegion(const RasterParams &p, const LDS &L,
                     streamStore4(p.writeThrough, depthTile + pixOff + b, __float_as_uint(dep[b]));
                 if (IDS)
                     streamStore4(p.writeThrough, idsTile + pixOff + b, (uint32_t)id[b]);
+                if (NRM)
+                    streamStore4(p.writeThrough, nrmTile + pixOff + b, nrm[b]);
             }
         }
     }
 }
 
 // A region no triangle can touch: background everywhere, no per-pixel work.
-template <bool IDS, bool FULL>
+template <bool IDS, bool FULL, bool NRM = false>
 __device__ __forceinline__ void storeBackground(const RasterParams &p, bool doRgb, bool doDepth, uint32_t *rgbTile,
                                                 float *depthTile, int32_t *idsTile,
-                                                uint32_t pixOff, uint32_t fx0, uint32_t fy)
+                                                uint32_t pixOff, uint32_t fx0, uint32_t fy, uint32_t *nrmTile = nullptr)
 {
     if (p.debugSkip & 1u)
         return;
@@ -732,6 +821,9 @@ __device__ __forceinline__ void storeBackground(const RasterParams &p, bool doRg
             streamStore16(p.writeThrough, depthTile + pixOff, 0u, 0u, 0u, 0u);
         if (IDS)
             streamStore16(p.writeThrough, idsTile + pixOff, ~0u, ~0u, ~0u, ~0u);
+        if (NRM)
+            streamStore16(p.writeThrough, nrmTile + pixOff, kNormalBackground, kNormalBackground, kNormalBackground,
+                          kNormalBackground);
     } else if (fy < p.nslow) {
 #pragma unroll
         for (int b = 0; b < kRegionBlocks; ++b) {
@@ -742,6 +834,8 @@ __device__ __forceinline__ void storeBackground(const RasterParams &p, bool doRg
                     streamStore4(p.writeThrough, depthTile + pixOff + b, 0u);
                 if (IDS)
                     streamStore4(p.writeThrough, idsTile + pixOff + b, ~0u);
+                if (NRM)
+                    streamStore4(p.writeThrough, nrmTile + pixOff + b, kNormalBackground);
             }
         }
     }
@@ -801,14 +895,20 @@ constexpr int groupWaves(bool tex) { return tex ? 4 : 8; }
 // COL: per-instance colour override: the set-up lanes read their row's packed colour beside its ObjectID.
 // MAT (with COL): per-instance material override: they read the row's material id too; the colour
 // column is then the slot of the pose block -- zero-filled in a renderer that has the material column alone.
+// NRM: the normals form (instantiated with COL and MAT, output selection by pointer and XMODE 0):
+// the set-up lanes pack their triangle's normal into an LDS array parallel to the shading records, phase R + O stores
+// one more tensor.  The colour and material columns are read behind null tests, and the XCD trade and report are
+// run-time tests of p.xcdPhase / p.xccReport here, so that two forms (uniform constants, per-view tables) cover
+// every renderer with the output.
 template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT, bool PV = false, bool LT = false, bool COL = false,
-          bool MAT = false>
+          bool MAT = false, bool NRM = false>
 __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances,
                                                 uint32_t hPool, uint32_t hShape, uint32_t hGroups, uint32_t hPrefix,
                                                 uint32_t hFirst01, uint32_t hFirst23, const RasterParams p)
 {
     __shared__ GroupLds<SLOTS, PV> lds;
     constexpr int kBackground = GroupLds<SLOTS, PV>::kBackground;
+    __shared__ uint32_t nrmLds[NRM ? GroupLds<SLOTS, PV>::kRecs + 1 : 1];   // [record], the background's last
     // readfirstlane: the compiler cannot see that threadIdx.x / 64 is
     // wave-uniform and would predicate every `wave` branch instead of jumping
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
@@ -831,11 +931,14 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     const float *aCamRot = FAST ? reinterpret_cast<const float *>(hPose + lay.camRot) : p.camRot;
     const float *aCamPos = FAST ? reinterpret_cast<const float *>(hPose + lay.camPos) : p.camPos;
     const int32_t *aInstObj = FAST ? reinterpret_cast<const int32_t *>(hPose + lay.instObj) : p.instObj;
-    const uint32_t *aInstColor = FAST ? reinterpret_cast<const uint32_t *>(hPose + lay.total)
+    // (NRM: whichever columns the renderer has -- null without)
+    const uint32_t *aInstColor = NRM ? p.instColor
+                                 : FAST ? reinterpret_cast<const uint32_t *>(hPose + lay.total)
                                  : MAT ? reinterpret_cast<const uint32_t *>(p.poseBlock + poseColorOffset(p.numViews, p.numInstances))
                                        : p.instColor;
-    const int32_t *aInstMat = FAST ? reinterpret_cast<const int32_t *>(hPose + lay.total + mrxAlign256(hInstances * 4u))
-                                   : p.instMat;
+    const int32_t *aInstMat = NRM ? p.instMat
+                              : FAST ? reinterpret_cast<const int32_t *>(hPose + lay.total + mrxAlign256(hInstances * 4u))
+                                     : p.instMat;
     const uint32_t tilesPerView = FAST ? 1u : p.tilesFast * p.tilesSlow;
     // FAST, untextured (16 slots, one-tile views): S2 hands phase R ready-made work items (GroupLds::items).
     // The plain entry and the textured kernels keep the per-tile masks: measured slower with the items
@@ -857,11 +960,11 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     // picks the instantiation by the parity workgroup 0 reported in an earlier launch
     // of this renderer -- every workgroup of a launch runs the same code, so the trade
     // is consistent whatever the hardware does; a stale value costs speed, never pixels.
-    const uint32_t blk = ((XMODE & 1) && SLOTS == 16 && aXcdSkew && (blockIdx.x ^ 1u) < aGrid)
+    const uint32_t blk = ((NRM ? (p.xcdPhase & 1u) != 0u : (XMODE & 1) != 0) && SLOTS == 16 && aXcdSkew && (blockIdx.x ^ 1u) < aGrid)
                              ? blockIdx.x ^ 1u : blockIdx.x;
     // workgroup 0 reports where it runs: a host-mapped word, written by the last wave,
     // which issues no loads during set-up -- the slow write sits ahead of nothing
-    if ((XMODE & 2) && blockIdx.x == 0 && threadIdx.x == (groupWaves(TEX) - 1) * kWave && p.xccReport)
+    if (((XMODE & 2) || (NRM && SLOTS == 16)) && blockIdx.x == 0 && threadIdx.x == (groupWaves(TEX) - 1) * kWave && p.xccReport)
         *p.xccReport = __builtin_amdgcn_s_getreg((3 << 11) | 20);   // HW_REG_XCC_ID[3:0]
     uint32_t bid = blk;
     if (aXcdRotate && (bid | 7u) < aGrid)
@@ -1025,10 +1128,18 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                     pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse, p.transposed };
                 InstXform x;
                 instanceTransform(sa, vc, wt.inst, x);
+                if (NRM) {
+                    const MatOverride mo = { aInstMat ? aInstMat[wt.inst] : -1, p.numMaterials, p.matTable };
+                    valid = setupTriangleCore<true, true, true, true>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
+                                                                      lds.shade[rec], lds.cold[rec],
+                                                                      aInstColor ? aInstColor[wt.inst] : 0u, mo,
+                                                                      NormalOut { nrmLds + rec });
+                } else {
                 const MatOverride mo = { MAT ? aInstMat[wt.inst] : -1, p.numMaterials, p.matTable };
                 valid = setupTriangleCore<true, OUT != kOutDepth, COL, MAT>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
                                                                             lds.shade[rec], lds.cold[rec],
                                                                             COL ? aInstColor[wt.inst] : 0u, mo);
+                }
             }
             MRX_STAMP(2);
             float4 *dst = reinterpret_cast<float4 *>(lds.planes[rec]);
@@ -1044,6 +1155,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             lds.shade[kBackground][1] = __int_as_float(-1);
             lds.shade[kBackground][2] = __int_as_float(-1);
             lds.shade[kBackground][3] = __int_as_float(-1);
+            if (NRM)
+                nrmLds[kBackground] = kNormalBackground;
         }
     }
     __syncthreads();
@@ -1116,6 +1229,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     uint32_t *rgbTile = nullptr;
     float *depthTile = nullptr;
     int32_t *idsTile = nullptr;
+    uint32_t *nrmTile = nullptr;
     const bool doRgb = storesRgb<OUT>(p.rgb), doDepth = storesDepth<OUT>(p.depth);
     uint32_t itemMasks = 0;     // readyItems: the item's surviving slots, left half bits 0..15, right half 16..31
     float tileNear = invNear;   // 1/znear of the item's view (PV: from LDS, tile by tile)
@@ -1154,6 +1268,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             rgbTile = p.rgb + tileBase;
             depthTile = p.depth + tileBase;
             idsTile = IDS ? p.ids + tileBase : nullptr;
+            nrmTile = NRM ? p.normal + tileBase : nullptr;
         } else {
             item = __builtin_amdgcn_readfirstlane((uint32_t)lds.itemOrder[item]);
             j = (int)(item >> 3);
@@ -1173,6 +1288,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                 rgbTile = p.rgb + tileBase;
                 depthTile = p.depth + tileBase;
                 idsTile = IDS ? p.ids + tileBase : nullptr;
+                nrmTile = NRM ? p.normal + tileBase : nullptr;
                 full = (p.nfast & 3u) == 0 && tileX0 + 64u <= p.nfast && tileY0 + 64u <= p.nslow;
                 // lane k looks at the region masks of triangle slots k, 64 + k, ... of tile j
                 anyTex = false;
@@ -1212,9 +1328,9 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             }
             if (!any) {
                 if (full)
-                    storeBackground<IDS, true>(p, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy);
+                    storeBackground<IDS, true, NRM>(p, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy, nrmTile);
                 else
-                    storeBackground<IDS, false>(p, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy);
+                    storeBackground<IDS, false, NRM>(p, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy, nrmTile);
                 continue;
             }
             const float (&px)[kRegionBlocks] = pxTile[hf];
@@ -1237,11 +1353,11 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                 }
             }
             if (full)
-                storeRegion<IDS, true, TEX, OUT>(p, lds, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy,
-                                            anyTex, px, py, best, bid);
+                storeRegion<IDS, true, TEX, OUT, NRM>(p, lds, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy,
+                                                      anyTex, px, py, best, bid, nrmLds, nrmTile);
             else
-                storeRegion<IDS, false, TEX, OUT>(p, lds, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy,
-                                             anyTex, px, py, best, bid);
+                storeRegion<IDS, false, TEX, OUT, NRM>(p, lds, doRgb, doDepth, rgbTile, depthTile, idsTile, pixOff, fx0, fy,
+                                                       anyTex, px, py, best, bid, nrmLds, nrmTile);
         }
     }
     MRX_STAMP(5);
@@ -1397,6 +1513,49 @@ void rasterGroupKernelFastPVLM(const char *hPose, const char *hGeom, uint32_t hV
                                                                                  hGroups, hPrefix, hFirst01, hFirst23, p);
 }
 
+// The normals forms (p.normal), instantiations of their own so that a renderer without the output
+// launches what it always did: N over the uniform projection and light of the kernel arguments, NPV over both tables;
+// the colour and material columns behind null tests, output selection by pointer.  The per-view form keeps the six
+// waves per SIMD of the other forms over the light table; the uniform form has six from 128 slots on -- held to the 64
+// registers of eight waves, its 128-slot instantiation with ids spilled 22 of them to scratch.
+template <bool IDS, int SLOTS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : (SLOTS >= 128 ? 6 : 8))
+void rasterGroupKernelN(const RasterParams p)
+{
+    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, false, false, true, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u,
+                                                                                             0u, 0u, 0u, p);
+}
+
+template <bool IDS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 8)
+void rasterGroupKernelFastN(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
+                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
+                            const RasterParams p)
+{
+    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, false, false, true, true, true>(hPose, hGeom, hViews, hInstances, hPool,
+                                                                                         hShape, hGroups, hPrefix, hFirst01,
+                                                                                         hFirst23, p);
+}
+
+template <bool IDS, int SLOTS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : 6)
+void rasterGroupKernelNPV(const RasterParams p)
+{
+    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, true, true, true, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u,
+                                                                                           0u, 0u, 0u, p);
+}
+
+template <bool IDS, bool TEX>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 6)
+void rasterGroupKernelFastNPV(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
+                              uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
+                              const RasterParams p)
+{
+    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, true, true, true, true, true>(hPose, hGeom, hViews, hInstances, hPool,
+                                                                                       hShape, hGroups, hPrefix, hFirst01,
+                                                                                       hFirst23, p);
+}
+
 }  // namespace
 
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
@@ -1426,7 +1585,19 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
         }                                                                                \
     } while (0)
         const OutSel out = outSelOf(p.rgb, p.depth);
-        if (pv) {
+#define MRX_BRUTE_FORM(K)                                                                \
+    do {                                                                                 \
+        if (ids) {                                                                       \
+            if (multi) K<true, true><<<grid, block, 0, stream>>>(p);                      \
+            else       K<true, false><<<grid, block, 0, stream>>>(p);                     \
+        } else {                                                                         \
+            if (multi) K<false, true><<<grid, block, 0, stream>>>(p);                     \
+            else       K<false, false><<<grid, block, 0, stream>>>(p);                    \
+        }                                                                                \
+    } while (0)
+        if (p.normal && pv) MRX_BRUTE_FORM(rasterBruteKernelNPV);
+        else if (p.normal)  MRX_BRUTE_FORM(rasterBruteKernelN);
+        else if (pv) {
             if (ids) {
                 if (multi) rasterBruteKernelPV<true, true><<<grid, block, 0, stream>>>(p);
                 else       rasterBruteKernelPV<true, false><<<grid, block, 0, stream>>>(p);
@@ -1439,10 +1610,17 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
         else if (out == kOutRGB) MRX_BRUTE(kOutRGB);
         else                     MRX_BRUTE(kOutRGBD);
 #undef MRX_BRUTE
+#undef MRX_BRUTE_FORM
     } else if (large) {
         // more triangles per world than the group kernel holds: one workgroup per tile
         if (entry) *entry = kEntryChunked;
-        if (pv) {
+        if (p.normal && pv) {
+            if (ids) rasterChunkedKernelNPV<true><<<dim3(items), block, 0, stream>>>(p);
+            else     rasterChunkedKernelNPV<false><<<dim3(items), block, 0, stream>>>(p);
+        } else if (p.normal) {
+            if (ids) rasterChunkedKernelN<true><<<dim3(items), block, 0, stream>>>(p);
+            else     rasterChunkedKernelN<false><<<dim3(items), block, 0, stream>>>(p);
+        } else if (pv) {
             if (ids) rasterChunkedKernelPV<true><<<dim3(items), block, 0, stream>>>(p);
             else     rasterChunkedKernelPV<false><<<dim3(items), block, 0, stream>>>(p);
         } else {
@@ -1557,7 +1735,11 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
     } while (0)
 #define MRX_GROUP_O(S, X, O, OP)                                               \
     do {                                                                       \
-        if (p.instMat && pv && p.tablesVary) {                                 \
+        if (p.normal && pv && p.tablesVary) {                                  \
+            MRX_GROUP_FORM(S, rasterGroupKernelFastNPV, rasterGroupKernelNPV); \
+        } else if (p.normal) {                                                 \
+            MRX_GROUP_FORM(S, rasterGroupKernelFastN, rasterGroupKernelN);     \
+        } else if (p.instMat && pv && p.tablesVary) {                          \
             MRX_GROUP_FORM(S, rasterGroupKernelFastPVLM, rasterGroupKernelPVLM);                          \
         } else if (p.instMat) {                                                \
             MRX_GROUP_FORM(S, rasterGroupKernelFastM, rasterGroupKernelM);     \

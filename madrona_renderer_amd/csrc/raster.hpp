@@ -220,6 +220,10 @@ struct RasterParams {
     // [numMaterials + 1] records of the renderer's material table (the last one a spare nothing may select)
     const MatRec *matTable;
     uint32_t numMaterials;
+    // Surface-normal output: [view][slow][fast] packed view-space normals, storage as rgb's;
+    // null = not rendered (no MRX_FLAG_NORMALS): the launchers then pick the kernels they always did, none of
+    // which reads this member -- the last of the block.
+    uint32_t *normal;
 };
 
 // ---- the argument header of the group kernel's fast prologue (raster.hip, FAST) -------------------------------------

@@ -141,22 +141,51 @@ __device__ __forceinline__ void instanceTransform(const PARAMS &p, const ViewCon
 // PARAMS: RasterParams, or any struct with the members read here (tris, triMats, s6bPad, sx, sz,
 // ox, oz, transposed, diffuse, ambient) -- the BVH kernel passes a copy it reads from the
 // kernel-argument segment batch by batch instead of holding the values in scalar registers.
+// NRMOUT: where the packed view-space normal of the triangle goes -- NormalOut, one dword
+// written where the colour work begins (under COLOR = false too: depth + normals), from the n, d and len S7 uses;
+// NoNormalOut (the default): nothing is computed, the function is what it always was.
+struct NoNormalOut {
+    static constexpr bool kOn = false;
+    __device__ __forceinline__ void put(uint32_t) const {}
+};
+struct NormalOut {
+    static constexpr bool kOn = true;
+    uint32_t *dst;
+    __device__ __forceinline__ void put(uint32_t v) const { *dst = v; }
+};
+constexpr uint32_t kNormalBackground = 0x00808080u;   // (128, 128, 128, 0): the zero vector, alpha 0 = a miss
+// S10: the unit normal turned towards the eye, one byte per axis: (uint) fma(clamp(c, -1, 1), 127, 128.5)
+__device__ __forceinline__ uint32_t packNormal(const float (&nn)[3], float d, float len)
+{
+    uint32_t b[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        float c = len > 0.0f ? nn[i] / len : 0.0f;
+        if (d > 0.0f)
+            c = -c;
+        b[i] = (uint32_t)__builtin_fmaf(fminf(fmaxf(c, -1.0f), 1.0f), 127.0f, 128.5f);
+    }
+    return b[0] | (b[1] << 8) | (b[2] << 16) | 0xFF000000u;
+}
 struct MatOverride {
     int32_t id;
     uint32_t count;           // materials of the table
     const MatRec *table;
+    // the row's colour override where the callable fetches it too (the BVH tile kernel's normals form: one register
+    // less through the plane arithmetic); OR-ed into `icol`, 0 everywhere else
+    uint32_t icol = 0u;
     __device__ __forceinline__ MatOverride operator()() const { return *this; }
 };
 struct NoMatOverride {
     __device__ __forceinline__ MatOverride operator()() const { return MatOverride { -1, 0u, nullptr }; }
 };
 template <bool UVPLANES = true, bool COLOR = true, bool ICOL = false, bool IMAT = false, typename PARAMS = RasterParams,
-          typename MATFN = NoMatOverride>
+          typename MATFN = NoMatOverride, typename NRMOUT = NoNormalOut>
 __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (&lv)[3],
                                                   const InstXform &x, uint32_t tri, int32_t obj,
                                                   int32_t kWorld, TriPlanes &out,
                                                   float *shade, float *cold, uint32_t icol = 0u,
-                                                  const MATFN matOf = MATFN())
+                                                  const MATFN matOf = MATFN(), const NRMOUT nrm = NRMOUT())
 {
     const float (&MV)[3][3] = x.MV;
     const float (&tv)[3] = x.tv;
@@ -263,6 +292,8 @@ __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (
         out.Dc = __builtin_fmaf(nn[2], p.oz, __builtin_fmaf(nn[0], p.ox, nn[1])) * rd;
     }
     if (!COLOR) {
+        if (NRMOUT::kOn)
+            nrm.put(packNormal(nn, d, sqrtf(dot3(nn[0], nn[1], nn[2], nn[0], nn[1], nn[2]))));
         shade[1] = __int_as_float(tex);
         shade[2] = obj >= 0 ? mc.w : __int_as_float(obj);
         shade[3] = __int_as_float(kWorld);
@@ -275,6 +306,8 @@ __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (
             mc.x = m.x; mc.y = m.y; mc.z = m.z;
             tex = __float_as_int(m.w);
         }
+        if (ICOL)
+            icol |= mo.icol;
     }
     // u/v planes (S8) are only ever read for textured triangles
     if (!UVPLANES) {
@@ -308,6 +341,10 @@ __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (
     shade[1] = __int_as_float(tex);
     shade[2] = obj >= 0 ? mc.w : __int_as_float(obj);   // the triangle's own object id (TriMat alpha slot)
     shade[3] = __int_as_float(kWorld);
+    // S10, last: the light, the material and the colour are out of the way (the BVH tile kernel has no register to
+    // hold them beside the three quotients)
+    if (NRMOUT::kOn)
+        nrm.put(packNormal(nn, d, len));
     return valid;
 }
 
@@ -325,14 +362,15 @@ __device__ __forceinline__ void uvPlanes(const TriPlanes &c, float rad, const fl
 }
 
 // The same for a draw-list entry: transform of the instance, then the triangle.
+template <typename NRMOUT = NoNormalOut>
 __device__ __forceinline__ bool setupTriangle(const RasterParams &p,
                                               const ViewConst &vc,
                                               WorldTri wt, int32_t kWorld,
-                                              TriPlanes &out, float *shade, float *cold)
+                                              TriPlanes &out, float *shade, float *cold, const NRMOUT nrm = NRMOUT())
 {
     InstXform x;
     instanceTransform(p, vc, wt.inst, x);
-    return setupTriangleCore(p, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold);
+    return setupTriangleCore(p, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold, 0u, NoMatOverride(), nrm);
 }
 
 // The projection constants of a view: its record of the per-view table when `perView`, else
@@ -399,7 +437,7 @@ __device__ __forceinline__ uint32_t shadeTextured(const RasterParams &p,
     return r | (g << 8) | (b << 16) | 0xFF000000u;
 }
 
-// The kernel-argument block (RasterParams by value, 408 bytes + the hidden arguments: seven 64-byte lines) is a
+// The kernel-argument block (RasterParams by value, 416 bytes + the hidden arguments: seven 64-byte lines) is a
 // fresh copy for every launch, so every CU's first read of each of its lines misses the scalar cache -- and the
 // compiler reads the arguments lazily, a few at a time, where the control flow first needs them: four or five
 // s_load + s_waitcnt rounds in a row ahead of a kernel's first pose load, each a miss on a line not touched before.

@@ -54,6 +54,8 @@ class SceneDesc:
     # then the ones of MTL files); an id outside it (-1) leaves the row its own materials.  None = no column; True = a
     # column of -1 (written later through instance_material_tensor()).  Worlds that alias rows share their ids.
     instance_materials: object = None
+    # the surface-normal output (normal_tensor()): view-space normals of the winning triangles, RGBA8-encoded
+    normals: bool = False
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -279,6 +281,8 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
             if mats.shape != (len(desc.instances),):
                 raise ValueError("instance_materials needs one material id per instance")
             extra["instance_materials"] = mats
+    if desc.normals:
+        extra["normals"] = True
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:

@@ -2,7 +2,10 @@
 """Kernel time of each output selection (RGBD, Depth, RGB: Manager::RenderOutputs) on the shapes
 that matter, one JSON line per (configuration, setting):
 
-  python scripts/bench_outputs.py [--rounds 5] [--budget-ms 30] [--only headline,c2,...]
+  python scripts/bench_outputs.py [--rounds 5] [--budget-ms 30] [--only headline,c2,...] [--normals]
+
+--normals times RGBD+N, Depth+N and RGB+N (the surface-normal output beside each selection) beside the
+three settings, in the same alternation; without it the script does what it always did.
 
 Every renderer of a configuration is created and warmed first; then the settings alternate within
 the process, `rounds` times, each measurement a batch of back-to-back renders between two events
@@ -23,6 +26,7 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBPS = 8000.0
 SETTINGS = ("RGBD", "Depth", "RGB")
+NORMAL_SETTINGS = ("RGBD+N", "Depth+N", "RGB+N")
 
 
 def configs(scenes):
@@ -43,7 +47,11 @@ def make(scenes, factory, setting, variant):
     if variant is not None:
         os.environ["MADRONA_MI355_KERNEL"] = str(variant)
     try:
-        return scenes.make_renderer(factory(), render_outputs=setting)
+        desc = factory()
+        if setting.endswith("+N"):
+            desc.normals = True
+            setting = setting[:-2]
+        return scenes.make_renderer(desc, render_outputs=setting)
     finally:
         os.environ.pop("MADRONA_MI355_KERNEL", None)
 
@@ -57,15 +65,17 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--budget-ms", type=float, default=30.0, help="device time of one measurement")
     ap.add_argument("--only", default="", help="comma-separated configuration keys")
+    ap.add_argument("--normals", action="store_true", help="also time each setting with the surface-normal output")
     a = ap.parse_args(argv)
     if a.rounds < 3:
         ap.error("--rounds must be at least 3")
     from madrona_renderer_amd import scenes
     only = set(filter(None, a.only.split(",")))
+    settings = SETTINGS + (NORMAL_SETTINGS if a.normals else ())
     for key, label, factory, variant in configs(scenes):
         if only and key not in only:
             continue
-        rs = {s: make(scenes, factory, s, variant) for s in SETTINGS}
+        rs = {s: make(scenes, factory, s, variant) for s in settings}
         views = factory().num_views
         # warm every shape: clocks up, first launches (XCC report, cold caches) out of the way
         steps = {}
@@ -74,12 +84,12 @@ def main(argv=None):
             while time.perf_counter() - t0 < 0.2:
                 est = us_per_render(r, 20)
             steps[s] = max(10, min(5000, int(a.budget_ms * 1000.0 / max(est, 1.0))))
-        times = {s: [] for s in SETTINGS}
+        times = {s: [] for s in settings}
         for _ in range(a.rounds):
-            for s in SETTINGS:
+            for s in settings:
                 times[s].append(us_per_render(rs[s], steps[s]))
         base = statistics.median(times["RGBD"])
-        for s in SETTINGS:
+        for s in settings:
             med = statistics.median(times[s])
             b = int(rs[s].bytes_per_step())
             print(json.dumps({
