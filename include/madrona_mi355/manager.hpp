@@ -104,7 +104,16 @@ public:
         // Surface-normal output (MRX_FLAG_NORMALS): normalTensor() holds the view-space normal of every pixel's
         // winning triangle, RGBA8-encoded; combines with every renderOutputs setting.
         bool normals = false;
+        // Per-instance labels (MRX_FLAG_INSTANCE_LABELS): [numInstances] int32 labels parallel to
+        // rcfg.importedInstances, the initial values of instanceLabelTensor(); kLabelObject = the id of the row's bound
+        // object.  Expanded per world as the poses are: worlds that alias rows share labels, spare rows get
+        // kLabelObject.  nullptr with instanceLabelColumn: a column of kLabelObject; nullptr without: none.  With the
+        // column segmaskTensor() exists in Rasterizer mode too and holds the label of the row that wins each pixel.
+        const int32_t *instanceLabels = nullptr;
+        bool instanceLabelColumn = false;
     };
+    // the label that stands for the id of the object a row is bound to (MRX_LABEL_OBJECT)
+    static constexpr int32_t kLabelObject = INT32_MIN;
 
     // Aborts (FATAL-style, like the reference) when construction fails.
     Manager(const Config &cfg);
@@ -146,6 +155,9 @@ public:
     // pixel's winning triangle turned towards the eye, byte = 128 + 127 * component, alpha 255; background
     // (128, 128, 128, 0).  Needs Config::normals.
     madrona::py::Tensor normalTensor(uint32_t shard = 0) const;
+    // i32 [instances], mutable: the label of every row, kLabelObject = the id of its bound object; what segmaskTensor()
+    // holds on the pixels the row wins (needs Config::instanceLabels or instanceLabelColumn)
+    madrona::py::Tensor instanceLabelTensor(uint32_t shard = 0) const;
     // binds every row to the (non-negative) object id its ObjectID column now holds: a spare
     // row gets its geometry, an existing row swaps it (makeEntityRenderable at run time,
     // src/sim.inl:5-8); waits for the device
@@ -183,6 +195,10 @@ public:
     bool setInstanceMaterials(uint32_t first, uint32_t count, const int32_t *materials);
     void instanceMaterials(uint32_t first, uint32_t count, int32_t *out) const;
     uint32_t numInstanceRows() const;
+    // per-instance labels, as the material override above: stream-ordered write of rows [first, first + count) from
+    // host memory, and the read-back
+    bool setInstanceLabels(uint32_t first, uint32_t count, const int32_t *labels);
+    void instanceLabels(uint32_t first, uint32_t count, int32_t *out) const;
 
     uint32_t numAgents;
 

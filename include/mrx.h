@@ -132,8 +132,19 @@ enum {
      * (normals + depth) and with MRX_FLAG_NO_DEPTH (normals + rgb).  Without it nothing is allocated, mrx_buffer /
      * mrx_buffer_shard / mrx_copy_to_host on the tensor fail with MRX_E_UNSUPPORTED and every launch is the one it
      * always was. */
-    MRX_FLAG_NORMALS = 1u << 6
+    MRX_FLAG_NORMALS = 1u << 6,
+    /* per-instance labels: allocates the MRX_BUF_INSTANCE_LABEL column, filled with MRX_LABEL_OBJECT, and the ids
+     * tensor in Rasterizer mode too, and selects the launch forms that read the column:
+     * MRX_BUF_SEGMASK then holds, in both modes, the label of the instance row that wins each pixel.  Labels change
+     * that tensor only.  Without the flag nothing is allocated, mrx_buffer / mrx_buffer_shard / mrx_copy_to_host on the
+     * column fail with MRX_E_UNSUPPORTED, Rasterizer-mode MRX_BUF_SEGMASK fails as it always did and every launch is
+     * the one it always was.  Together with MRX_FLAG_VISIBILITY_IDS the one ids tensor holds visibility ids:
+     * the column exists and is mutable, MRX_BUF_SEGMASK is refused. */
+    MRX_FLAG_INSTANCE_LABELS = 1u << 7
 };
+
+/* the label that stands for "the id of the object the row is bound to" (INT32_MIN): what the column starts at */
+#define MRX_LABEL_OBJECT ((int32_t)(-2147483647 - 1))
 
 /* Manager::Config + Config::RenderConfig, /root/reference/src/mgr.hpp:49-88.
  * All pointers are borrowed for the duration of mrx_create() only. */
@@ -212,7 +223,8 @@ typedef struct mrx_renderer mrx_renderer;
 enum {
     MRX_BUF_RGB = 0,            /* u8  [views,H,W,4]  (Raytracer: [views,res,res,4]) */
     MRX_BUF_DEPTH = 1,          /* f32 [views,H,W,1]  (Raytracer: [views,res,res])   */
-    MRX_BUF_SEGMASK = 2,        /* i32 [views,res,res], Raytracer only               */
+    MRX_BUF_SEGMASK = 2,        /* i32 [views,res,res], Raytracer only -- with MRX_FLAG_INSTANCE_LABELS in Rasterizer
+                                 * mode too, [views,H,W]: per pixel the label of the winning row, -1 = background */
     MRX_BUF_INSTANCE_POSITION = 3, /* f32 [instances,3]                              */
     MRX_BUF_INSTANCE_ROTATION = 4, /* f32 [instances,4]  w,x,y,z                     */
     MRX_BUF_CAMERA_POSITION = 5,   /* f32 [cameras,3]                                */
@@ -256,7 +268,17 @@ enum {
      * vector, alpha 0 marks the miss.  Independent of winding, mirroring scales, light, material, colour override and
      * texture.  One tensor per shard, like rgb. */
     MRX_BUF_NORMAL = 12,
-    MRX_NUM_BUFFERS_EXT2 = 13
+    MRX_NUM_BUFFERS_EXT2 = 13,
+    /* i32 [instances], mutable, needs MRX_FLAG_INSTANCE_LABELS: the label of every row.  On the pixels
+     * a row's triangles win, the segmask holds the row's label -- any int32, stored as it is, -1 and other negatives
+     * included -- except MRX_LABEL_OBJECT (INT32_MIN), which stands for the id of the object the row is bound to: the
+     * segmask value of a renderer without the column.  Background pixels hold -1.  It changes the ids tensor only --
+     * never which kernel family renders, visibility, depth, rgb or normals -- and belongs to the row: it stays through
+     * hiding and through mrx_refresh_objects() (a row at MRX_LABEL_OBJECT follows whatever object it is bound to);
+     * spare rows start at MRX_LABEL_OBJECT.  Written on the device, like a pose, on the renderer's stream; read under
+     * every output selection, a depth-only renderer included. */
+    MRX_BUF_INSTANCE_LABEL = 13,
+    MRX_NUM_BUFFERS_EXT3 = 14
 };
 
 enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2 };
@@ -489,6 +511,15 @@ int mrx_light_constants(mrx_light light, float out[5]);
  *    column back (it waits for the stream). */
 int mrx_set_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, const int32_t *materials);
 int mrx_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, int32_t *out);
+
+/* -- per-instance labels (MRX_FLAG_INSTANCE_LABELS).  Rows are the rows of MRX_BUF_INSTANCE_LABEL over the whole job,
+ *    as above.  mrx_set_instance_labels writes rows [first_row, first_row + count) and is stream-ordered as
+ *    mrx_set_instance_materials is: renders enqueued before it keep the old labels, the next render has the new ones.
+ *    Any int32 is accepted; MRX_LABEL_OBJECT gives a row the id of its bound object back.  MRX_E_INVALID: a null
+ *    pointer or rows outside the renderer; MRX_E_UNSUPPORTED: no column.  mrx_instance_labels reads the column back
+ *    (it waits for the stream). */
+int mrx_set_instance_labels(mrx_renderer *r, uint32_t first_row, uint32_t count, const int32_t *labels);
+int mrx_instance_labels(mrx_renderer *r, uint32_t first_row, uint32_t count, int32_t *out);
 
 int mrx_device_count(void);
 int mrx_abi_version(void);

@@ -1078,6 +1078,24 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     } else {
                         valid = setupTriangleCore<false, true, PV>(sa, lv, x, e.y, objL, (int32_t)kTri, c, shade, cold, icol);
                     }
+                    // (S11, DESIGN.md 4.16 -- the per-view segmask instantiations: the label of the triangle's row into the
+                    // record's label slot, fetched here, behind the plane arithmetic, as the material override is; a
+                    // renderer without the column reads the ObjectID column behind scalar selects and keeps the slot)
+                    if (PV && IDS == 2) {
+                        KernargParams pl = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
+                        asm volatile("" : "+s"(pl));
+                        uint32_t rowBase = passBase;
+                        if (MULTI) {
+                            const uint32_t uni = pl->bvhUniInst, cams = pl->bvhUniCams;
+                            if (uni)
+                                rowBase = (cams != 1u ? view / cams : view) * uni;
+                            else
+                                rowBase = pl->worldInstStart[pl->viewWorld[view]];
+                        }
+                        const int32_t *labels = pl->instLabel;
+                        const int32_t lab = (labels ? labels : pl->instObj)[rowBase + ws->queue[lane].x];
+                        shade[2] = (labels && lab != kLabelObject) ? __int_as_float(lab) : shade[2];
+                    }
                     live = valid && c.bbX1 >= TX0 && c.bbX0 <= TX1 && c.bbY1 >= TY0 && c.bbY0 <= TY1;
                     // The planes at the tile's corners: fl(A x + fl(B y + C)) is monotone in x and in
                     // y, so its extreme over the tile's pixels is taken at a corner pixel, and a
@@ -1734,6 +1752,9 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
             } else {
                 valid = setupTriangleCore<false, OUT != kOutDepth>(p, vc.lv, y, myTri, objL, (int32_t)lane, c, shade, cold);
             }
+            // (S11, DESIGN.md 4.16: the per-view segmask instantiations, a renderer with the label column)
+            if (PV && IDS == 2)
+                applyLabel(shade, p.instLabel, myRow);
             if (TEX && NRM)
                 nrmTab[lane + 1] = nrmv;
             const bool texRec = OUT != kOutDepth && valid && __float_as_int(shade[1]) >= 0;

@@ -10,6 +10,8 @@
 //                     [--instance-colors SEED]   (an opaque colour override per instance row, splitmix64(SEED, row))
 //                     [--instance-materials SEED]   (a material override per instance row, rows 1::4 left without)
 //                     [--normals]   (the surface-normal output; --dump-last-frame also writes NAME.normals.png)
+//                     [--instance-labels SEED]   (a label per instance row, rows 1::4 left at their object's id;
+//                                                 --dump-last-frame also writes NAME.labels.png)
 //
 // --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
 // renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
@@ -74,6 +76,10 @@ struct Args {
     uint64_t materialSeed = 0;
     // --normals: render the surface-normal output too; --dump-last-frame then also writes NAME.normals.png
     bool normals = false;
+    // --instance-labels SEED: every instance row but rows 1::4 labelled 1000 + a draw from the seed and the row;
+    // --dump-last-frame then also writes NAME.labels.png
+    bool hasLabels = false;
+    uint64_t labelSeed = 0;
 };
 
 // a number of the whole argument, finite
@@ -92,7 +98,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -172,6 +178,16 @@ Args parse(int argc, char **argv)
                 std::exit(EXIT_FAILURE);
             }
             a.hasMaterials = true;
+        } else if (!std::strcmp(argv[i], "--instance-labels") && i + 1 < argc) {
+            const char *s = argv[++i];
+            char *end = nullptr;
+            errno = 0;
+            a.labelSeed = std::strtoull(s, &end, 0);
+            if (!*s || *s == '-' || *s == '+' || *end || errno != 0) {
+                std::fprintf(stderr, "--instance-labels: not an unsigned integer seed: %s\n", s);
+                std::exit(EXIT_FAILURE);
+            }
+            a.hasLabels = true;
         } else if (!std::strcmp(argv[i], "--znear") && i + 1 < argc) {
             a.znear = parseFloat("--znear", argv[++i]);
             if (!(a.znear > 0.0f)) {
@@ -322,14 +338,17 @@ void buildDemo(Scene &s, uint32_t n, const std::string &dataDir)
 // DumpWhat::InvDepth (a depth-only renderer's default): grey 255 * dmin / d, dmin = the
 // nearest depth of the frame, 0 for background.
 // DumpWhat::Normal: the surface-normal tensor, in rgb's format (its bytes as they are, alpha included).
-enum class DumpWhat { Rgb, Depth, InvDepth, Normal };
+// DumpWhat::Labels: the segmask of a renderer with the label column: the low 24 bits of each pixel's label as
+// (r, g, b), r lowest, alpha 255; background pixels (-1) are (0, 0, 0, 0).
+enum class DumpWhat { Rgb, Depth, InvDepth, Normal, Labels };
 bool dumpTiled(const std::string &name, mrx_renderer *shard, uint32_t numImages, uint32_t resX,
                uint32_t resY, DumpWhat what, bool transpose)
 {
-    const bool depth = what != DumpWhat::Rgb && what != DumpWhat::Normal;
+    const bool depth = what != DumpWhat::Rgb && what != DumpWhat::Normal && what != DumpWhat::Labels;
     const size_t bytesPerImage = (size_t)4 * resX * resY;
     std::vector<uint8_t> host(bytesPerImage * numImages);
-    if (mrx_copy_to_host(shard, depth ? MRX_BUF_DEPTH : what == DumpWhat::Normal ? MRX_BUF_NORMAL : MRX_BUF_RGB,
+    if (mrx_copy_to_host(shard, depth ? MRX_BUF_DEPTH : what == DumpWhat::Normal ? MRX_BUF_NORMAL
+                                : what == DumpWhat::Labels ? MRX_BUF_SEGMASK : MRX_BUF_RGB,
                          host.data(), host.size()) != MRX_OK) {
         std::fprintf(stderr, "%s\n", mrx_last_error());
         return false;
@@ -361,6 +380,11 @@ bool dumpTiled(const std::string &name, mrx_renderer *shard, uint32_t numImages,
                                           : (uint8_t)(255.0f * std::fmin(d / 255.0f, 1.0f));
                     dst[0] = dst[1] = dst[2] = g;
                     dst[3] = 255;
+                } else if (what == DumpWhat::Labels) {
+                    int32_t lab;
+                    std::memcpy(&lab, src + 4 * si, 4);
+                    const uint32_t px = lab == -1 ? 0u : (((uint32_t)lab & 0xFFFFFFu) | 0xFF000000u);
+                    dst[0] = (uint8_t)px; dst[1] = (uint8_t)(px >> 8); dst[2] = (uint8_t)(px >> 16); dst[3] = (uint8_t)(px >> 24);
                 } else {
                     std::memcpy(dst, src + 4 * si, 4);
                 }
@@ -451,6 +475,16 @@ int main(int argc, char **argv)
         cfg.instanceMaterials = matIds.data();
         cfg.instanceMaterialColumn = true;
     }
+    // --instance-labels: row i gets 1000 + splitmix64(splitmix64(SEED) ^ i) % 1000; rows 1::4 keep the sentinel, the id
+    // of their bound object
+    std::vector<int32_t> labels;
+    if (args.hasLabels) {
+        const uint64_t base = splitmix64(args.labelSeed);
+        for (uint64_t i = 0; i < s.instances.size(); ++i)
+            labels.push_back(i % 4 != 1 ? (int32_t)(1000 + splitmix64(base ^ i) % 1000) : Manager::kLabelObject);
+        cfg.instanceLabels = labels.data();
+        cfg.instanceLabelColumn = true;
+    }
     rc.worlds = s.worlds.data();
     if (args.gpus > 1) {
         cfg.deviceIDs = devices.data();
@@ -492,6 +526,8 @@ int main(int argc, char **argv)
             ok = dumpTiled(name, sh, hi - lo, args.width, resY, what, rt) && ok;
             if (args.normals)
                 ok = dumpTiled(name + ".normals", sh, hi - lo, args.width, resY, DumpWhat::Normal, rt) && ok;
+            if (args.hasLabels)
+                ok = dumpTiled(name + ".labels", sh, hi - lo, args.width, resY, DumpWhat::Labels, rt) && ok;
         }
     }
     if (!ok)

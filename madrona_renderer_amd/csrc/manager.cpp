@@ -106,6 +106,8 @@ Manager::Manager(const Config &cfg)
         c.flags |= MRX_FLAG_INSTANCE_MATERIALS;
     if (cfg.normals)
         c.flags |= MRX_FLAG_NORMALS;
+    if (cfg.instanceLabelColumn || cfg.instanceLabels)
+        c.flags |= MRX_FLAG_INSTANCE_LABELS;
     if (cfg.renderOutputs == RenderOutputs::Depth)
         c.flags |= MRX_FLAG_NO_RGB;
     else if (cfg.renderOutputs == RenderOutputs::RGB)
@@ -119,22 +121,33 @@ Manager::Manager(const Config &cfg)
 
     if (mrx_create(&c, &impl_->r) != MRX_OK)
         detail::fatal(mrx_last_error());
-    if (cfg.instanceMaterials) {
-        // the initial ids, world-major as mrx_create lays the rows out (spare rows -1), then the first frame again:
-        // what a caller reads before its first step() already shows them
-        std::vector<int32_t> ids;
+    // the initial values of an int32 column, world-major as mrx_create lays the rows out (spare rows `spare`)
+    const auto expand = [&](const int32_t *perInstance, int32_t spare) {
+        std::vector<int32_t> rows;
         for (uint32_t w = 0; w < cfg.numWorlds; ++w) {
             const Sim::WorldInit &wi = rc.worlds[w];
-            const uint32_t rows = std::max(wi.numInstances, cfg.maxInstancesPerWorld);
-            for (uint32_t i = 0; i < rows; ++i)
-                ids.push_back(i < wi.numInstances ? cfg.instanceMaterials[wi.instancesOffset + i] : -1);
+            const uint32_t n = std::max(wi.numInstances, cfg.maxInstancesPerWorld);
+            for (uint32_t i = 0; i < n; ++i)
+                rows.push_back(i < wi.numInstances ? perInstance[wi.instancesOffset + i] : spare);
         }
+        return rows;
+    };
+    if (cfg.instanceMaterials) {
+        const std::vector<int32_t> ids = expand(cfg.instanceMaterials, -1);
         if (!ids.empty() &&
             mrx_set_instance_materials(impl_->r, 0, (uint32_t)ids.size(), ids.data()) != MRX_OK)
             detail::fatal(mrx_last_error());
-        if (mrx_render(impl_->r) != MRX_OK)
+    }
+    if (cfg.instanceLabels) {
+        const std::vector<int32_t> labels = expand(cfg.instanceLabels, MRX_LABEL_OBJECT);
+        if (!labels.empty() &&
+            mrx_set_instance_labels(impl_->r, 0, (uint32_t)labels.size(), labels.data()) != MRX_OK)
             detail::fatal(mrx_last_error());
     }
+    // ... then the first frame again: what a caller reads before its first step() already shows them
+    if (cfg.instanceMaterials || cfg.instanceLabels)
+        if (mrx_render(impl_->r) != MRX_OK)
+            detail::fatal(mrx_last_error());
 
     // vestigial in the reference too (mgr.cpp:516-522)
     const char *num_agents_str = std::getenv("HIDESEEK_NUM_AGENTS");
@@ -171,6 +184,7 @@ Tensor Manager::instanceObjectTensor(uint32_t shard) const { return impl_->wrap(
 Tensor Manager::instanceScaleTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_SCALE, shard); }
 Tensor Manager::instanceColorTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_COLOR, shard); }
 Tensor Manager::instanceMaterialTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_MATERIAL, shard); }
+Tensor Manager::instanceLabelTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_LABEL, shard); }
 
 Tensor Manager::normalTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_NORMAL, shard); }
 
@@ -312,6 +326,22 @@ bool Manager::setInstanceMaterials(uint32_t first, uint32_t count, const int32_t
 void Manager::instanceMaterials(uint32_t first, uint32_t count, int32_t *out) const
 {
     if (mrx_instance_materials(impl_->r, first, count, out) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+bool Manager::setInstanceLabels(uint32_t first, uint32_t count, const int32_t *labels)
+{
+    const int rc = mrx_set_instance_labels(impl_->r, first, count, labels);
+    if (rc == MRX_E_INVALID)
+        return false;
+    if (rc != MRX_OK)
+        detail::fatal(mrx_last_error());
+    return true;
+}
+
+void Manager::instanceLabels(uint32_t first, uint32_t count, int32_t *out) const
+{
+    if (mrx_instance_labels(impl_->r, first, count, out) != MRX_OK)
         detail::fatal(mrx_last_error());
 }
 

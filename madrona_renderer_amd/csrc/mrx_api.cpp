@@ -355,6 +355,12 @@ struct mrx_renderer {
     int32_t *matStage = nullptr;
     hipEvent_t matEv = nullptr;
     bool matCopyPending = false;
+    // the label column (MRX_FLAG_INSTANCE_LABELS): the slice of the pose block behind the material
+    // column's slot; no pointer without the flag.  Staging and event of mrx_set_instance_labels as the material column's.
+    DevBuf<int32_t> instLabel;
+    int32_t *labelStage = nullptr;
+    hipEvent_t labelEv = nullptr;
+    bool labelCopyPending = false;
     DevBuf<uint32_t> rgb;
     DevBuf<float> depth;
     DevBuf<int32_t> ids;
@@ -442,6 +448,7 @@ struct mrx_renderer {
         viewTris.release(); viewTriCount.release();
         instPos.release(); instRot.release(); instScale.release();
         camPos.release(); camRot.release(); instObj.release(); instColor.release(); instMat.release();
+        instLabel.release();
         matTable.release();
         projDev.release();
         lightDev.release();
@@ -455,6 +462,10 @@ struct mrx_renderer {
             (void)hipHostFree(matStage);
         if (matEv)
             (void)hipEventDestroy(matEv);
+        if (labelStage)
+            (void)hipHostFree(labelStage);
+        if (labelEv)
+            (void)hipEventDestroy(labelEv);
         poseBlock.release(); geomBlock.release();
         rgb.release(); depth.release(); ids.release(); normal.release(); stamps.release();
         if (xccHost) (void)hipHostFree(xccHost);
@@ -1179,7 +1190,7 @@ int bindGeometry(mrx_renderer &r)
 // stream, behind every render enqueued so far and ahead of every later one, and the kernels' per-view instantiations
 // read them; the table of whichever does not vary holds the uniform values.
 // A renderer that shades with the colour column (params.instColor) or the material column
-// (params.instMat, 4.14) always launches with the tables: the chunked, brute and BVH kernels read the columns in their
+// (params.instMat, 4.14) or the label column (params.instLabel, 4.16) always launches with the tables: the chunked, brute and BVH kernels read the columns in their
 // per-view instantiations.  params.tablesVary tells the
 // group kernels, which have a colour form over the uniform constants, whether the tables hold anything else.
 int applyViewTables(mrx_renderer &r)
@@ -1213,7 +1224,7 @@ int applyViewTables(mrx_renderer &r)
     p.diffuse = lc.diffuse;
     const size_t n = r.proj.size();
     p.tablesVary = uniform ? 0u : 1u;
-    if (uniform && !((p.instColor || p.instMat) && n)) {
+    if (uniform && !((p.instColor || p.instMat || p.instLabel) && n)) {
         p.viewProj = nullptr;
         p.viewLight = nullptr;
         p.lightTable = 0;
@@ -1423,6 +1434,7 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     // one spare record past the end in a colour no test material has -- a missing range guard shows, it does not stray
     std::vector<MatRec> matRecs;
     const bool wantMats = (cfg.flags & MRX_FLAG_INSTANCE_MATERIALS) != 0;
+    const bool wantLabels = (cfg.flags & MRX_FLAG_INSTANCE_LABELS) != 0;
     r.anyMatTextured = false;
     if (wantMats) {
         for (const mrx_material &m : allMats) {
@@ -1551,7 +1563,9 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
         const PoseLayout lay = poseLayout(nv, ni);
         // (the colour column, where there is one, behind the layout the FAST prologue relies on; the material column
         // behind the colour column's slot, which a renderer with the material column alone has zero-filled)
-        const size_t poseBytes = (size_t)lay.total + (wantMats ? 2u * mrxAlign256(ni * 4u) : wantColors ? mrxAlign256(ni * 4u) : 0u) + 256;
+        // (the label column behind the slots of both, whichever of them the renderer has)
+        const size_t poseBytes = (size_t)lay.total +
+                                 (wantLabels ? 3u : wantMats ? 2u : wantColors ? 1u : 0u) * (size_t)mrxAlign256(ni * 4u) + 256;
         MRX_HIP(r.poseBlock.alloc(poseBytes));
         MRX_HIP(hipMemset(r.poseBlock.ptr, 0, poseBytes));
         uint8_t *b = r.poseBlock.ptr;
@@ -1582,6 +1596,14 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
             MRX_HIP(hipHostMalloc((void **)&r.matStage, (size_t)(ni ? ni : 1u) * sizeof(int32_t), hipHostMallocDefault));
             MRX_HIP(hipEventCreateWithFlags(&r.matEv, hipEventDisableTiming));
         }
+        if (wantLabels) {
+            // (every row at the sentinel: the segmask of S9 until a caller writes the column)
+            const std::vector<int32_t> labels(ni, MRX_LABEL_OBJECT);
+            r.instLabel.view(b + poseLabelOffset(nv, ni), labels.size());
+            MRX_HIP(up(r.instLabel.ptr, labels.data(), labels.size() * 4));
+            MRX_HIP(hipHostMalloc((void **)&r.labelStage, (size_t)(ni ? ni : 1u) * sizeof(int32_t), hipHostMallocDefault));
+            MRX_HIP(hipEventCreateWithFlags(&r.labelEv, hipEventDisableTiming));
+        }
     }
 
     const bool rt = cfg.render_mode == MRX_MODE_RAYTRACER;
@@ -1601,13 +1623,15 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
             if (pre.alloc((size_t)std::atoll(dbg) << 20) != hipSuccess)
                 (void)hipGetLastError();
         MRX_HIP(allocOutputs(px, !(cfg.flags & MRX_FLAG_NO_RGB), !(cfg.flags & MRX_FLAG_NO_DEPTH),
-                             rt || (cfg.flags & MRX_FLAG_VISIBILITY_IDS), firstKindIsOneBlock(px), r.rgb, r.depth, r.ids,
+                             rt || wantLabels || (cfg.flags & MRX_FLAG_VISIBILITY_IDS), firstKindIsOneBlock(px), r.rgb, r.depth,
+                             r.ids,
                              (cfg.flags & MRX_FLAG_NORMALS) != 0, r.normal));
         const char *hold = std::getenv("MRX_OUT_PRE_HOLD");
         if (!(hold && hold[0] == '1'))
             pre.release();
     }
-    const bool wantIds = rt || (cfg.flags & MRX_FLAG_VISIBILITY_IDS);
+    // (the label column brings the ids tensor to Rasterizer mode too: S11's segmask)
+    const bool wantIds = rt || wantLabels || (cfg.flags & MRX_FLAG_VISIBILITY_IDS);
 
     RasterParams &p = r.params;
     p.tris = r.tris.ptr;
@@ -1627,6 +1651,9 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     p.instMat = (cfg.flags & MRX_FLAG_NO_RGB) ? nullptr : r.instMat.ptr;
     p.matTable = r.matTable.ptr;
     p.numMaterials = wantMats ? (uint32_t)allMats.size() : 0u;
+    // (read under every output selection; never where the ids tensor holds visibility ids, which win over the segmask:
+    // such a renderer keeps the column and launches what one without it does)
+    p.instLabel = (cfg.flags & MRX_FLAG_VISIBILITY_IDS) ? nullptr : r.instLabel.ptr;
     p.camPos = r.camPos.ptr;
     p.camRot = r.camRot.ptr;
     p.rgb = r.rgb.ptr;
@@ -1660,7 +1687,7 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     }
     p.transposed = rt ? 1 : 0;
     // Raytracer ids are the segmask unless the caller asked for visibility ids
-    p.idsAreSegmask = (rt && !(cfg.flags & MRX_FLAG_VISIBILITY_IDS)) ? 1 : 0;
+    p.idsAreSegmask = ((rt || wantLabels) && !(cfg.flags & MRX_FLAG_VISIBILITY_IDS)) ? 1 : 0;
     p.debugSkip = 0;
     if (const char *dbg = std::getenv("MRX_DEBUG_SKIP"))
         p.debugSkip = (uint32_t)std::atoi(dbg);
@@ -1777,7 +1804,8 @@ int buildScene(const mrx_config &cfg, mrx_renderer &r)
     inf.num_shards = 1;
     inf.bytes_per_step = (uint64_t)px * (4u * ((r.rgb.ptr ? 1u : 0u) + (r.depth.ptr ? 1u : 0u) + (r.normal.ptr ? 1u : 0u)) +
                                          (wantIds ? 4u : 0u)) +
-                         (44ull + (r.instColor.ptr ? 4ull : 0ull) + (r.instMat.ptr ? 4ull : 0ull)) * inf.num_instances +
+                         (44ull + (r.instColor.ptr ? 4ull : 0ull) + (r.instMat.ptr ? 4ull : 0ull) +
+                          (r.instLabel.ptr ? 4ull : 0ull)) * inf.num_instances +
                          28ull * nviews;
     return bindGeometry(r);
 }
@@ -1998,26 +2026,41 @@ static std::vector<std::pair<mrx_renderer *, uint64_t>> rowOwners(mrx_renderer *
     return out;
 }
 
-static int rowRange(mrx_renderer *r, uint32_t first, uint32_t count, const void *ptr)
+// One int32 column of the instance rows with a host-side setter: the device slice, the pinned staging of the setter (one
+// word per row), the event behind its last copy, and the words of its error messages.
+struct RowColumn {
+    DevBuf<int32_t> mrx_renderer::*dev;
+    int32_t *mrx_renderer::*stage;
+    hipEvent_t mrx_renderer::*ev;
+    bool mrx_renderer::*pending;
+    const char *nullMsg, *noneMsg;
+};
+static const RowColumn kMaterialColumn = {
+    &mrx_renderer::instMat, &mrx_renderer::matStage, &mrx_renderer::matEv, &mrx_renderer::matCopyPending, "null material array",
+    "no instance materials: this renderer was created without MRX_FLAG_INSTANCE_MATERIALS" };
+static const RowColumn kLabelColumn = {
+    &mrx_renderer::instLabel, &mrx_renderer::labelStage, &mrx_renderer::labelEv, &mrx_renderer::labelCopyPending,
+    "null label array", "no instance labels: this renderer was created without MRX_FLAG_INSTANCE_LABELS" };
+
+static int rowRange(mrx_renderer *r, const RowColumn &col, uint32_t first, uint32_t count, const void *ptr)
 {
     uint64_t total = 0;
     bool column = true;
     for (const auto &o : rowOwners(r)) {
         total += o.first->info.num_instances;
-        column = column && o.first->instMat.ptr;
+        column = column && (o.first->*col.dev).ptr;
     }
     if (!ptr)
-        return fail(MRX_E_INVALID, "null material array");
+        return fail(MRX_E_INVALID, col.nullMsg);
     if ((uint64_t)first + count > total)
         return fail(MRX_E_INVALID, "rows [" + std::to_string(first) + ", " + std::to_string((uint64_t)first + count) +
                                        ") outside the renderer's " + std::to_string(total));
     if (!column)
-        return fail(MRX_E_UNSUPPORTED,
-                    "no instance materials: this renderer was created without MRX_FLAG_INSTANCE_MATERIALS");
+        return fail(MRX_E_UNSUPPORTED, col.noneMsg);
     return MRX_OK;
 }
 
-int mrx_set_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, const int32_t *materials)
+static int setRows(mrx_renderer *r, const RowColumn &col, uint32_t first_row, uint32_t count, const int32_t *values)
 {
     {
         const int src = settle(r);
@@ -2026,7 +2069,7 @@ int mrx_set_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t cou
     }
     if (!r)
         return fail(MRX_E_INVALID, "null renderer");
-    const int rc = rowRange(r, first_row, count, materials);
+    const int rc = rowRange(r, col, first_row, count, values);
     if (rc != MRX_OK)
         return rc;
     for (const auto &o : rowOwners(r)) {
@@ -2038,19 +2081,19 @@ int mrx_set_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t cou
         // (through the pinned staging: the copy runs on the stream behind every render enqueued so far, and the caller's
         // array is free when the call returns; the staging is overwritten only once the last copy from it has run)
         MRX_HIP(hipSetDevice(sh.device));
-        if (sh.matCopyPending)
-            MRX_HIP(hipEventSynchronize(sh.matEv));
-        int32_t *stage = sh.matStage + (lo - o.second);
-        std::memcpy(stage, materials + (lo - first_row), (hi - lo) * sizeof(int32_t));
-        MRX_HIP(hipMemcpyAsync(sh.instMat.ptr + (lo - o.second), stage, (hi - lo) * sizeof(int32_t), hipMemcpyHostToDevice,
+        if (sh.*col.pending)
+            MRX_HIP(hipEventSynchronize(sh.*col.ev));
+        int32_t *stage = sh.*col.stage + (lo - o.second);
+        std::memcpy(stage, values + (lo - first_row), (hi - lo) * sizeof(int32_t));
+        MRX_HIP(hipMemcpyAsync((sh.*col.dev).ptr + (lo - o.second), stage, (hi - lo) * sizeof(int32_t), hipMemcpyHostToDevice,
                                sh.stream));
-        MRX_HIP(hipEventRecord(sh.matEv, sh.stream));
-        sh.matCopyPending = true;
+        MRX_HIP(hipEventRecord(sh.*col.ev, sh.stream));
+        sh.*col.pending = true;
     }
     return MRX_OK;
 }
 
-int mrx_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, int32_t *out)
+static int getRows(mrx_renderer *r, const RowColumn &col, uint32_t first_row, uint32_t count, int32_t *out)
 {
     {
         const int src = settle(r);
@@ -2059,7 +2102,7 @@ int mrx_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, 
     }
     if (!r)
         return fail(MRX_E_INVALID, "null renderer");
-    const int rc = rowRange(r, first_row, count, out);
+    const int rc = rowRange(r, col, first_row, count, out);
     if (rc != MRX_OK)
         return rc;
     for (const auto &o : rowOwners(r)) {
@@ -2070,10 +2113,30 @@ int mrx_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, 
             continue;
         MRX_HIP(hipSetDevice(sh.device));
         MRX_HIP(hipStreamSynchronize(sh.stream));
-        MRX_HIP(hipMemcpy(out + (lo - first_row), sh.instMat.ptr + (lo - o.second), (hi - lo) * sizeof(int32_t),
+        MRX_HIP(hipMemcpy(out + (lo - first_row), (sh.*col.dev).ptr + (lo - o.second), (hi - lo) * sizeof(int32_t),
                           hipMemcpyDeviceToHost));
     }
     return MRX_OK;
+}
+
+int mrx_set_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, const int32_t *materials)
+{
+    return setRows(r, kMaterialColumn, first_row, count, materials);
+}
+
+int mrx_instance_materials(mrx_renderer *r, uint32_t first_row, uint32_t count, int32_t *out)
+{
+    return getRows(r, kMaterialColumn, first_row, count, out);
+}
+
+int mrx_set_instance_labels(mrx_renderer *r, uint32_t first_row, uint32_t count, const int32_t *labels)
+{
+    return setRows(r, kLabelColumn, first_row, count, labels);
+}
+
+int mrx_instance_labels(mrx_renderer *r, uint32_t first_row, uint32_t count, int32_t *out)
+{
+    return getRows(r, kLabelColumn, first_row, count, out);
 }
 
 int mrx_device_count(void)
@@ -2619,8 +2682,8 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
             return nullptr;
         }
         break;
-    case MRX_BUF_SEGMASK:   // mgr.cpp:592-605
-        if (!rt) {
+    case MRX_BUF_SEGMASK:   // mgr.cpp:592-605; with the label column S11's segmask, in both modes
+        if (!rt && !r->instLabel.ptr) {
             fail(MRX_E_UNSUPPORTED, "Segmask not implemented for rasterizer");
             return nullptr;
         }
@@ -2656,6 +2719,13 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
         if (!ptr) {
             fail(MRX_E_UNSUPPORTED,
                  "no instance materials: this renderer was created without MRX_FLAG_INSTANCE_MATERIALS");
+            return nullptr;
+        }
+        break;
+    case MRX_BUF_INSTANCE_LABEL:      // the label column; MRX_LABEL_OBJECT = the bound object's id
+        dims[0] = I; *ndim = 1; *dtype = MRX_DTYPE_I32; ptr = r->instLabel.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED, "no instance labels: this renderer was created without MRX_FLAG_INSTANCE_LABELS");
             return nullptr;
         }
         break;

@@ -182,6 +182,11 @@ PYBIND11_MODULE(madrona_renderer, m)
     m.attr("MRX_FLAG_NORMALS") = (uint32_t)MRX_FLAG_NORMALS;
     m.attr("MRX_BUF_NORMAL") = (int)MRX_BUF_NORMAL;
     m.attr("MRX_NUM_BUFFERS_EXT2") = (int)MRX_NUM_BUFFERS_EXT2;
+    // ... and of the label column
+    m.attr("MRX_FLAG_INSTANCE_LABELS") = (uint32_t)MRX_FLAG_INSTANCE_LABELS;
+    m.attr("MRX_BUF_INSTANCE_LABEL") = (int)MRX_BUF_INSTANCE_LABEL;
+    m.attr("MRX_NUM_BUFFERS_EXT3") = (int)MRX_NUM_BUFFERS_EXT3;
+    m.attr("MRX_LABEL_OBJECT") = (int32_t)MRX_LABEL_OBJECT;
     m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
     m.attr("MRX_CONFIG_SIZE") = (uint32_t)sizeof(mrx_config);
 
@@ -301,7 +306,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<Sim::WorldInit> &worlds,
                          const std::vector<int> &device_ids, int max_instances_per_world,
                          Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors,
-                         py::object instance_materials, bool normals) {
+                         py::object instance_materials, bool normals, py::object instance_labels) {
                  if (mesh_vertices.size() && (mesh_vertices.ndim() != 2 || mesh_vertices.shape(1) != 3))
                      throw py::value_error("mesh_vertices must have shape [N, 3]");
                  if (mesh_uvs.size() && (mesh_uvs.ndim() != 2 || mesh_uvs.shape(1) != 2))
@@ -416,6 +421,17 @@ PYBIND11_MODULE(madrona_renderer, m)
                      cfg.instanceMaterialColumn = true;
                  }
                  cfg.normals = normals;
+                 // instance_labels: None (no column), True (a column of MRX_LABEL_OBJECT) or [num_instances] int32
+                 py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels;
+                 if (py::isinstance<py::bool_>(instance_labels)) {
+                     cfg.instanceLabelColumn = instance_labels.cast<bool>();
+                 } else if (!instance_labels.is_none()) {
+                     labels = py::array_t<int32_t, py::array::c_style | py::array::forcecast>::ensure(instance_labels);
+                     if (!labels || labels.ndim() != 1 || (size_t)labels.shape(0) != instances.size())
+                         throw py::value_error("instance_labels must be None, True or an int32 array of shape [num_instances]");
+                     cfg.instanceLabels = labels.data();
+                     cfg.instanceLabelColumn = true;
+                 }
                  return new Manager(cfg);
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -438,7 +454,9 @@ PYBIND11_MODULE(madrona_renderer, m)
              // instance_materials = True or a [num_instances] int32 array: the material override column
              py::arg("instance_materials") = py::none(),
              // normals = True: the surface-normal output, normal_tensor()
-             py::arg("normals") = false)
+             py::arg("normals") = false,
+             // instance_labels = True or a [num_instances] int32 array: the label column (the segmask in both modes)
+             py::arg("instance_labels") = py::none())
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -487,6 +505,12 @@ PYBIND11_MODULE(madrona_renderer, m)
         .def("instance_color_tensor",
              [](py::object self, py::object shard) {
                  return wrapTensor(self, self.cast<Manager &>().instanceColorTensor(shardOf(self, shard)));
+             },
+             py::arg("shard") = py::none())
+        // i32 [instances]: the label of every row, MRX_LABEL_OBJECT = the bound object's id (needs instance_labels=)
+        .def("instance_label_tensor",
+             [](py::object self, py::object shard) {
+                 return wrapTensor(self, self.cast<Manager &>().instanceLabelTensor(shardOf(self, shard)));
              },
              py::arg("shard") = py::none())
         // i32 [instances]: the material override of every row, outside the table = none (needs instance_materials=)
@@ -670,6 +694,26 @@ PYBIND11_MODULE(madrona_renderer, m)
              })
         // per-instance material override from host memory (rows of the whole job from first_row on; a renderer of
         // several shards splits them).  Stream-ordered: renders enqueued before keep the old ids.
+        // per-instance labels from host memory, as set_instance_materials / instance_materials below
+        .def("set_instance_labels",
+             [](Manager &self, py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids, int64_t first_row) {
+                 if (ids.ndim() != 1)
+                     throw py::value_error("labels must be a one-dimensional int32 array");
+                 if (first_row < 0 || first_row + (int64_t)ids.shape(0) > (int64_t)self.numInstanceRows())
+                     throw py::value_error("more labels than instance rows from first_row on");
+                 const int32_t none = MRX_LABEL_OBJECT;
+                 if (!self.setInstanceLabels((uint32_t)first_row, (uint32_t)ids.shape(0), ids.shape(0) ? ids.data() : &none))
+                     throw py::value_error(mrx_last_error());
+             },
+             py::arg("labels"), py::arg("first_row") = 0)
+        .def("instance_labels",
+             [](Manager &self) {
+                 const uint32_t n = self.numInstanceRows();
+                 py::array_t<int32_t> out(n);
+                 int32_t none = MRX_LABEL_OBJECT;
+                 self.instanceLabels(0, n, n ? out.mutable_data() : &none);
+                 return out;
+             })
         .def("set_instance_materials",
              [](Manager &self, py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids, int64_t first_row) {
                  if (ids.ndim() != 1)

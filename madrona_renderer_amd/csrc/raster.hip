@@ -107,8 +107,8 @@ struct GroupSetupArgs {
 
 // setupTriangle under the projection constants `pr` of the view and the light `lt` of its world (per-view form), and
 // under the colour and material overrides of the instance row where the renderer has the columns (DESIGN.md 4.13,
-// 4.14; wave-uniform tests)
-template <typename NRMOUT = NoNormalOut>
+// 4.14; wave-uniform tests).  LAB (the instantiations that store ids): under the label column too (S11, 4.16).
+template <bool LAB = false, typename NRMOUT = NoNormalOut>
 __device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const ViewProj &pr, const ViewLight &lt,
                                                   const ViewConst &vc, WorldTri wt, int32_t kWorld, TriPlanes &out,
                                                   float *shade, float *cold, const NRMOUT nrm = NRMOUT())
@@ -122,14 +122,18 @@ __device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const V
     const auto matOf = [&]() -> MatOverride {
         return MatOverride { p.instMat ? p.instMat[wt.inst] : -1, p.numMaterials, p.matTable };
     };
-    return setupTriangleCore<true, true, true, true>(sa, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade, cold, icol,
-                                                     matOf, nrm);
+    const bool valid = setupTriangleCore<true, true, true, true>(sa, vc.lv, x, wt.tri, p.instObj[wt.inst], kWorld, out, shade,
+                                                                 cold, icol, matOf, nrm);
+    if (LAB)
+        applyLabel(shade, p.instLabel, wt.inst);
+    return valid;
 }
 
 // S for one chunk of up to 64 world-triangles; returns the valid-lane mask.
 // PV: the per-view form, the view's projection constants in `pr` and its world's light in `lt`.
 // NRM: the normals form: the packed normal of the lane's triangle goes to nrmTab[lane].
-template <bool PV, bool NRM = false>
+// LAB: passed on to setupTriangleProj.
+template <bool PV, bool NRM = false, bool LAB = false>
 __device__ __forceinline__ uint64_t setupChunk(const RasterParams &p, const ViewConst &vc,
                                                const TileCtx &t, uint32_t chunk, int lane,
                                                WaveLds &L, const ViewProj &pr, const ViewLight &lt,
@@ -142,10 +146,10 @@ __device__ __forceinline__ uint64_t setupChunk(const RasterParams &p, const View
         TriPlanes c;
         float *h = L.hot[lane];
         if (NRM)
-            valid = PV ? setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, h + 12, L.cold[lane], NormalOut { nrmTab + lane })
+            valid = PV ? setupTriangleProj<LAB>(p, pr, lt, vc, wt, (int32_t)k, c, h + 12, L.cold[lane], NormalOut { nrmTab + lane })
                        : setupTriangle(p, vc, wt, (int32_t)k, c, h + 12, L.cold[lane], NormalOut { nrmTab + lane });
         else
-            valid = PV ? setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, h + 12, L.cold[lane])
+            valid = PV ? setupTriangleProj<LAB>(p, pr, lt, vc, wt, (int32_t)k, c, h + 12, L.cold[lane])
                        : setupTriangle(p, vc, wt, (int32_t)k, c, h + 12, L.cold[lane]);
         h[0] = c.A0; h[1] = c.B0; h[2] = c.C0;
         h[3] = c.A1; h[4] = c.B1; h[5] = c.C1;
@@ -241,7 +245,7 @@ __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
 
     uint64_t mask0 = 0;
     if (!MULTI)
-        mask0 = setupChunk<PV, NRM>(p, vc, t, 0, lane, L, pr, lt, nrmTab);
+        mask0 = setupChunk<PV, NRM, IDS>(p, vc, t, 0, lane, L, pr, lt, nrmTab);
 
     for (int band = 0; band < 4; ++band) {
         float best[kBlocksPerBand];
@@ -273,7 +277,7 @@ __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
                 }
         } else {
             for (uint32_t chunk = 0; chunk < t.numTris; chunk += kChunk) {
-                const uint64_t mask = setupChunk<PV, NRM>(p, vc, t, chunk, lane, L, pr, lt, nrmTab);
+                const uint64_t mask = setupChunk<PV, NRM, IDS>(p, vc, t, chunk, lane, L, pr, lt, nrmTab);
                 rasterBandBrute(L, mask, pxf, py0, py1, invNear, best, bid);
                 // resolve this chunk's winners before its records are replaced
 #pragma unroll
@@ -582,13 +586,13 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
                 if (k < t.numTris && !(p.debugSkip & 8u)) {
                     const WorldTri wt = p.viewTris[t.triBegin + k];
                     if (NRM && PV)
-                        valid = setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec],
-                                                  NormalOut { nrmLds + rec });
+                        valid = setupTriangleProj<IDS>(p, pr, lt, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec],
+                                                       NormalOut { nrmLds + rec });
                     else if (NRM)
                         valid = setupTriangle(p, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec],
                                               NormalOut { nrmLds + rec });
                     else if (PV)
-                        valid = setupTriangleProj(p, pr, lt, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
+                        valid = setupTriangleProj<IDS>(p, pr, lt, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
                     else
                         valid = setupTriangle(p, vc, wt, (int32_t)k, c, lds.rec.shade[rec], lds.rec.cold[rec]);
                 }
@@ -900,8 +904,13 @@ constexpr int groupWaves(bool tex) { return tex ? 4 : 8; }
 // one more tensor.  The colour and material columns are read behind null tests, and the XCD trade and report are
 // run-time tests of p.xcdPhase / p.xccReport here, so that two forms (uniform constants, per-view tables) cover
 // every renderer with the output.
+// LAB: the label form (instantiated with IDS, PV, LT, COL and MAT, output selection by pointer and
+// XMODE 0, with and without NRM): the set-up lanes read their row's label beside its ObjectID and write S11's value into
+// the record's label slot.  Everything optional is taken as the normals form takes it: the colour and material columns
+// behind null tests, the XCD trade and report at run time, so one form per family and normals setting covers every
+// renderer with the column (which always launches with the per-view tables filled).
 template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT, bool PV = false, bool LT = false, bool COL = false,
-          bool MAT = false, bool NRM = false>
+          bool MAT = false, bool NRM = false, bool LAB = false>
 __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances,
                                                 uint32_t hPool, uint32_t hShape, uint32_t hGroups, uint32_t hPrefix,
                                                 uint32_t hFirst01, uint32_t hFirst23, const RasterParams p)
@@ -931,12 +940,13 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     const float *aCamRot = FAST ? reinterpret_cast<const float *>(hPose + lay.camRot) : p.camRot;
     const float *aCamPos = FAST ? reinterpret_cast<const float *>(hPose + lay.camPos) : p.camPos;
     const int32_t *aInstObj = FAST ? reinterpret_cast<const int32_t *>(hPose + lay.instObj) : p.instObj;
-    // (NRM: whichever columns the renderer has -- null without)
-    const uint32_t *aInstColor = NRM ? p.instColor
+    // (NRM, LAB: whichever columns the renderer has -- null without)
+    constexpr bool BYPTR = NRM || LAB;
+    const uint32_t *aInstColor = BYPTR ? p.instColor
                                  : FAST ? reinterpret_cast<const uint32_t *>(hPose + lay.total)
                                  : MAT ? reinterpret_cast<const uint32_t *>(p.poseBlock + poseColorOffset(p.numViews, p.numInstances))
                                        : p.instColor;
-    const int32_t *aInstMat = NRM ? p.instMat
+    const int32_t *aInstMat = BYPTR ? p.instMat
                               : FAST ? reinterpret_cast<const int32_t *>(hPose + lay.total + mrxAlign256(hInstances * 4u))
                                      : p.instMat;
     const uint32_t tilesPerView = FAST ? 1u : p.tilesFast * p.tilesSlow;
@@ -960,11 +970,11 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     // picks the instantiation by the parity workgroup 0 reported in an earlier launch
     // of this renderer -- every workgroup of a launch runs the same code, so the trade
     // is consistent whatever the hardware does; a stale value costs speed, never pixels.
-    const uint32_t blk = ((NRM ? (p.xcdPhase & 1u) != 0u : (XMODE & 1) != 0) && SLOTS == 16 && aXcdSkew && (blockIdx.x ^ 1u) < aGrid)
+    const uint32_t blk = ((BYPTR ? (p.xcdPhase & 1u) != 0u : (XMODE & 1) != 0) && SLOTS == 16 && aXcdSkew && (blockIdx.x ^ 1u) < aGrid)
                              ? blockIdx.x ^ 1u : blockIdx.x;
     // workgroup 0 reports where it runs: a host-mapped word, written by the last wave,
     // which issues no loads during set-up -- the slow write sits ahead of nothing
-    if (((XMODE & 2) || (NRM && SLOTS == 16)) && blockIdx.x == 0 && threadIdx.x == (groupWaves(TEX) - 1) * kWave && p.xccReport)
+    if (((XMODE & 2) || (BYPTR && SLOTS == 16)) && blockIdx.x == 0 && threadIdx.x == (groupWaves(TEX) - 1) * kWave && p.xccReport)
         *p.xccReport = __builtin_amdgcn_s_getreg((3 << 11) | 20);   // HW_REG_XCC_ID[3:0]
     uint32_t bid = blk;
     if (aXcdRotate && (bid | 7u) < aGrid)
@@ -1128,12 +1138,19 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                     pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse, p.transposed };
                 InstXform x;
                 instanceTransform(sa, vc, wt.inst, x);
-                if (NRM) {
+                if (BYPTR) {
                     const MatOverride mo = { aInstMat ? aInstMat[wt.inst] : -1, p.numMaterials, p.matTable };
-                    valid = setupTriangleCore<true, true, true, true>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
-                                                                      lds.shade[rec], lds.cold[rec],
-                                                                      aInstColor ? aInstColor[wt.inst] : 0u, mo,
-                                                                      NormalOut { nrmLds + rec });
+                    if constexpr (NRM)
+                        valid = setupTriangleCore<true, true, true, true>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
+                                                                          lds.shade[rec], lds.cold[rec],
+                                                                          aInstColor ? aInstColor[wt.inst] : 0u, mo,
+                                                                          NormalOut { nrmLds + rec });
+                    else
+                        valid = setupTriangleCore<true, true, true, true>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
+                                                                          lds.shade[rec], lds.cold[rec],
+                                                                          aInstColor ? aInstColor[wt.inst] : 0u, mo);
+                    if (LAB)
+                        applyLabel(lds.shade[rec], p.instLabel, wt.inst);
                 } else {
                 const MatOverride mo = { MAT ? aInstMat[wt.inst] : -1, p.numMaterials, p.matTable };
                 valid = setupTriangleCore<true, OUT != kOutDepth, COL, MAT>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
@@ -1556,6 +1573,28 @@ void rasterGroupKernelFastNPV(const char *hPose, const char *hGeom, uint32_t hVi
                                                                                        hFirst23, p);
 }
 
+// The label forms (p.instLabel): one per family and normals setting.  They store ids (the
+// segmask), read both tables -- a renderer with the label column always fills them -- and every other column behind a
+// null test; six waves per SIMD, as the other forms over the light table have.
+template <int SLOTS, bool TEX, bool NRM>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : 6)
+void rasterGroupKernelL(const RasterParams p)
+{
+    groupKernelBody<true, SLOTS, TEX, 0, false, kOutByPointer, true, true, true, true, NRM, true>(nullptr, nullptr, 0u, 0u, 0u, 0u,
+                                                                                                 0u, 0u, 0u, 0u, p);
+}
+
+template <bool TEX, bool NRM>
+__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 6)
+void rasterGroupKernelFastL(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
+                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
+                            const RasterParams p)
+{
+    groupKernelBody<true, 16, TEX, 0, true, kOutByPointer, true, true, true, true, NRM, true>(hPose, hGeom, hViews, hInstances,
+                                                                                             hPool, hShape, hGroups, hPrefix,
+                                                                                             hFirst01, hFirst23, p);
+}
+
 }  // namespace
 
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
@@ -1735,7 +1774,20 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
     } while (0)
 #define MRX_GROUP_O(S, X, O, OP)                                               \
     do {                                                                       \
-        if (p.normal && pv && p.tablesVary) {                                  \
+        if (p.instLabel && ids && pv) {                                        \
+            if (fast && S == 16) {                                             \
+                if (p.normal) { if (p.anyTextured) rasterGroupKernelFastL<true, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);    \
+                                else rasterGroupKernelFastL<false, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }               \
+                else          { if (p.anyTextured) rasterGroupKernelFastL<true, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
+                                else rasterGroupKernelFastL<false, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }              \
+            } else if (p.normal) {                                             \
+                if (p.anyTextured) rasterGroupKernelL<S, true, true><<<grid, gblock, 0, stream>>>(q);     \
+                else               rasterGroupKernelL<S, false, true><<<grid, gblock, 0, stream>>>(q);    \
+            } else {                                                           \
+                if (p.anyTextured) rasterGroupKernelL<S, true, false><<<grid, gblock, 0, stream>>>(q);    \
+                else               rasterGroupKernelL<S, false, false><<<grid, gblock, 0, stream>>>(q);   \
+            }                                                                  \
+        } else if (p.normal && pv && p.tablesVary) {                                  \
             MRX_GROUP_FORM(S, rasterGroupKernelFastNPV, rasterGroupKernelNPV); \
         } else if (p.normal) {                                                 \
             MRX_GROUP_FORM(S, rasterGroupKernelFastN, rasterGroupKernelN);     \

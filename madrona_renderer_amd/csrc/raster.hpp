@@ -222,9 +222,19 @@ struct RasterParams {
     uint32_t numMaterials;
     // Surface-normal output: [view][slow][fast] packed view-space normals, storage as rgb's;
     // null = not rendered (no MRX_FLAG_NORMALS): the launchers then pick the kernels they always did, none of
-    // which reads this member -- the last of the block.
+    // which reads this member.
     uint32_t *normal;
+    // Per-instance label: [I] int32; kLabelObject = the id of the object the row is bound to
+    // (S9's segmask value), any other value is what the segmask holds on the pixels the row's triangles win.  The slice
+    // of the pose block behind the material column's slot (poseLabelOffset); null = no column, or a renderer whose ids
+    // tensor holds visibility ids.  Set together with viewProj and with ids (idsAreSegmask): the per-view segmask
+    // instantiations of the chunked, brute and BVH kernels read it behind a null check, the group kernels have label
+    // forms of their own.  The last member of the block.
+    const int32_t *instLabel;
 };
+
+// the label that stands for "the bound object's id" (include/mrx.h MRX_LABEL_OBJECT)
+constexpr int32_t kLabelObject = INT32_MIN;
 
 // ---- the argument header of the group kernel's fast prologue (raster.hip, FAST) -------------------------------------
 // The command processor can write the first dwords of a kernel's argument block into SGPRs at wave launch
@@ -262,6 +272,12 @@ MRX_HD inline uint32_t poseColorOffset(uint32_t views, uint32_t instances) { ret
 MRX_HD inline uint32_t poseMaterialOffset(uint32_t views, uint32_t instances)
 {
     return poseColorOffset(views, instances) + mrxAlign256(instances * 4u);
+}
+// the label column of a renderer that has one (RasterParams::instLabel): [instances] dwords behind the slots of the
+// colour and the material column, whether or not the renderer has those
+MRX_HD inline uint32_t poseLabelOffset(uint32_t views, uint32_t instances)
+{
+    return poseMaterialOffset(views, instances) + mrxAlign256(instances * 4u);
 }
 // geometry block: ObjTri[pool] at 0, TriMat[pool] at geomMatsOffset(pool)
 MRX_HD inline uint32_t geomMatsOffset(uint32_t poolTris) { return mrxAlign256(poolTris * 64u); }

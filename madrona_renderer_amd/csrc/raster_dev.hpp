@@ -348,6 +348,17 @@ __device__ __forceinline__ bool setupTriangleCore(const PARAMS &p, const float (
     return valid;
 }
 
+// S11: the label slot of the shading record `shade` setupTriangleCore has just written, under the
+// label column of the renderer: the row's label where it is not kLabelObject, else the bound object's id, which is
+// there already.  `labels` null (a wave-uniform test) = no column.  One dword load and one select per (view, triangle).
+__device__ __forceinline__ void applyLabel(float *shade, const int32_t *labels, uint32_t row)
+{
+    if (labels) {
+        const int32_t lab = labels[row];
+        shade[2] = lab != kLabelObject ? __int_as_float(lab) : shade[2];
+    }
+}
+
 // S8 u/v planes of a triangle whose edge planes are `c` (as setupTriangleCore left them:
 // transposed and flipped), `rad` = |1/d|, uv = the six texture coordinates of ObjTri:
 // the same operations in the same order as in setupTriangleCore<true>.

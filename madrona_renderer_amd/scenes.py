@@ -19,6 +19,9 @@ SEED = 0x4D52584D
 DATA_DIR = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))),
                         "data")
 
+# the label that stands for "the id of the object the row is bound to" (MRX_LABEL_OBJECT, the module's constant)
+LABEL_OBJECT = -2 ** 31
+
 
 @dataclass
 class SceneDesc:
@@ -54,6 +57,11 @@ class SceneDesc:
     # then the ones of MTL files); an id outside it (-1) leaves the row its own materials.  None = no column; True = a
     # column of -1 (written later through instance_material_tensor()).  Worlds that alias rows share their ids.
     instance_materials: object = None
+    # per-instance labels, parallel to `instances`: [N] int32; LABEL_OBJECT (INT32_MIN) = the id of the row's bound object.
+    # With the column segmask_tensor() holds, in both render modes, the label of the row that wins each pixel.  None = no
+    # column; True = a column of LABEL_OBJECT (written later through instance_label_tensor()).  Worlds that alias rows
+    # share their labels.
+    instance_labels: object = None
     # the surface-normal output (normal_tensor()): view-space normals of the winning triangles, RGBA8-encoded
     normals: bool = False
 
@@ -283,6 +291,14 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
             extra["instance_materials"] = mats
     if desc.normals:
         extra["normals"] = True
+    if desc.instance_labels is not None:
+        if desc.instance_labels is True:
+            extra["instance_labels"] = True
+        else:
+            labels = np.ascontiguousarray(desc.instance_labels, np.int32)
+            if labels.shape != (len(desc.instances),):
+                raise ValueError("instance_labels needs one label per instance")
+            extra["instance_labels"] = labels
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:

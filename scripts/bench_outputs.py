@@ -2,10 +2,15 @@
 """Kernel time of each output selection (RGBD, Depth, RGB: Manager::RenderOutputs) on the shapes
 that matter, one JSON line per (configuration, setting):
 
-  python scripts/bench_outputs.py [--rounds 5] [--budget-ms 30] [--only headline,c2,...] [--normals]
+  python scripts/bench_outputs.py [--rounds 5] [--budget-ms 30] [--only headline,c2,...] [--normals] [--labels]
+                                  [--root TREE]
 
 --normals times RGBD+N, Depth+N and RGB+N (the surface-normal output beside each selection) beside the
 three settings, in the same alternation; without it the script does what it always did.
+--labels times RGBD+V (the ids tensor holding visibility ids: in Rasterizer mode the renderer that writes the same
+12 B/px without labels) and RGBD+L (mixed labels in the label column, DESIGN.md 4.16: the segmask in both modes) beside
+them.  --root TREE imports madrona_renderer_amd from another checkout (a build of the parent commit, say); a tree
+whose SceneDesc has no instance_labels skips RGBD+L, so the same command line measures both builds.
 
 Every renderer of a configuration is created and warmed first; then the settings alternate within
 the process, `rounds` times, each measurement a batch of back-to-back renders between two events
@@ -27,6 +32,7 @@ sys.path.insert(0, ROOT)
 HBM_PEAK_GBPS = 8000.0
 SETTINGS = ("RGBD", "Depth", "RGB")
 NORMAL_SETTINGS = ("RGBD+N", "Depth+N", "RGB+N")
+LABEL_SETTINGS = ("RGBD+V", "RGBD+L")
 
 
 def configs(scenes):
@@ -51,9 +57,20 @@ def make(scenes, factory, setting, variant):
         if setting.endswith("+N"):
             desc.normals = True
             setting = setting[:-2]
+        elif setting.endswith("+V"):
+            os.environ["MADRONA_MI355_VISIBILITY"] = "1"
+            setting = setting[:-2]
+        elif setting.endswith("+L"):
+            # labels in [1000, 2000), rows 1::4 at the sentinel (tests/label_oracle.py::mixed)
+            import numpy as np
+            labels = np.random.default_rng(11).integers(1000, 2000, len(desc.instances)).astype(np.int32)
+            labels[1::4] = -2 ** 31
+            desc.instance_labels = labels
+            setting = setting[:-2]
         return scenes.make_renderer(desc, render_outputs=setting)
     finally:
         os.environ.pop("MADRONA_MI355_KERNEL", None)
+        os.environ.pop("MADRONA_MI355_VISIBILITY", None)
 
 
 def us_per_render(r, steps):
@@ -66,12 +83,19 @@ def main(argv=None):
     ap.add_argument("--budget-ms", type=float, default=30.0, help="device time of one measurement")
     ap.add_argument("--only", default="", help="comma-separated configuration keys")
     ap.add_argument("--normals", action="store_true", help="also time each setting with the surface-normal output")
+    ap.add_argument("--labels", action="store_true", help="also time RGBD with visibility ids and with the label column")
+    ap.add_argument("--root", default="", help="import madrona_renderer_amd from this checkout instead")
     a = ap.parse_args(argv)
     if a.rounds < 3:
         ap.error("--rounds must be at least 3")
+    if a.root:
+        sys.path.insert(0, os.path.abspath(a.root))
     from madrona_renderer_amd import scenes
     only = set(filter(None, a.only.split(",")))
     settings = SETTINGS + (NORMAL_SETTINGS if a.normals else ())
+    if a.labels:
+        has = "instance_labels" in scenes.SceneDesc.__dataclass_fields__
+        settings += LABEL_SETTINGS if has else LABEL_SETTINGS[:1]
     for key, label, factory, variant in configs(scenes):
         if only and key not in only:
             continue
