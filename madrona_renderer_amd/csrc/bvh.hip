@@ -1503,42 +1503,34 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
 #undef MRX_TLAS_HDR
 }
 
+// May a form of the tile kernel be instantiated with CLS?  Every one but the per-view normals form of a textured scene
+// (classifiesPerStrip, the run-time rule of the launcher, is written with this function).
+constexpr bool tileFormClassifies(KernelForm f, bool tex) { return !(f == KernelForm::NPV && tex); }
+
+// launch bounds of the tile kernels, uniform and form alike: one wave per strip of the tile, four waves per SIMD
+constexpr int tileThreads(int th) { return kWave * (th / 8); }
+constexpr int kTileWavesPerSimd = 4;
+
 template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
-__global__ __launch_bounds__(kWave *(TH / 8), 4)
+__global__ __launch_bounds__(tileThreads(TH), kTileWavesPerSimd)
 void bvhTileKernel(const RasterParams p)
 {
     tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, false>(p);
 }
 
-// the per-view form (p.viewProj)
-template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
-__global__ __launch_bounds__(kWave *(TH / 8), 4)
-void bvhTileKernelPV(const RasterParams p)
+// The form kernel (raster.hpp KernelForm): PV the per-view form (p.viewProj); PVM that of a renderer with the material
+// override column (p.instMat); N and NPV the normals forms (p.normal, 4.15), N over the uniform
+// constants, NPV over the per-view tables and the colour / material columns (null tests).  The body's MAT is the
+// material column of the per-view forms: the uniform normals form reads no column.
+template <KernelForm F, int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
+__global__ __launch_bounds__(tileThreads(TH), kTileWavesPerSimd)
+void bvhTileFormKernel(const RasterParams p)
 {
-    tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, true>(p);
-}
-
-// the per-view form of a renderer with the material override column (p.instMat)
-template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
-__global__ __launch_bounds__(kWave *(TH / 8), 4)
-void bvhTileKernelPVM(const RasterParams p)
-{
-    tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, true, true>(p);
-}
-// the normals forms (p.normal): N over the uniform constants, NPV over the per-view tables and the
-// colour / material columns (null tests)
-template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
-__global__ __launch_bounds__(kWave *(TH / 8), 4)
-void bvhTileKernelN(const RasterParams p)
-{
-    tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, false, false, true>(p);
-}
-
-template <int IDS, bool TEX, int TW, int TH, bool CLS = false, bool MULTI = false>
-__global__ __launch_bounds__(kWave *(TH / 8), 4)
-void bvhTileKernelNPV(const RasterParams p)
-{
-    tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, true, true, true>(p);
+    static_assert(F == KernelForm::PV || F == KernelForm::PVM || F == KernelForm::N || F == KernelForm::NPV,
+                  "the forms of this family");
+    static_assert(!CLS || tileFormClassifies(F, TEX), "launchBvh, classifiesPerStrip");
+    constexpr FormFlags f = formFlags(F);
+    tileKernelBody<IDS, TEX, TW, TH, CLS, MULTI, f.pv, f.pv && f.mat, f.nrm>(p);
 }
 
 // ---------------------------------------------------------------------------
@@ -1979,34 +1971,24 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
 #undef MRX_STAMP
 }
 
+// launch bounds of the flat kernels, uniform and form alike
+constexpr int kFlatThreads = kWave * 8, kFlatWavesPerSimd = MRX_FLAT_ZBUFS == 2 ? 4 : 6;
+
 template <int IDS, bool TEX, int OUT = kOutRGBD>
-__global__ __launch_bounds__(kWave * 8, MRX_FLAT_ZBUFS == 2 ? 4 : 6)
+__global__ __launch_bounds__(kFlatThreads, kFlatWavesPerSimd)
 void bvhFlatKernel(const RasterParams p)
 {
     flatKernelBody<IDS, TEX, OUT, false>(p);
 }
 
-// the per-view form (p.viewProj): output selection by pointer
-template <int IDS, bool TEX>
-__global__ __launch_bounds__(kWave * 8, MRX_FLAT_ZBUFS == 2 ? 4 : 6)
-void bvhFlatKernelPV(const RasterParams p)
+// the form kernel, output selection by pointer: PV the per-view form (p.viewProj), N and NPV the normals forms
+// (p.normal)
+template <KernelForm F, int IDS, bool TEX>
+__global__ __launch_bounds__(kFlatThreads, kFlatWavesPerSimd)
+void bvhFlatFormKernel(const RasterParams p)
 {
-    flatKernelBody<IDS, TEX, kOutByPointer, true>(p);
-}
-
-// the normals forms (p.normal): output selection by pointer in both
-template <int IDS, bool TEX>
-__global__ __launch_bounds__(kWave * 8, MRX_FLAT_ZBUFS == 2 ? 4 : 6)
-void bvhFlatKernelN(const RasterParams p)
-{
-    flatKernelBody<IDS, TEX, kOutByPointer, false, true>(p);
-}
-
-template <int IDS, bool TEX>
-__global__ __launch_bounds__(kWave * 8, MRX_FLAT_ZBUFS == 2 ? 4 : 6)
-void bvhFlatKernelNPV(const RasterParams p)
-{
-    flatKernelBody<IDS, TEX, kOutByPointer, true, true>(p);
+    static_assert(F == KernelForm::PV || F == KernelForm::N || F == KernelForm::NPV, "the forms of this family");
+    flatKernelBody<IDS, TEX, kOutByPointer, formFlags(F).pv, formFlags(F).nrm>(p);
 }
 
 }  // namespace
@@ -2021,6 +2003,46 @@ size_t ldsFor(uint32_t passInst, bool textured, int tw, int th, bool cls, uint32
     return (size_t)(tw + kZPad) * th * 8 + tabBytes(textured, (int)cap) + 64 + (size_t)bigCap(tw, th, cls, textured) * 64 +
            ((size_t)passInst * (kInstRecDw + 4) * 4 + 16) * tlasBlocks + sizeof(WaveScratch) * (size_t)(th / 8);
 }
+
+// The kernels need more dynamic LDS than the 64 KB a launch may ask for by default.  The opt-in is a property of
+// (function, device) -- a renderer per device in one process (mrx_config.device_ids, renderer_headless --gpus N)
+// launches the same instantiation on several devices, from several host threads -- so what has been granted is
+// remembered per device, under a lock, in a table of the KERNEL's own: the static of a function template
+// over the kernel.  An error of the opt-in is returned without a launch, else the launch's.
+// The tile kernel's LDS depends on the launch: the table holds the size granted, and a larger one is granted again.
+template <auto Kernel>
+hipError_t launchTileKernel(dim3 grid, dim3 block, size_t lds, int dev, hipStream_t stream, const RasterParams &p)
+{
+    static size_t allowed[kMaxDevices] = {};
+    {
+        std::lock_guard<std::mutex> guard(attrMutex);
+        if (lds > allowed[dev]) {
+            const hipError_t e = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+            if (e != hipSuccess)
+                return e;
+            allowed[dev] = lds;
+        }
+    }
+    Kernel<<<grid, block, lds, stream>>>(p);
+    return hipGetLastError();
+}
+// The flat kernel's LDS is a constant of the instantiation: the table holds a flag.
+template <auto Kernel>
+hipError_t launchFlatKernel(dim3 grid, dim3 block, size_t flatLds, int dev, hipStream_t stream, const RasterParams &p)
+{
+    static bool allowed[kMaxDevices] = {};
+    {
+        std::lock_guard<std::mutex> guard(attrMutex);
+        if (!allowed[dev]) {
+            const hipError_t e = hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flatLds);
+            if (e != hipSuccess)
+                return e;
+            allowed[dev] = true;
+        }
+    }
+    Kernel<<<grid, block, flatLds, stream>>>(p);
+    return hipGetLastError();
+}
 }  // namespace
 
 size_t bvhLdsBytes(uint32_t passInst, bool textured, bool classify, uint32_t groupViews, uint32_t texCap)
@@ -2028,12 +2050,23 @@ size_t bvhLdsBytes(uint32_t passInst, bool textured, bool classify, uint32_t gro
     return ldsFor(passInst, textured, 64, 64, classify, groupViews, texCap);
 }
 
+// Which form a launch takes (host; first match wins).  `tile`: the tile kernel, which alone has PVM; else the flat one.
+static KernelForm bvhForm(const RasterParams &p, bool tile)
+{
+    if (p.normal && p.viewProj)         return KernelForm::NPV;   // normals over the per-view tables and the columns
+    if (p.normal)                       return KernelForm::N;     // normals over the uniform constants
+    if (tile && p.viewProj && p.instMat) return KernelForm::PVM;  // per-view tables and the material column
+    if (p.viewProj)                     return KernelForm::PV;    // per-view tables
+    return KernelForm::Uniform;
+}
+
 // Does a launch take the instantiations that classify the listed large triangles per strip (CLS)?  Not the per-view
 // normals form of a textured scene: its classifying instantiations want 130 registers and spilled; it
-// renders with the plain ones, to the same pixels.
+// renders with the plain ones, to the same pixels.  tileFormClassifies is the same rule at compile time: launchBvh
+// instantiates no CLS kernel of a form it excludes.
 static bool classifiesPerStrip(const RasterParams &p)
 {
-    return p.bvhTile == 0 && p.bvhClassify && !(p.normal && p.viewProj && p.anyTextured);
+    return p.bvhTile == 0 && p.bvhClassify && tileFormClassifies(bvhForm(p, true), p.anyTextured != 0);
 }
 
 BvhLaunchShape bvhLaunchShape(const RasterParams &p)
@@ -2100,41 +2133,23 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
             return hipErrorInvalidDevice;
         // (the normals forms of textured scenes: a dword per record slot behind everything else)
         const size_t flatLds = flatLdsBytes(tex) + ((p.normal && tex) ? (size_t)(kFlatTris + 2) * 4u : 0u);
-#define MRX_FLAT_K(K)                                                                           \
-    do {                                                                                       \
-        static bool allowed[kMaxDevices] = {};                                                 \
-        {                                                                                      \
-            std::lock_guard<std::mutex> guard(attrMutex);                                      \
-            if (!allowed[dev]) {                                                               \
-                const hipError_t e = hipFuncSetAttribute((const void *)K,                     \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)flatLds); \
-                if (e != hipSuccess)                                                           \
-                    return e;                                                                  \
-                allowed[dev] = true;                                                           \
-            }                                                                                  \
-        }                                                                                      \
-        K<<<grid, block, flatLds, stream>>>(p);                                                \
-    } while (0)
-#define MRX_FLAT_O(I, T, O) MRX_FLAT_K((bvhFlatKernel<I, T, O>))
-        // output selection: one instantiation per setting (kOutRGBD = the kernel as it always was); the per-view
-        // form (p.viewProj) has one instantiation that selects by pointer
+        // output selection: one instantiation per setting (kOutRGBD = the kernel as it always was); the forms
+        //  have one instantiation each that selects by pointer
+        const KernelForm form = bvhForm(p, false);
         const OutSel out = outSelOf(p.rgb, p.depth);
-#define MRX_FLAT(I, T)                                                                          \
-    do {                                                                                       \
-        if (p.normal && p.viewProj) MRX_FLAT_K((bvhFlatKernelNPV<I, T>));                      \
-        else if (p.normal)       MRX_FLAT_K((bvhFlatKernelN<I, T>));                           \
-        else if (p.viewProj)     MRX_FLAT_K((bvhFlatKernelPV<I, T>));                          \
-        else if (out == kOutDepth) MRX_FLAT_O(I, T, kOutDepth);                                \
-        else if (out == kOutRGB) MRX_FLAT_O(I, T, kOutRGB);                                    \
-        else                     MRX_FLAT_O(I, T, kOutRGBD);                                   \
-    } while (0)
-        if (ids == 2) { if (tex) MRX_FLAT(2, true); else MRX_FLAT(2, false); }
-        else if (ids == 1) { if (tex) MRX_FLAT(1, true); else MRX_FLAT(1, false); }
-        else { if (tex) MRX_FLAT(0, true); else MRX_FLAT(0, false); }
-#undef MRX_FLAT
-#undef MRX_FLAT_O
-#undef MRX_FLAT_K
-        return hipGetLastError();
+        return withValue<int, 2, 1, 0>(ids, [&](auto IDS) {
+            return withBool(tex, [&](auto TEX) {
+                constexpr int kIds = decltype(IDS)::value;
+                constexpr bool kTex = decltype(TEX)::value;
+                if (form != KernelForm::Uniform)
+                    return withValue<KernelForm, KernelForm::NPV, KernelForm::N, KernelForm::PV>(form, [&](auto F) {
+                        return launchFlatKernel<bvhFlatFormKernel<decltype(F)::value, kIds, kTex>>(grid, block, flatLds, dev, stream, p);
+                    });
+                return withValue<int, kOutDepth, kOutRGB, kOutRGBD>(out, [&](auto O) {
+                    return launchFlatKernel<bvhFlatKernel<kIds, kTex, decltype(O)::value>>(grid, block, flatLds, dev, stream, p);
+                });
+            });
+        });
     }
     // tile shape: p.bvhTile = 0 (64x64), 1 (64x32: TW 64, TH 32), 2 (32x32)
     const int tw = p.bvhTile == 2 ? 32 : 64, th = p.bvhTile == 0 ? 64 : 32;
@@ -2163,11 +2178,7 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
     const size_t lds = ldsFor(p.bvhPassInst, tex, tw, th, cls, groupViews, p.bvhTexCap) +
                        ((p.normal && tex) ? (size_t)p.bvhTexCap * 4u : 0u);
     const dim3 grid(items), block(kWave * (th / 8));
-    // The kernel needs more dynamic LDS than the 64 KB a launch may ask for by default.  The
-    // opt-in is a property of (function, device) -- a renderer per device in one process
-    // (mrx_config.device_ids, renderer_headless --gpus N) launches the same instantiation on
-    // several devices, from several host threads -- so what has been granted is remembered
-    // per device, under a lock.
+    // (the dynamic-LDS opt-in is per device: launchTileKernel)
     int dev = 0;
     {
         const hipError_t e = hipGetDevice(&dev);
@@ -2176,50 +2187,33 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
         if (dev < 0 || dev >= kMaxDevices)
             return hipErrorInvalidDevice;
     }
-#define MRX_BVH_K(K)                                                                            \
-    do {                                                                                       \
-        static size_t allowed[kMaxDevices] = {};                                               \
-        {                                                                                      \
-            std::lock_guard<std::mutex> guard(attrMutex);                                      \
-            if (lds > allowed[dev]) {                                                          \
-                const hipError_t e = hipFuncSetAttribute((const void *)K,                     \
-                                                         hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-                if (e != hipSuccess)                                                           \
-                    return e;                                                                  \
-                allowed[dev] = lds;                                                            \
-            }                                                                                  \
-        }                                                                                      \
-        K<<<grid, block, lds, stream>>>(p);                                                    \
-    } while (0)
-    // the per-view form (p.viewProj): the same shape, its per-view instantiation
-#define MRX_BVH(I, T, W, H, C, M)                                                               \
-    do {                                                                                       \
-        if (p.normal && p.viewProj) MRX_BVH_K((bvhTileKernelNPV<I, T, W, H, (C) && !(T), M>)); \
-        else if (p.normal) MRX_BVH_K((bvhTileKernelN<I, T, W, H, C, M>));                      \
-        else if (p.viewProj && p.instMat) MRX_BVH_K((bvhTileKernelPVM<I, T, W, H, C, M>));     \
-        else if (p.viewProj) MRX_BVH_K((bvhTileKernelPV<I, T, W, H, C, M>));                   \
-        else            MRX_BVH_K((bvhTileKernel<I, T, W, H, C, M>));                          \
-    } while (0)
-#define MRX_BVH_SHAPE(I, T)                                                                    \
-    do {                                                                                       \
-        if (p.bvhTile == 0 && multi && cls) MRX_BVH(I, T, 64, 64, true, true);                 \
-        else if (p.bvhTile == 0 && multi) MRX_BVH(I, T, 64, 64, false, true);                  \
-        else if (p.bvhTile == 0 && cls) MRX_BVH(I, T, 64, 64, true, false);                    \
-        else if (p.bvhTile == 0) MRX_BVH(I, T, 64, 64, false, false);                          \
-        else if (p.bvhTile == 1) MRX_BVH(I, T, 64, 32, false, false);                          \
-        else MRX_BVH(I, T, 32, 32, false, false);                                              \
-    } while (0)
-    if (ids == 2) {
-        if (tex) MRX_BVH_SHAPE(2, true); else MRX_BVH_SHAPE(2, false);
-    } else if (ids == 1) {
-        if (tex) MRX_BVH_SHAPE(1, true); else MRX_BVH_SHAPE(1, false);
-    } else {
-        if (tex) MRX_BVH_SHAPE(0, true); else MRX_BVH_SHAPE(0, false);
-    }
-#undef MRX_BVH_SHAPE
-#undef MRX_BVH
-#undef MRX_BVH_K
-    return hipGetLastError();
+    // Instantiation choice: the form (bvhForm), then ids x textured x tile shape.  The per-view normals form of a
+    // textured scene has no CLS instantiation (tileFormClassifies; `cls` is false for it: classifiesPerStrip).
+    const KernelForm form = bvhForm(p, true);
+    return withValue<int, 2, 1, 0>(ids, [&](auto IDS) {
+        return withBool(tex, [&](auto TEX) {
+            const auto launch = [&](auto TW, auto TH, auto CLS, auto MULTI) {
+                constexpr int kIds = decltype(IDS)::value, kTW = decltype(TW)::value, kTH = decltype(TH)::value;
+                constexpr bool kTex = decltype(TEX)::value, kCls = decltype(CLS)::value, kMulti = decltype(MULTI)::value;
+                if (form == KernelForm::Uniform)
+                    return launchTileKernel<bvhTileKernel<kIds, kTex, kTW, kTH, kCls, kMulti>>(grid, block, lds, dev, stream, p);
+                return withValue<KernelForm, KernelForm::NPV, KernelForm::N, KernelForm::PVM, KernelForm::PV>(form, [&](auto F) {
+                    constexpr KernelForm kForm = decltype(F)::value;
+                    return launchTileKernel<bvhTileFormKernel<kForm, kIds, kTex, kTW, kTH, kCls && tileFormClassifies(kForm, kTex), kMulti>>(
+                        grid, block, lds, dev, stream, p);
+                });
+            };
+            using W64 = std::integral_constant<int, 64>;
+            using W32 = std::integral_constant<int, 32>;
+            if (p.bvhTile == 0)
+                return withBool(multi, [&](auto MULTI) {
+                    return withBool(cls, [&](auto CLS) { return launch(W64 {}, W64 {}, CLS, MULTI); });
+                });
+            if (p.bvhTile == 1)
+                return launch(W64 {}, W32 {}, std::false_type {}, std::false_type {});
+            return launch(W32 {}, W32 {}, std::false_type {}, std::false_type {});
+        });
+    });
 }
 
 }  // namespace mrx

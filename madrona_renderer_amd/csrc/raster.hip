@@ -28,6 +28,9 @@ namespace mrx {
 namespace {
 
 constexpr int kWavesPerBlock = 4;
+// launch bounds of the brute and the chunked kernels, uniform and form alike (the second bound is waves per SIMD)
+constexpr int kBruteThreads = kWave * kWavesPerBlock;
+constexpr int kChunkedThreads = kWave * kWavesPerBlock, kChunkedWavesPerSimd = 3;
 constexpr int kChunk = 64;       // triangles set up per pass (one per lane)
 constexpr int kHot = 16;         // dwords: edges, depth plane, rgba, tex, seg, k
 constexpr int kBandRows = 16;    // a band is 64 x 16 pixels = 16 blocks of 8x8
@@ -318,34 +321,21 @@ __device__ __forceinline__ void bruteKernelBody(const RasterParams p)
 }
 
 template <bool IDS, bool MULTI, int OUT = kOutRGBD>
-__global__ __launch_bounds__(kWave *kWavesPerBlock)
+__global__ __launch_bounds__(kBruteThreads)
 void rasterBruteKernel(const RasterParams p)
 {
     bruteKernelBody<IDS, MULTI, OUT, false>(p);
 }
 
-// the per-view form (p.viewProj): one instantiation per id setting, output selection by pointer
-template <bool IDS, bool MULTI>
-__global__ __launch_bounds__(kWave *kWavesPerBlock)
-void rasterBruteKernelPV(const RasterParams p)
+// The form kernel (raster.hpp KernelForm; the bound does not depend on the form), output selection by pointer:
+// PV the per-view form (p.viewProj), N and NPV the normals forms (p.normal) over the uniform constants
+// and over the per-view tables (and the colour / material columns behind their null checks).
+template <KernelForm F, bool IDS, bool MULTI>
+__global__ __launch_bounds__(kBruteThreads)
+void rasterBruteFormKernel(const RasterParams p)
 {
-    bruteKernelBody<IDS, MULTI, kOutByPointer, true>(p);
-}
-
-// the normals forms (p.normal): N over the uniform constants, NPV over the per-view tables (and the
-// colour / material columns behind their null checks); output selection by pointer in both
-template <bool IDS, bool MULTI>
-__global__ __launch_bounds__(kWave *kWavesPerBlock)
-void rasterBruteKernelN(const RasterParams p)
-{
-    bruteKernelBody<IDS, MULTI, kOutByPointer, false, true>(p);
-}
-
-template <bool IDS, bool MULTI>
-__global__ __launch_bounds__(kWave *kWavesPerBlock)
-void rasterBruteKernelNPV(const RasterParams p)
-{
-    bruteKernelBody<IDS, MULTI, kOutByPointer, true, true>(p);
+    static_assert(F == KernelForm::PV || F == KernelForm::N || F == KernelForm::NPV, "the forms of this family");
+    bruteKernelBody<IDS, MULTI, kOutByPointer, formFlags(F).pv, formFlags(F).nrm>(p);
 }
 
 // Bits 0..15: the tile's 32x8 regions (bit 2*strip + half) the lane's triangle
@@ -654,33 +644,19 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
 }
 
 template <bool IDS>
-__global__ __launch_bounds__(kWave *kWavesPerBlock, 3)
+__global__ __launch_bounds__(kChunkedThreads, kChunkedWavesPerSimd)
 void rasterChunkedKernel(const RasterParams p)
 {
     chunkedKernelBody<IDS, false>(p);
 }
 
-// the per-view form (p.viewProj)
-template <bool IDS>
-__global__ __launch_bounds__(kWave *kWavesPerBlock, 3)
-void rasterChunkedKernelPV(const RasterParams p)
+// the form kernel: PV, N and NPV, as the brute kernel's
+template <KernelForm F, bool IDS>
+__global__ __launch_bounds__(kChunkedThreads, kChunkedWavesPerSimd)
+void rasterChunkedFormKernel(const RasterParams p)
 {
-    chunkedKernelBody<IDS, true>(p);
-}
-
-// the normals forms (p.normal), as the brute kernel's
-template <bool IDS>
-__global__ __launch_bounds__(kWave *kWavesPerBlock, 3)
-void rasterChunkedKernelN(const RasterParams p)
-{
-    chunkedKernelBody<IDS, false, true>(p);
-}
-
-template <bool IDS>
-__global__ __launch_bounds__(kWave *kWavesPerBlock, 3)
-void rasterChunkedKernelNPV(const RasterParams p)
-{
-    chunkedKernelBody<IDS, true, true>(p);
+    static_assert(F == KernelForm::PV || F == KernelForm::N || F == KernelForm::NPV, "the forms of this family");
+    chunkedKernelBody<IDS, formFlags(F).pv, formFlags(F).nrm>(p);
 }
 
 // ---------------------------------------------------------------------------
@@ -1385,14 +1361,35 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
 #undef MRX_STAMP
 }
 
+// Launch bounds of the group kernels, uniform and form, plain and FAST (FAST: slots = 16).  Block size:
+constexpr int groupThreads(bool tex) { return kWave * groupWaves(tex); }
+// The second bound, waves per SIMD.
+constexpr int groupWavesPerSimd(KernelForm f, int slots, bool tex)
+{
+    // textured (four waves per workgroup): four; 256-slot groups are LDS-limited to 3 per CU
+    if (tex)
+        return slots > 128 ? 3 : 4;
+    // The forms over the light table (PVL, PVLC, PVLM, NPV, L, LN): six waves per SIMD -- three
+    // workgroups of eight waves -- where the others have eight.  The set-up lanes span views, so the five words of the
+    // light are per lane, on top of the five of the projection: with them the set-up wants 68 - 69 registers, and held
+    // to the 64 of eight waves it spills five to fifteen of them to scratch wherever the loads are placed.
+    if (formFlags(f).lt)
+        return 6;
+    // The uniform normals form has six FROM 128 slots ON (>=, where the others below have >):
+    // held to the 64 registers of eight waves, its 128-slot instantiation with ids spilled 22 of them to scratch.
+    if (f == KernelForm::N)
+        return slots >= 128 ? 6 : 8;
+    // the uniform kernels, PV, C, M: eight, six with 256 slots
+    return slots > 128 ? 6 : 8;
+}
+
 // The two entry points of the body: the plain one (arguments = RasterParams, as every other kernel here) and the
 // FAST one with the preloaded header in front.
 // OUT: output selection (raster.hpp OutSel): kOutRGBD or kOutDepth fixed per instantiation; rgb only takes
 // kOutByPointer -- a runtime guard on the depth stores -- because a fixed rgb-only instantiation of the 128-slot
 // kernel spilled 20 VGPRs to scratch
 template <bool IDS, int SLOTS, bool TEX, int XMODE = 0, int OUT = kOutRGBD>
-// (the second bound is waves per SIMD; 256-slot groups are LDS-limited to 3 per CU)
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : (SLOTS > 128 ? 6 : 8))
+__global__ __launch_bounds__(groupThreads(TEX), groupWavesPerSimd(KernelForm::Uniform, SLOTS, TEX))
 void rasterGroupKernel(const RasterParams p)
 {
     groupKernelBody<IDS, SLOTS, TEX, XMODE, false, OUT>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
@@ -1400,7 +1397,7 @@ void rasterGroupKernel(const RasterParams p)
 
 // OUT: output selection (raster.hpp OutSel: kOutRGBD, kOutDepth or kOutRGB), fixed per instantiation
 template <bool IDS, bool TEX, int XMODE, int OUT>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 8)
+__global__ __launch_bounds__(groupThreads(TEX), groupWavesPerSimd(KernelForm::Uniform, 16, TEX))
 void rasterGroupKernelFast(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
                            const RasterParams p)
@@ -1409,190 +1406,75 @@ void rasterGroupKernelFast(const char *hPose, const char *hGeom, uint32_t hViews
                                                hFirst23, p);
 }
 
-// The per-view form (p.viewProj) of both entry points: XMODE 0 (the XCD phase trade and report are
-// left to the uniform form) and output selection by pointer, so that one instantiation per id / texture / slot setting
-// covers every batch.
-template <bool IDS, int SLOTS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : (SLOTS > 128 ? 6 : 8))
-void rasterGroupKernelPV(const RasterParams p)
+// The form kernels of both entry points (raster.hpp KernelForm, formFlags): XMODE 0 (the XCD phase
+// trade and report are left to the uniform kernels, or are run-time tests in the normals and label forms) and output
+// selection by pointer, so that one instantiation per id / texture / slot setting covers every batch of a form.
+// Instantiations of their own, so that a renderer without the tables, columns or outputs launches what it always did:
+//   PV, PVL     the per-view forms (p.viewProj, 4.11): PVL with the light table (p.lightTable, 4.12), so that batches
+//               whose projections alone differ keep PV
+//   C, PVLC     the colour forms (p.instColor, 4.13): C over the uniform projection and light of the kernel arguments,
+//               PVLC over both tables (batches whose projections alone differ take it too); a depth-only renderer has
+//               no colour form -- it never reads the column
+//   M, PVLM     the material forms (p.instMat, 4.14), as the colour forms are.  They read both columns -- a renderer
+//               with the material column has the colour column's slot, zero-filled where it has no colour column -- so
+//               two forms cover every renderer with this column
+//   N, NPV      the normals forms (p.normal, 4.15): N over the uniform projection and light, NPV over both tables; the
+//               colour and material columns behind null tests
+//   L, LN       the label forms (p.instLabel, S11, 4.16), without and with normals; IDS only.  They store ids (the
+//               segmask), read both tables -- a renderer with the label column always fills them -- and every other
+//               column behind a null test
+template <KernelForm F, bool IDS, int SLOTS, bool TEX>
+__global__ __launch_bounds__(groupThreads(TEX), groupWavesPerSimd(F, SLOTS, TEX))
+void rasterGroupFormKernel(const RasterParams p)
 {
-    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
+    constexpr FormFlags f = formFlags(F);
+    static_assert(F != KernelForm::Uniform && F != KernelForm::PVM && (IDS || !f.lab), "the forms of this family");
+    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, f.pv, f.lt, f.col, f.mat, f.nrm, f.lab>(
+        nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
 }
 
-template <bool IDS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 8)
-void rasterGroupKernelFastPV(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
-                             uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
-                             const RasterParams p)
-{
-    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, true>(hPose, hGeom, hViews, hInstances, hPool, hShape, hGroups, hPrefix,
-                                                           hFirst01, hFirst23, p);
-}
-
-// The per-view form with the light table (p.lightTable): instantiations of their own, so that batches
-// whose projections alone differ keep the kernels above.  Untextured: six waves per SIMD -- three workgroups of eight
-// waves -- where the others have eight.  The set-up lanes span views, so the five words of the light are per lane, on
-// top of the five of the projection: with them the set-up wants 68 - 69 registers, and held to the 64 of eight waves
-// it spills five to fifteen of them to scratch wherever the loads are placed.
-template <bool IDS, int SLOTS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : 6)
-void rasterGroupKernelPVL(const RasterParams p)
-{
-    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
-}
-
-template <bool IDS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 6)
-void rasterGroupKernelFastPVL(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
-                              uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
-                              const RasterParams p)
-{
-    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, true, true>(hPose, hGeom, hViews, hInstances, hPool, hShape, hGroups,
-                                                                 hPrefix, hFirst01, hFirst23, p);
-}
-
-// The colour forms (p.instColor), instantiations of their own so that a renderer without the column
-// launches what it always did: C over the uniform projection and light of the kernel arguments, PVLC over both tables
-// (batches whose projections alone differ take it too).  Output selection by pointer; a depth-only renderer has no
-// colour form -- it never reads the column.
-template <bool IDS, int SLOTS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : (SLOTS > 128 ? 6 : 8))
-void rasterGroupKernelC(const RasterParams p)
-{
-    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, false, false, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u,
-                                                                                 0u, p);
-}
-
-template <bool IDS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 8)
-void rasterGroupKernelFastC(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
-                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
-                            const RasterParams p)
-{
-    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, false, false, true>(hPose, hGeom, hViews, hInstances, hPool, hShape,
-                                                                             hGroups, hPrefix, hFirst01, hFirst23, p);
-}
-
-template <bool IDS, int SLOTS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : 6)
-void rasterGroupKernelPVLC(const RasterParams p)
-{
-    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, true, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u,
-                                                                               p);
-}
-
-template <bool IDS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 6)
-void rasterGroupKernelFastPVLC(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
+// (the argument list is the FAST entry's: ten header words, then RasterParams -- the body relies on their preload)
+template <KernelForm F, bool IDS, bool TEX>
+__global__ __launch_bounds__(groupThreads(TEX), groupWavesPerSimd(F, 16, TEX))
+void rasterGroupFormKernelFast(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
                                uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
                                const RasterParams p)
 {
-    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, true, true, true>(hPose, hGeom, hViews, hInstances, hPool, hShape,
-                                                                           hGroups, hPrefix, hFirst01, hFirst23, p);
+    constexpr FormFlags f = formFlags(F);
+    static_assert(F != KernelForm::Uniform && F != KernelForm::PVM && (IDS || !f.lab), "the forms of this family");
+    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, f.pv, f.lt, f.col, f.mat, f.nrm, f.lab>(
+        hPose, hGeom, hViews, hInstances, hPool, hShape, hGroups, hPrefix, hFirst01, hFirst23, p);
 }
 
-// The material forms (p.instMat), as the colour forms are: M over the uniform projection and light,
-// PVLM over both tables.  They read both columns -- a renderer with the material column has the colour column's slot,
-// zero-filled where it has no colour column -- so two forms cover every renderer with this column.
-template <bool IDS, int SLOTS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : (SLOTS > 128 ? 6 : 8))
-void rasterGroupKernelM(const RasterParams p)
+// ---- which form a launch takes (host; first match wins) ---------------------------------------------------------------
+// The brute and the chunked kernel:
+KernelForm tileForm(const RasterParams &p)
 {
-    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, false, false, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u,
-                                                                                       0u, 0u, p);
+    if (p.normal && p.viewProj) return KernelForm::NPV;   // normals over the per-view tables
+    if (p.normal)               return KernelForm::N;     // normals over the uniform constants
+    if (p.viewProj)             return KernelForm::PV;    // per-view tables (columns behind null checks)
+    return KernelForm::Uniform;
 }
-
-template <bool IDS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 8)
-void rasterGroupKernelFastM(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
-                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
-                            const RasterParams p)
+// The group kernel, both entries:
+KernelForm groupForm(const RasterParams &p)
 {
-    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, false, false, true, true>(hPose, hGeom, hViews, hInstances, hPool,
-                                                                                   hShape, hGroups, hPrefix, hFirst01, hFirst23, p);
-}
-
-template <bool IDS, int SLOTS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : 6)
-void rasterGroupKernelPVLM(const RasterParams p)
-{
-    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, true, true, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u,
-                                                                                     0u, p);
-}
-
-template <bool IDS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 6)
-void rasterGroupKernelFastPVLM(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
-                               uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
-                               const RasterParams p)
-{
-    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, true, true, true, true>(hPose, hGeom, hViews, hInstances, hPool, hShape,
-                                                                                 hGroups, hPrefix, hFirst01, hFirst23, p);
-}
-
-// The normals forms (p.normal), instantiations of their own so that a renderer without the output
-// launches what it always did: N over the uniform projection and light of the kernel arguments, NPV over both tables;
-// the colour and material columns behind null tests, output selection by pointer.  The per-view form keeps the six
-// waves per SIMD of the other forms over the light table; the uniform form has six from 128 slots on -- held to the 64
-// registers of eight waves, its 128-slot instantiation with ids spilled 22 of them to scratch.
-template <bool IDS, int SLOTS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : (SLOTS >= 128 ? 6 : 8))
-void rasterGroupKernelN(const RasterParams p)
-{
-    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, false, false, true, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u,
-                                                                                             0u, 0u, 0u, p);
-}
-
-template <bool IDS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 8)
-void rasterGroupKernelFastN(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
-                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
-                            const RasterParams p)
-{
-    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, false, false, true, true, true>(hPose, hGeom, hViews, hInstances, hPool,
-                                                                                         hShape, hGroups, hPrefix, hFirst01,
-                                                                                         hFirst23, p);
-}
-
-template <bool IDS, int SLOTS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : 6)
-void rasterGroupKernelNPV(const RasterParams p)
-{
-    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, true, true, true, true, true>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u,
-                                                                                           0u, 0u, 0u, p);
-}
-
-template <bool IDS, bool TEX>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 6)
-void rasterGroupKernelFastNPV(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
-                              uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
-                              const RasterParams p)
-{
-    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, true, true, true, true, true>(hPose, hGeom, hViews, hInstances, hPool,
-                                                                                       hShape, hGroups, hPrefix, hFirst01,
-                                                                                       hFirst23, p);
-}
-
-// The label forms (p.instLabel): one per family and normals setting.  They store ids (the
-// segmask), read both tables -- a renderer with the label column always fills them -- and every other column behind a
-// null test; six waves per SIMD, as the other forms over the light table have.
-template <int SLOTS, bool TEX, bool NRM>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? (SLOTS > 128 ? 3 : 4) : 6)
-void rasterGroupKernelL(const RasterParams p)
-{
-    groupKernelBody<true, SLOTS, TEX, 0, false, kOutByPointer, true, true, true, true, NRM, true>(nullptr, nullptr, 0u, 0u, 0u, 0u,
-                                                                                                 0u, 0u, 0u, 0u, p);
-}
-
-template <bool TEX, bool NRM>
-__global__ __launch_bounds__(kWave *groupWaves(TEX), TEX ? 4 : 6)
-void rasterGroupKernelFastL(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances, uint32_t hPool,
-                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
-                            const RasterParams p)
-{
-    groupKernelBody<true, 16, TEX, 0, true, kOutByPointer, true, true, true, true, NRM, true>(hPose, hGeom, hViews, hInstances,
-                                                                                             hPool, hShape, hGroups, hPrefix,
-                                                                                             hFirst01, hFirst23, p);
+    const bool pv = p.viewProj != nullptr;
+    // the label column of a segmask renderer (which always fills the tables): the label forms, with or without normals
+    if (p.instLabel && p.ids && pv)       return p.normal ? KernelForm::LN : KernelForm::L;
+    // the normals output: over the tables where they vary, else over the uniform constants
+    if (p.normal && pv && p.tablesVary)   return KernelForm::NPV;
+    if (p.normal)                         return KernelForm::N;
+    // the material column (and the colour column's slot), likewise
+    if (p.instMat && pv && p.tablesVary)  return KernelForm::PVLM;
+    if (p.instMat)                        return KernelForm::M;
+    // the colour column alone, likewise
+    if (p.instColor && pv && p.tablesVary) return KernelForm::PVLC;
+    if (p.instColor)                      return KernelForm::C;
+    // no column, no extra output: the tables, with the light where the worlds' lights differ
+    if (pv && p.lightTable)               return KernelForm::PVL;
+    if (pv)                               return KernelForm::PV;
+    // the uniform kernels, by XMODE and OUT
+    return KernelForm::Uniform;
 }
 
 }  // namespace
@@ -1606,66 +1488,41 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
     const dim3 block(kWave * kWavesPerBlock);
     const bool ids = p.ids != nullptr;
     const bool multi = maxWorldTris > (uint32_t)kChunk;       // brute variant: chunk loop
-    // per-view projection: the same kernel family, its per-view instantiation
-    const bool pv = p.viewProj != nullptr;
     const bool large = maxWorldTris > (uint32_t)kGroupSlotsMax;
     if (variant == kVariantBrute) {
         // v1 reference: one wave per tile, every triangle at every pixel
         if (entry) *entry = kEntryBrute;
         const dim3 grid((items + kWavesPerBlock - 1) / kWavesPerBlock);
-#define MRX_BRUTE(O)                                                                     \
-    do {                                                                                 \
-        if (ids) {                                                                       \
-            if (multi) rasterBruteKernel<true, true, O><<<grid, block, 0, stream>>>(p);   \
-            else       rasterBruteKernel<true, false, O><<<grid, block, 0, stream>>>(p);  \
-        } else {                                                                         \
-            if (multi) rasterBruteKernel<false, true, O><<<grid, block, 0, stream>>>(p);  \
-            else       rasterBruteKernel<false, false, O><<<grid, block, 0, stream>>>(p); \
-        }                                                                                \
-    } while (0)
+        const KernelForm form = tileForm(p);
         const OutSel out = outSelOf(p.rgb, p.depth);
-#define MRX_BRUTE_FORM(K)                                                                \
-    do {                                                                                 \
-        if (ids) {                                                                       \
-            if (multi) K<true, true><<<grid, block, 0, stream>>>(p);                      \
-            else       K<true, false><<<grid, block, 0, stream>>>(p);                     \
-        } else {                                                                         \
-            if (multi) K<false, true><<<grid, block, 0, stream>>>(p);                     \
-            else       K<false, false><<<grid, block, 0, stream>>>(p);                    \
-        }                                                                                \
-    } while (0)
-        if (p.normal && pv) MRX_BRUTE_FORM(rasterBruteKernelNPV);
-        else if (p.normal)  MRX_BRUTE_FORM(rasterBruteKernelN);
-        else if (pv) {
-            if (ids) {
-                if (multi) rasterBruteKernelPV<true, true><<<grid, block, 0, stream>>>(p);
-                else       rasterBruteKernelPV<true, false><<<grid, block, 0, stream>>>(p);
-            } else {
-                if (multi) rasterBruteKernelPV<false, true><<<grid, block, 0, stream>>>(p);
-                else       rasterBruteKernelPV<false, false><<<grid, block, 0, stream>>>(p);
-            }
-        }
-        else if (out == kOutDepth) MRX_BRUTE(kOutDepth);
-        else if (out == kOutRGB) MRX_BRUTE(kOutRGB);
-        else                     MRX_BRUTE(kOutRGBD);
-#undef MRX_BRUTE
-#undef MRX_BRUTE_FORM
+        const auto byIdsMulti = [&](auto f) {
+            withBool(ids, [&](auto IDS) { withBool(multi, [&](auto MULTI) { f(IDS, MULTI); }); });
+        };
+        if (form != KernelForm::Uniform)
+            withValue<KernelForm, KernelForm::NPV, KernelForm::N, KernelForm::PV>(form, [&](auto F) {
+                byIdsMulti([&](auto IDS, auto MULTI) {
+                    rasterBruteFormKernel<decltype(F)::value, decltype(IDS)::value, decltype(MULTI)::value><<<grid, block, 0, stream>>>(p);
+                });
+            });
+        else
+            withValue<int, kOutDepth, kOutRGB, kOutRGBD>(out, [&](auto O) {
+                byIdsMulti([&](auto IDS, auto MULTI) {
+                    rasterBruteKernel<decltype(IDS)::value, decltype(MULTI)::value, decltype(O)::value><<<grid, block, 0, stream>>>(p);
+                });
+            });
     } else if (large) {
         // more triangles per world than the group kernel holds: one workgroup per tile
         if (entry) *entry = kEntryChunked;
-        if (p.normal && pv) {
-            if (ids) rasterChunkedKernelNPV<true><<<dim3(items), block, 0, stream>>>(p);
-            else     rasterChunkedKernelNPV<false><<<dim3(items), block, 0, stream>>>(p);
-        } else if (p.normal) {
-            if (ids) rasterChunkedKernelN<true><<<dim3(items), block, 0, stream>>>(p);
-            else     rasterChunkedKernelN<false><<<dim3(items), block, 0, stream>>>(p);
-        } else if (pv) {
-            if (ids) rasterChunkedKernelPV<true><<<dim3(items), block, 0, stream>>>(p);
-            else     rasterChunkedKernelPV<false><<<dim3(items), block, 0, stream>>>(p);
-        } else {
-            if (ids) rasterChunkedKernel<true><<<dim3(items), block, 0, stream>>>(p);
-            else     rasterChunkedKernel<false><<<dim3(items), block, 0, stream>>>(p);
-        }
+        const KernelForm form = tileForm(p);
+        withBool(ids, [&](auto IDS) {
+            constexpr bool kIds = decltype(IDS)::value;
+            if (form != KernelForm::Uniform)
+                withValue<KernelForm, KernelForm::PV, KernelForm::N, KernelForm::NPV>(form, [&](auto F) {
+                    rasterChunkedFormKernel<decltype(F)::value, kIds><<<dim3(items), block, 0, stream>>>(p);
+                });
+            else
+                rasterChunkedKernel<kIds><<<dim3(items), block, 0, stream>>>(p);
+        });
     } else {
         // triangle slots per view: the smallest of 16 ... 256 that holds a world
         int slots = 16;
@@ -1755,96 +1612,59 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
             h.first01 = p.uniFirstTri[0] | (p.uniFirstTri[1] << 16);
             h.first23 = p.uniFirstTri[2] | (p.uniFirstTri[3] << 16);
         }
-#define MRX_GROUP_ARGS h.pose, h.geom, h.views, h.instances, h.poolTris, h.shape, h.groups, h.prefix, h.first01, h.first23, q
-// (the forms over tables and / or colours: FK<IDS, TEX> the FAST entry, K<IDS, S, TEX> the plain one)
-#define MRX_GROUP_FORM(S, FK, K)                                               \
-    do {                                                                       \
-        if (fast && S == 16) {                                                 \
-            if (ids) { if (p.anyTextured) FK<true, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);    \
-                       else FK<true, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }               \
-            else     { if (p.anyTextured) FK<false, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
-                       else FK<false, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }              \
-        } else if (ids) {                                                      \
-            if (p.anyTextured) K<true, S, true><<<grid, gblock, 0, stream>>>(q);                          \
-            else               K<true, S, false><<<grid, gblock, 0, stream>>>(q);                         \
-        } else {                                                               \
-            if (p.anyTextured) K<false, S, true><<<grid, gblock, 0, stream>>>(q);                         \
-            else               K<false, S, false><<<grid, gblock, 0, stream>>>(q);                        \
-        }                                                                      \
-    } while (0)
-#define MRX_GROUP_O(S, X, O, OP)                                               \
-    do {                                                                       \
-        if (p.instLabel && ids && pv) {                                        \
-            if (fast && S == 16) {                                             \
-                if (p.normal) { if (p.anyTextured) rasterGroupKernelFastL<true, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);    \
-                                else rasterGroupKernelFastL<false, true><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }               \
-                else          { if (p.anyTextured) rasterGroupKernelFastL<true, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
-                                else rasterGroupKernelFastL<false, false><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); }              \
-            } else if (p.normal) {                                             \
-                if (p.anyTextured) rasterGroupKernelL<S, true, true><<<grid, gblock, 0, stream>>>(q);     \
-                else               rasterGroupKernelL<S, false, true><<<grid, gblock, 0, stream>>>(q);    \
-            } else {                                                           \
-                if (p.anyTextured) rasterGroupKernelL<S, true, false><<<grid, gblock, 0, stream>>>(q);    \
-                else               rasterGroupKernelL<S, false, false><<<grid, gblock, 0, stream>>>(q);   \
-            }                                                                  \
-        } else if (p.normal && pv && p.tablesVary) {                                  \
-            MRX_GROUP_FORM(S, rasterGroupKernelFastNPV, rasterGroupKernelNPV); \
-        } else if (p.normal) {                                                 \
-            MRX_GROUP_FORM(S, rasterGroupKernelFastN, rasterGroupKernelN);     \
-        } else if (p.instMat && pv && p.tablesVary) {                          \
-            MRX_GROUP_FORM(S, rasterGroupKernelFastPVLM, rasterGroupKernelPVLM);                          \
-        } else if (p.instMat) {                                                \
-            MRX_GROUP_FORM(S, rasterGroupKernelFastM, rasterGroupKernelM);     \
-        } else if (p.instColor && pv && p.tablesVary) {                        \
-            MRX_GROUP_FORM(S, rasterGroupKernelFastPVLC, rasterGroupKernelPVLC);                          \
-        } else if (p.instColor) {                                              \
-            MRX_GROUP_FORM(S, rasterGroupKernelFastC, rasterGroupKernelC);     \
-        } else if (pv && p.lightTable) {                                       \
-            MRX_GROUP_FORM(S, rasterGroupKernelFastPVL, rasterGroupKernelPVL); \
-        } else if (pv) {                                                       \
-            MRX_GROUP_FORM(S, rasterGroupKernelFastPV, rasterGroupKernelPV);   \
-        } else if (fast && S == 16) {                                          \
-            if (p.anyTextured) {                                               \
-                if (ids) rasterGroupKernelFast<true, true, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);   \
-                else     rasterGroupKernelFast<false, true, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);  \
-            } else {                                                           \
-                if (ids) rasterGroupKernelFast<true, false, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS);  \
-                else     rasterGroupKernelFast<false, false, X, O><<<grid, gblock, 0, stream>>>(MRX_GROUP_ARGS); \
-            }                                                                  \
-        } else if (p.anyTextured) {                                            \
-            if (ids) rasterGroupKernel<true, S, true, X, OP><<<grid, gblock, 0, stream>>>(q);   \
-            else     rasterGroupKernel<false, S, true, X, OP><<<grid, gblock, 0, stream>>>(q);  \
-        } else {                                                               \
-            if (ids) rasterGroupKernel<true, S, false, X, OP><<<grid, gblock, 0, stream>>>(q);  \
-            else     rasterGroupKernel<false, S, false, X, OP><<<grid, gblock, 0, stream>>>(q); \
-        }                                                                      \
-    } while (0)
+        // Instantiation choice: the form (groupForm), then slots x ids x textured; the uniform kernels by XMODE and OUT
+        // too.  FAST and XMODE 1..3 exist with 16 slots only, the label forms with ids only.
+        const KernelForm form = groupForm(p);
+        const bool tex = p.anyTextured != 0;
         // output selection: one instantiation per setting (kOutRGBD = the kernels as they always were)
         const OutSel out = outSelOf(p.rgb, p.depth);
-#define MRX_GROUP_X(S, X)                                                      \
-    do {                                                                       \
-        if (out == kOutDepth)    MRX_GROUP_O(S, X, kOutDepth, kOutDepth);      \
-        else if (out == kOutRGB) MRX_GROUP_O(S, X, kOutRGB, kOutByPointer);    \
-        else                     MRX_GROUP_O(S, X, kOutRGBD, kOutRGBD);        \
-    } while (0)
-#define MRX_GROUP(S) MRX_GROUP_X(S, 0)
-        if (slots == 16) {
-            // XCD phase: trade places within the pairs on an odd start, ask for a report now and then
-            const int xmode = ((q.xcdSkew && (p.xcdPhase & 1u)) ? 1 : 0) | (p.xccReport ? 2 : 0);
-            if (xmode == 0) MRX_GROUP_X(16, 0);
-            else if (xmode == 1) MRX_GROUP_X(16, 1);
-            else if (xmode == 2) MRX_GROUP_X(16, 2);
-            else MRX_GROUP_X(16, 3);
-        }
-        else if (slots == 32) MRX_GROUP(32);
-        else if (slots == 64) MRX_GROUP(64);
-        else if (slots == 128) MRX_GROUP(128);
-        else MRX_GROUP(256);
-#undef MRX_GROUP_ARGS
-#undef MRX_GROUP_X
-#undef MRX_GROUP_O
-#undef MRX_GROUP_FORM
-#undef MRX_GROUP
+        // XCD phase: trade places within the pairs on an odd start, ask for a report now and then
+        const int xmode = slots != 16 ? 0 : ((q.xcdSkew && (p.xcdPhase & 1u)) ? 1 : 0) | (p.xccReport ? 2 : 0);
+        const auto byTexIds = [&](auto f) {
+            withBool(tex, [&](auto TEX) { withBool(ids, [&](auto IDS) { f(IDS, TEX); }); });
+        };
+        const auto launchFast = [&](auto kernel) {        // the FAST entry: the header in front
+            kernel<<<grid, gblock, 0, stream>>>(h.pose, h.geom, h.views, h.instances, h.poolTris, h.shape, h.groups, h.prefix,
+                                                h.first01, h.first23, q);
+        };
+        const auto launchPlain = [&](auto kernel) { kernel<<<grid, gblock, 0, stream>>>(q); };
+        withValue<int, 16, 32, 64, 128, 256>(slots, [&](auto S) {
+            constexpr int kSlots = decltype(S)::value;
+            if (form != KernelForm::Uniform) {
+                withValue<KernelForm, KernelForm::PV, KernelForm::PVL, KernelForm::C, KernelForm::PVLC, KernelForm::M,
+                          KernelForm::PVLM, KernelForm::N, KernelForm::NPV, KernelForm::L, KernelForm::LN>(form, [&](auto F) {
+                    constexpr KernelForm kForm = decltype(F)::value;
+                    byTexIds([&](auto IDS, auto TEX) {
+                        constexpr bool kIds = decltype(IDS)::value, kTex = decltype(TEX)::value;
+                        if constexpr (kIds || !formFlags(kForm).lab) {   // (groupForm: labels with ids only)
+                            if constexpr (kSlots == 16) {
+                                if (fast)
+                                    return launchFast(rasterGroupFormKernelFast<kForm, kIds, kTex>);
+                            }
+                            launchPlain(rasterGroupFormKernel<kForm, kIds, kSlots, kTex>);
+                        }
+                    });
+                });
+                return;
+            }
+            withValue<int, 0, 1, 2, 3>(xmode, [&](auto X) {
+                constexpr int kX = decltype(X)::value;
+                if constexpr (kX == 0 || kSlots == 16)
+                    withValue<int, kOutDepth, kOutRGB, kOutRGBD>(out, [&](auto O) {
+                        // rgb only: the FAST entry has its fixed instantiation, the plain one selects by pointer
+                        constexpr int kO = decltype(O)::value, kOP = kO == kOutRGB ? kOutByPointer : kO;
+                        if constexpr (kSlots == 16) {
+                            if (fast)
+                                return byTexIds([&](auto IDS, auto TEX) {
+                                    launchFast(rasterGroupKernelFast<decltype(IDS)::value, decltype(TEX)::value, kX, kO>);
+                                });
+                        }
+                        byTexIds([&](auto IDS, auto TEX) {
+                            launchPlain(rasterGroupKernel<decltype(IDS)::value, kSlots, decltype(TEX)::value, kX, kOP>);
+                        });
+                    });
+            });
+        });
     }
     return hipGetLastError();
 }

@@ -3,6 +3,7 @@
 #pragma once
 
 #include <cstdint>
+#include <type_traits>
 #include <hip/hip_runtime_api.h>
 
 namespace mrx {
@@ -311,6 +312,60 @@ enum OutSel : int {
 inline OutSel outSelOf(const void *rgb, const void *depth)
 {
     return !rgb ? kOutDepth : !depth ? kOutRGB : kOutRGBD;
+}
+
+// Kernel forms.  Beside its uniform kernel every kernel family has ONE form kernel, a template over
+// this enum: which tables and columns of RasterParams the instantiation reads, which extra outputs it stores.  The
+// launchers pick the form with one host function per family (groupForm in raster.hip, bvhForm in bvh.hip).  Not every
+// family has every form: the brute, chunked and flat kernels have PV, N and NPV, the BVH tile kernel those and PVM.
+enum class KernelForm : int {
+    Uniform = 0,   // the uniform kernels themselves (projection and light from the kernel arguments, no column)
+    PV, PVL, C, PVLC, M, PVLM, N, NPV, L, LN,
+    PVM,           // BVH tile kernel only: per-view tables and the material column
+};
+struct FormFlags {
+    bool pv;    // per-view projection table (viewProj)
+    bool lt;    // per-view light table (viewLight, 4.12)
+    bool col;   // colour column (instColor, 4.13)
+    bool mat;   // material column (instMat, 4.14)
+    bool nrm;   // normals output (normal, 4.15)
+    bool lab;   // label column (instLabel, 4.16)
+};
+constexpr FormFlags formFlags(KernelForm f)
+{
+    switch (f) {                                     //  pv     lt     col    mat    nrm    lab
+    case KernelForm::PV:   return FormFlags { true,  false, false, false, false, false };
+    case KernelForm::PVL:  return FormFlags { true,  true,  false, false, false, false };
+    case KernelForm::C:    return FormFlags { false, false, true,  false, false, false };
+    case KernelForm::PVLC: return FormFlags { true,  true,  true,  false, false, false };
+    case KernelForm::M:    return FormFlags { false, false, true,  true,  false, false };
+    case KernelForm::PVLM: return FormFlags { true,  true,  true,  true,  false, false };
+    case KernelForm::N:    return FormFlags { false, false, true,  true,  true,  false };
+    case KernelForm::NPV:  return FormFlags { true,  true,  true,  true,  true,  false };
+    case KernelForm::L:    return FormFlags { true,  true,  true,  true,  false, true };
+    case KernelForm::LN:   return FormFlags { true,  true,  true,  true,  true,  true };
+    case KernelForm::PVM:  return FormFlags { true,  false, false, true,  false, false };
+    default:               return FormFlags { false, false, false, false, false, false };
+    }
+}
+
+// ---- run-time value -> template argument (the launchers' instantiation choice) --------------------------------------
+// withBool(b, f) calls f(std::true_type) or f(std::false_type); withValue<T, V0, V1, ...>(v, f) calls
+// f(std::integral_constant<T, Vi>) for the first Vi equal to v, and for the LAST value of the list when none is (the
+// list's "otherwise").  f is a generic lambda that reads the constant as decltype(arg)::value; `if constexpr` on such
+// constants inside it keeps combinations nothing launches from being instantiated.  Both return what f returns.
+template <typename F>
+inline auto withBool(bool b, F &&f)
+{
+    return b ? f(std::true_type {}) : f(std::false_type {});
+}
+template <typename T, T V0, T... Vs, typename F>
+inline auto withValue(T v, F &&f)
+{
+    if constexpr (sizeof...(Vs) == 0)
+        return f(std::integral_constant<T, V0> {});
+    else
+        return v == V0 ? f(std::integral_constant<T, V0> {}) : withValue<T, Vs...>(v, f);
 }
 
 // Kernel variants (mrx_config.kernel_variant).

@@ -5,6 +5,7 @@ reports it (-Rpass-analysis=kernel-resource-usage) under the product's flags.  N
   python scripts/kernel_resources.py madrona_renderer_amd/csrc/bvh.hip [extra hipcc flags]
   python scripts/kernel_resources.py --write      # profiles/kernel_resources_latest.txt, both sources
 """
+import os
 import re
 import subprocess
 import sys
@@ -44,14 +45,23 @@ def line(k):
 
 SOURCES = ["madrona_renderer_amd/csrc/raster.hip", "madrona_renderer_amd/csrc/bvh.hip"]
 
+
+def form_legend(root):
+    """number -> name of raster.hpp's KernelForm: the form kernels' rows show it as (mrx::KernelForm)N"""
+    text = open(os.path.join(root, "madrona_renderer_amd", "csrc", "raster.hpp")).read()
+    body = re.sub(r"//[^\n]*", "", re.search(r"enum class KernelForm : int \{(.*?)\};", text, re.S).group(1))
+    names = [n.split("=")[0].strip() for n in body.split(",") if n.strip()]
+    return ", ".join("%d %s" % (i, n) for i, n in enumerate(names))
+
+
 if __name__ == "__main__":
     if sys.argv[1:2] == ["--write"]:
         # the committed table tests/test_kernel_resources.py compares HEAD with
-        import os
         root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
         with open(os.path.join(root, "profiles", "kernel_resources_latest.txt"), "w") as f:
             f.write("## hipcc -Rpass-analysis=kernel-resource-usage under the product's flags (scripts/kernel_resources.py --write);\n"
-                    "## tests/test_kernel_resources.py fails when this table is not what HEAD compiles to\n")
+                    "## tests/test_kernel_resources.py fails when this table is not what HEAD compiles to\n"
+                    "## (mrx::KernelForm)N in a form kernel's row: %s\n" % form_legend(root))
             for src in SOURCES:
                 f.write("# %s\n" % src)
                 for k in resources(os.path.join(root, src)):

@@ -116,6 +116,20 @@ def test_colours_mixed_lights_and_mixed_projections_together(native, case):
     _assert_colours_decided_pixels(base, ref, views, lights, projs)
 
 
+@pytest.mark.parametrize("tables", [False, True], ids=["uniform", "tables"])
+def test_colours_through_the_plain_entry_at_16_slots(native, monkeypatch, tables):
+    # both colour forms (over the uniform constants, over the tables) behind the plain entry of a 16-slot world (the
+    # FAST entry switched off): two one-tile views
+    monkeypatch.setenv("MRX_GROUP_FAST", "0")
+    base = scenes.synthetic_scene(2)
+    colors = co.mixed(len(base.instances))
+    lights = lo.mixed(base.num_worlds, shift=2) if tables else None
+    projs = po.mixed(len(base.cameras)) if tables else None
+    r = _make(_with(base, colors, lights, projs))
+    assert r.raster_entry() == "group"
+    _check(r, co.render(base, colors, lights, projs, want_ids=True), False, (0, base.num_views))
+
+
 def test_colours_beside_projections_alone_and_a_uniform_light(native):
     # projections differ, lights do not: the group kernels' table form with colours
     base = scenes.synthetic_scene(256, textured=True)

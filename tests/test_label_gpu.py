@@ -283,6 +283,23 @@ def test_the_label_forms_beside_every_column_in_the_other_families(native, oracl
         assert torch.equal(t == -1, p == -1)               # the same pixels covered as in the object-id segmask
 
 
+@pytest.mark.parametrize("normals", [False, True], ids=["labels", "labels-normals"])
+def test_labels_through_the_plain_entry_at_16_slots(native, oracle_mod, monkeypatch, normals):
+    # both label forms (without and with the normals output) behind the plain entry of a 16-slot world (the FAST entry
+    # switched off): two one-tile views
+    monkeypatch.setenv("MRX_GROUP_FAST", "0")
+    base = scenes.synthetic_scene(2)
+    labels = lb.mixed(len(base.instances))
+    r = _make(_with(base, labels, normals=normals), visibility=False)
+    assert r.raster_entry() == "group"
+    views = (0, base.num_views)
+    fs = oracle_mod.FlatScene(base)
+    ref = lo.render(base, None, None, views[0], views[1], want_ids=True)
+    _check(r, fs, lb.expand(base, labels), ref, views)
+    if normals:
+        assert np.array_equal(r.normal_tensor().to_torch().cpu().numpy(), no.normals(fs, ref["tri_id"], views[0], views[1]))
+
+
 @pytest.mark.parametrize("outputs", ["Depth", "RGB"])
 @pytest.mark.parametrize("case", ["group-fast", "group", "bvh-tile", "flat"])
 def test_labels_in_depth_only_and_rgb_only_renderers(native, oracle_mod, case, outputs):

@@ -69,6 +69,16 @@ def test_mixed_lights_match_the_oracle(native, case):
     _assert_light_decided_pixels(base, ref_ids, rt)
 
 
+def test_mixed_lights_through_the_plain_entry_at_16_slots(native, monkeypatch):
+    # the light-table form behind the plain entry of a 16-slot world (the FAST entry switched off): two one-tile views
+    monkeypatch.setenv("MRX_GROUP_FAST", "0")
+    base = scenes.synthetic_scene(2)
+    lights = lo.mixed(base.num_worlds)
+    r = _make(_with(base, lights))
+    assert r.raster_entry() == "group"
+    _check(r, base, lights)
+
+
 @pytest.mark.parametrize("outputs", ["RGBD", "Depth"])
 def test_raytracer_flat_kernel_with_mixed_lights(native, outputs):
     # BASELINE configs[4]'s shape (4096 views of 256x256, Raytracer mode): the BVH path's flat kernel; a slice of the

@@ -178,6 +178,21 @@ def test_materials_colours_mixed_lights_and_mixed_projections_together(native, c
     _assert_materials_decided_pixels(base, ref, views, lights, projs, colors, share=0.1)
 
 
+@pytest.mark.parametrize("tables", [False, True], ids=["uniform", "tables"])
+def test_materials_through_the_plain_entry_at_16_slots(native, monkeypatch, tables):
+    # both material forms (over the uniform constants, over the tables and beside colours) behind the plain entry of a
+    # 16-slot world (the FAST entry switched off): two one-tile views
+    monkeypatch.setenv("MRX_GROUP_FAST", "0")
+    base = mo.with_table(scenes.synthetic_scene(2))
+    ids = mo.mixed(len(base.instances), mo.num_materials(base))
+    colors = np.roll(co.mixed(len(base.instances), seed=3), 2, axis=0) if tables else None
+    lights = lo.mixed(base.num_worlds, shift=2) if tables else None
+    projs = po.mixed(len(base.cameras)) if tables else None
+    r = _make(_with(base, ids, colors, lights, projs))
+    assert r.raster_entry() == "group"
+    _check(r, mo.render(base, ids, colors, lights, projs, want_ids=True), False, (0, base.num_views))
+
+
 def test_materials_alone_over_uniform_tables_and_beside_colours(native):
     # no lights, no projections: the group kernels' uniform material form, with and without a colour column
     base = mo.with_table(scenes.synthetic_scene(256, textured=True))

@@ -194,6 +194,27 @@ def test_normals_do_not_depend_on_projection_light_colour_or_material(native, or
     assert torch.equal(r.normal_tensor().to_torch(), q.normal_tensor().to_torch())
 
 
+@pytest.mark.parametrize("tables", [False, True], ids=["uniform", "tables"])
+def test_normals_through_the_plain_entry_at_16_slots(native, oracle_mod, monkeypatch, tables):
+    # both normals forms (over the uniform constants, over the tables) behind the plain entry of a 16-slot world (the
+    # FAST entry switched off): two one-tile views
+    monkeypatch.setenv("MRX_GROUP_FAST", "0")
+    base = scenes.synthetic_scene(2)
+    lights = lo.mixed(base.num_worlds) if tables else None
+    projs = po.mixed(len(base.cameras)) if tables else None
+    d = _on(base)
+    if tables:
+        d.world_lights, d.camera_projections = list(lights), list(projs)
+    r = _make(d)
+    assert r.raster_entry() == "group"
+    views = (0, base.num_views)
+    ref = lo.render(base, lights, projs, views[0], views[1], want_ids=True)
+    want = no.normals(oracle_mod.FlatScene(base), ref["tri_id"], views[0], views[1])
+    assert int((_normals(r, views) != want).any(axis=-1).sum()) == 0
+    others = _fetch_cut(r, False, views)
+    assert_parity(others, {k: ref[k][views[0]:views[1]] for k in others})
+
+
 def test_textured_tile_kernel_with_per_strip_classification(native, oracle_mod, monkeypatch):
     """A textured world on the BVH tile kernel with the per-strip classification of large triangles on (as scenes with
     BLAS meshes have it).  Over the uniform constants the normals form classifies like the plain kernel; over per-view

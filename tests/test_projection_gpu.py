@@ -110,6 +110,17 @@ def test_mixed_projections_under_output_selection(native, outputs):
     _check(r, desc, visibility=False, outputs=None if outputs == "RGBD" else outputs)
 
 
+def test_mixed_projections_through_the_plain_entry_at_16_slots(native, monkeypatch):
+    # the per-view form behind the plain entry of a 16-slot world, which a batch reaches only with the FAST entry
+    # switched off: two one-tile views
+    monkeypatch.setenv("MRX_GROUP_FAST", "0")
+    base = scenes.synthetic_scene(2)
+    desc = _with(base, po.mixed(len(base.cameras)))
+    r = _make(desc)
+    assert r.raster_entry() == "group"
+    _check(r, desc)
+
+
 @pytest.mark.parametrize("outputs", ["RGBD", "Depth"])
 def test_raytracer_flat_kernel_with_mixed_projections(native, outputs):
     # BASELINE configs[4]'s shape (4096 views of 256x256, Raytracer mode): the BVH path's flat kernel; a slice of the
