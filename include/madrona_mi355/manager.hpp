@@ -111,6 +111,10 @@ public:
         // column segmaskTensor() exists in Rasterizer mode too and holds the label of the row that wins each pixel.
         const int32_t *instanceLabels = nullptr;
         bool instanceLabelColumn = false;
+        // Supersampled antialiasing (MRX_FLAG_SUPERSAMPLE_MASK): 1 ... 4; with s > 1 every view is rendered at s times
+        // the width and height and resolved to the configured size -- rgb box-filtered, depth, normals and the ids
+        // tensor point-sampled -- so every tensor getter keeps its shape.
+        uint32_t supersample = 1;
     };
     // the label that stands for the id of the object a row is bound to (MRX_LABEL_OBJECT)
     static constexpr int32_t kLabelObject = INT32_MIN;
@@ -158,6 +162,11 @@ public:
     // i32 [instances], mutable: the label of every row, kLabelObject = the id of its bound object; what segmaskTensor()
     // holds on the pixels the row wins (needs Config::instanceLabels or instanceLabelColumn)
     madrona::py::Tensor instanceLabelTensor(uint32_t shard = 0) const;
+    // supersampling: the factor; the s * W x s * H tensor the render writes for an output id (MRX_BUF_RGB, _DEPTH,
+    // _SEGMASK, _VISIBILITY, _NORMAL; fatal at factor 1 or on an output that is not rendered); the resolve stage alone
+    uint32_t supersample() const;
+    madrona::py::Tensor sampleTensor(int which, uint32_t shard = 0) const;
+    void resolve();
     // binds every row to the (non-negative) object id its ObjectID column now holds: a spare
     // row gets its geometry, an existing row swaps it (makeEntityRenderable at run time,
     // src/sim.inl:5-8); waits for the device

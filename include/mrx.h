@@ -142,6 +142,17 @@ enum {
      * the column exists and is mutable, MRX_BUF_SEGMASK is refused. */
     MRX_FLAG_INSTANCE_LABELS = 1u << 7
 };
+/* supersampled antialiasing: a two-bit field of the flags holds the factor,
+ * s = 1 + ((flags >> MRX_FLAG_SUPERSAMPLE_SHIFT) & 3), so s = 1 ... 4 and MRX_FLAG_SUPERSAMPLE(s) sets it.  With s > 1
+ * the render runs exactly as a renderer of s * view_width x s * view_height views would (Raytracer mode: s * res
+ * square) -- the sample tensors, mrx_sample_buffer -- and a resolve stage behind it on the same stream writes the
+ * view_width x view_height tensors every other entry point sees: rgb box-filtered per byte, (sum + s*s/2) / (s*s);
+ * depth, normals and the ids tensor unfiltered, each native pixel (x, y) taking sample (s*x + s/2, s*y + s/2).
+ * s * view_width or s * view_height above 16384: MRX_E_INVALID.  With the field zero nothing is allocated and every
+ * launch is the one it always was. */
+#define MRX_FLAG_SUPERSAMPLE_SHIFT 8
+#define MRX_FLAG_SUPERSAMPLE_MASK (3u << MRX_FLAG_SUPERSAMPLE_SHIFT)
+#define MRX_FLAG_SUPERSAMPLE(s) ((((uint32_t)(s) - 1u) & 3u) << MRX_FLAG_SUPERSAMPLE_SHIFT)
 
 /* the label that stands for "the id of the object the row is bound to" (INT32_MIN): what the column starts at */
 #define MRX_LABEL_OBJECT ((int32_t)(-2147483647 - 1))
@@ -317,6 +328,22 @@ int mrx_sync(mrx_renderer *r);
  *    mrx_destroy) or NULL on error. */
 void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim,
                  int *dtype, int *device);
+
+/* -- supersampling (MRX_FLAG_SUPERSAMPLE_MASK).  mrx_supersample returns the factor s, 1 ... 4 (MRX_E_INVALID for a
+ *    null renderer).  On a renderer with s > 1 mrx_buffer / mrx_buffer_shard / mrx_copy_to_host give the resolved
+ *    tensors, mrx_info the native storage_fast / storage_slow (bytes_per_step: the sample render's bytes plus what the
+ *    resolve reads and writes), mrx_set_view_projection / mrx_view_projection speak in the caller's terms, and
+ *    mrx_step / mrx_render / mrx_time_renders / the first frame of mrx_create enqueue the render and then the resolve.
+ *    mrx_sample_buffer is mrx_buffer for the s * W x s * H tensor the render writes: same signature, ownership and
+ *    lifetime; `which` is an output id (rgb, depth, segmask, visibility, normal).  NULL with MRX_E_UNSUPPORTED at
+ *    s = 1, on an output that is not rendered, and on a renderer of several shards (address one shard).
+ *    mrx_resolve enqueues the resolve stage alone on the renderer's stream (every shard's on its own), as mrx_render
+ *    enqueues the render: what a caller that wrote the sample tensors itself, or timed the stage, calls.
+ *    MRX_E_UNSUPPORTED at s = 1. */
+int mrx_supersample(mrx_renderer *r);
+void *mrx_sample_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim,
+                        int *dtype, int *device);
+int mrx_resolve(mrx_renderer *r);
 
 /* -- debug readback: waits for the stream, then copies the first `bytes`
  *    bytes of a buffer to host memory (what /root/reference/src/dump.cpp:53-70

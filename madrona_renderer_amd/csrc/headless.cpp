@@ -12,6 +12,8 @@
 //                     [--normals]   (the surface-normal output; --dump-last-frame also writes NAME.normals.png)
 //                     [--instance-labels SEED]   (a label per instance row, rows 1::4 left at their object's id;
 //                                                 --dump-last-frame also writes NAME.labels.png)
+//                     [--supersample N]   (1 ... 4: every view rendered at N times the width and height and resolved;
+//                                          --dump-last-frame writes the resolved images)
 //
 // --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
 // renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
@@ -80,6 +82,8 @@ struct Args {
     // --dump-last-frame then also writes NAME.labels.png
     bool hasLabels = false;
     uint64_t labelSeed = 0;
+    // --supersample N: the supersampling factor, 1 ... 4 (the sample image at most 16384 pixels a side)
+    uint32_t supersample = 1;
 };
 
 // a number of the whole argument, finite
@@ -98,7 +102,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -188,6 +192,16 @@ Args parse(int argc, char **argv)
                 std::exit(EXIT_FAILURE);
             }
             a.hasLabels = true;
+        } else if (!std::strcmp(argv[i], "--supersample") && i + 1 < argc) {
+            const char *s = argv[++i];
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long v = std::strtoull(s, &end, 10);
+            if (!*s || *s == '-' || *s == '+' || *end || errno != 0 || v < 1 || v > 4) {
+                std::fprintf(stderr, "--supersample: not a factor from 1 to 4: %s\n", s);
+                std::exit(EXIT_FAILURE);
+            }
+            a.supersample = (uint32_t)v;
         } else if (!std::strcmp(argv[i], "--znear") && i + 1 < argc) {
             a.znear = parseFloat("--znear", argv[++i]);
             if (!(a.znear > 0.0f)) {
@@ -206,6 +220,11 @@ Args parse(int argc, char **argv)
     }
     if (a.numWorlds == 0 || a.width == 0 || a.height == 0 || a.gpus == 0 || a.gpus > a.numWorlds)
         usage(argv[0]);
+    if ((uint64_t)a.supersample * a.width > 16384 || (uint64_t)a.supersample * a.height > 16384) {
+        std::fprintf(stderr, "--supersample: %u times %u x %u is more than 16384 pixels a side\n", a.supersample, a.width,
+                     a.height);
+        std::exit(EXIT_FAILURE);
+    }
     if (a.mode == Mode::Raycaster && !(a.znear < 1000.0f)) {
         std::fprintf(stderr, "--znear: must be below the Raytracer far plane (1000)\n");
         std::exit(EXIT_FAILURE);
@@ -492,6 +511,7 @@ int main(int argc, char **argv)
     }
     cfg.renderOutputs = args.outputs;
     cfg.normals = args.normals;
+    cfg.supersample = args.supersample;
 
     Manager mgr(cfg);              // aborts (FATAL) on failure, like the reference
     mgr.sync();

@@ -38,11 +38,13 @@ struct Manager::Impl {
     mrx_renderer *r = nullptr;
     ~Impl() { mrx_destroy(r); }
 
-    Tensor wrap(int which, uint32_t shard) const
+    Tensor wrap(int which, uint32_t shard, bool sample = false) const
     {
         int64_t dims[4] = { 0, 0, 0, 0 };
         int ndim = 0, dtype = 0, dev = 0;
-        void *p = mrx_buffer_shard(r, (int)shard, which, dims, &ndim, &dtype, &dev);
+        mrx_renderer *sh = sample ? mrx_shard(r, (int)shard) : nullptr;
+        void *p = sample ? (sh ? mrx_sample_buffer(sh, which, dims, &ndim, &dtype, &dev) : nullptr)
+                         : mrx_buffer_shard(r, (int)shard, which, dims, &ndim, &dtype, &dev);
         if (!p)
             detail::fatal(mrx_last_error());
         TensorElementType t = dtype == MRX_DTYPE_U8 ? TensorElementType::UInt8
@@ -108,6 +110,9 @@ Manager::Manager(const Config &cfg)
         c.flags |= MRX_FLAG_NORMALS;
     if (cfg.instanceLabelColumn || cfg.instanceLabels)
         c.flags |= MRX_FLAG_INSTANCE_LABELS;
+    if (cfg.supersample < 1 || cfg.supersample > 4)
+        detail::fatal("supersample " + std::to_string(cfg.supersample) + " is not in 1 ... 4");
+    c.flags |= MRX_FLAG_SUPERSAMPLE(cfg.supersample);
     if (cfg.renderOutputs == RenderOutputs::Depth)
         c.flags |= MRX_FLAG_NO_RGB;
     else if (cfg.renderOutputs == RenderOutputs::RGB)
@@ -208,6 +213,16 @@ Tensor Manager::cameraRotationTensor(uint32_t shard) const
 uint64_t Manager::rgbCudaPtr(uint32_t shard) const { return (uint64_t)rgbTensor(shard).devicePtr(); }
 uint64_t Manager::depthCudaPtr(uint32_t shard) const { return (uint64_t)depthTensor(shard).devicePtr(); }
 uint64_t Manager::segmaskCudaPtr(uint32_t shard) const { return (uint64_t)segmaskTensor(shard).devicePtr(); }
+
+uint32_t Manager::supersample() const { return (uint32_t)mrx_supersample(impl_->r); }
+
+Tensor Manager::sampleTensor(int which, uint32_t shard) const { return impl_->wrap(which, shard, true); }
+
+void Manager::resolve()
+{
+    if (mrx_resolve(impl_->r) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
 
 void Manager::refreshObjects()
 {

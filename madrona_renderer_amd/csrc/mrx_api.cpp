@@ -26,6 +26,7 @@
 #include "assets.hpp"
 #include "bvh.hpp"
 #include "raster.hpp"
+#include "resolve.hpp"
 
 namespace {
 
@@ -365,6 +366,14 @@ struct mrx_renderer {
     DevBuf<float> depth;
     DevBuf<int32_t> ids;
     DevBuf<uint32_t> normal;                    // MRX_FLAG_NORMALS; no pointer without the flag
+    // supersampling: with ss > 1 everything above is the renderer of ss * W x ss * H views -- the
+    // four tensors hold the samples -- and these are the native tensors the resolve stage writes, the ones a caller
+    // sees; info.storage_fast / storage_slow are native.  ss == 1: no pointers, no second launch.
+    uint32_t ss = 1;
+    DevBuf<uint32_t> outRgb;
+    DevBuf<float> outDepth;
+    DevBuf<int32_t> outIds;
+    DevBuf<uint32_t> outNormal;
     DevBuf<unsigned long long> stamps;
     // XCD phase feedback (raster.hip): a host-mapped word workgroup 0 reports its XCC id to
     uint32_t *xccHost = nullptr, *xccDev = nullptr;
@@ -417,7 +426,32 @@ struct mrx_renderer {
     DevBuf<mrx::ViewLight> lightDev;
     mrx::ViewLight *lightStage = nullptr;
 
+    // a step's launches: the render and, on a supersampled renderer, the resolve behind it on the same stream
     hipError_t launch()
+    {
+        const hipError_t e = launchRender();
+        return e == hipSuccess && ss > 1 ? launchResolve() : e;
+    }
+
+    // (the sample pointers are read from the render's parameters at every launch: the placement search re-binds them)
+    hipError_t launchResolve()
+    {
+        mrx::ResolveParams q {};
+        q.rgbIn = params.rgb;
+        q.depthIn = reinterpret_cast<const uint32_t *>(params.depth);
+        q.idsIn = reinterpret_cast<const uint32_t *>(params.ids);
+        q.normalIn = params.normal;
+        q.rgbOut = outRgb.ptr;
+        q.depthOut = reinterpret_cast<uint32_t *>(outDepth.ptr);
+        q.idsOut = reinterpret_cast<uint32_t *>(outIds.ptr);
+        q.normalOut = outNormal.ptr;
+        q.rows = params.numViews * info.storage_slow;
+        q.nfast = info.storage_fast;
+        q.numCUs = params.numCUs;
+        return mrx::launchResolve(q, (int)ss, stream);
+    }
+
+    hipError_t launchRender()
     {
         // the parity workgroup 0 reported some launches ago (the word is written by the
         // device without synchronisation: any value it ever held is a valid prediction)
@@ -468,6 +502,7 @@ struct mrx_renderer {
             (void)hipEventDestroy(labelEv);
         poseBlock.release(); geomBlock.release();
         rgb.release(); depth.release(); ids.release(); normal.release(); stamps.release();
+        outRgb.release(); outDepth.release(); outIds.release(); outNormal.release();
         if (xccHost) (void)hipHostFree(xccHost);
         bvhNodes.release(); bvhLeafTris.release(); worldInstStart.release();
         viewWorld.release(); instKBase.release(); objInfo.release();
@@ -490,7 +525,7 @@ struct mrx_renderer {
 // handshake.  Workers spin on their word for a while after a command (a simulation loop calls
 // step() every few tens of microseconds) and then sleep in a futex; MRX_SHARD_SPIN_US sets how
 // long (default 200), MRX_SHARD_THREADS=0 restores the serial form (startShardWorkers).
-enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdExit };
+enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdExit };
 
 struct ShardWorker {
     std::vector<mrx_renderer *> shards;         // the shards of ONE device, launched in order
@@ -565,6 +600,10 @@ int groupRun(const std::vector<mrx_renderer *> &shards, int cmd, int steps, bool
     case kCmdRender:
         for (mrx_renderer *sh : shards)
             MRX_HIP(sh->launch());
+        return MRX_OK;
+    case kCmdResolve:
+        for (mrx_renderer *sh : shards)
+            MRX_HIP(sh->launchResolve());
         return MRX_OK;
     case kCmdSync:
         for (mrx_renderer *sh : shards)
@@ -2194,7 +2233,7 @@ static int choosePlacement(mrx_renderer *r)
         r->params.normal = c.normal.ptr;
     };
     auto freeCand = [](Cand &c) { c.rgb.release(); c.depth.release(); c.ids.release(); c.normal.release(); };
-    auto launch = [&]() { return r->launch(); };
+    auto launch = [&]() { return r->launchRender(); };     // (the sample render alone: the resolve reads whatever is kept)
     auto timeBatch = [&](int n, float &ms) -> hipError_t {
         hipError_t e = hipEventRecord(r->ev0, r->stream);
         for (int i = 0; i < n && e == hipSuccess; ++i)
@@ -2279,6 +2318,31 @@ static int choosePlacement(mrx_renderer *r)
     return MRX_OK;
 }
 
+static uint32_t supersampleOf(uint32_t flags)
+{
+    return 1u + ((flags & MRX_FLAG_SUPERSAMPLE_MASK) >> MRX_FLAG_SUPERSAMPLE_SHIFT);
+}
+
+// the native tensors of a supersampled renderer, one per sample tensor, laid out as the outputs of a plain renderer of
+// the native size are; info then describes what the caller sees: native storage, and the resolve's bytes on top of the
+// sample render's -- s * s * 4 read per native pixel of rgb, 4 per point-sampled tensor, 4 written per tensor
+static int allocResolved(mrx_renderer &r)
+{
+    const uint32_t s = r.ss;
+    const uint32_t nfast = r.params.nfast / s, nslow = r.params.nslow / s;
+    const uint64_t px = (uint64_t)r.params.numViews * nfast * nslow;
+    if (px > mrx::kResolveMaxPixels)
+        return fail(MRX_E_INVALID, "supersampling: more than 2^32 - 1 native pixels");
+    MRX_HIP(allocOutputs((size_t)px, r.rgb.ptr != nullptr, r.depth.ptr != nullptr, r.ids.ptr != nullptr,
+                         firstKindIsOneBlock((size_t)px), r.outRgb, r.outDepth, r.outIds, r.normal.ptr != nullptr,
+                         r.outNormal));
+    r.info.storage_fast = nfast;
+    r.info.storage_slow = nslow;
+    const uint64_t points = (r.depth.ptr ? 1u : 0u) + (r.ids.ptr ? 1u : 0u) + (r.normal.ptr ? 1u : 0u);
+    r.info.bytes_per_step += px * ((r.rgb.ptr ? 4ull * s * s + 4ull : 0ull) + 8ull * points);
+    return MRX_OK;
+}
+
 // one renderer on one device (mrx_create proper, or one shard of a multi-device renderer)
 static int createOne(const mrx_config &cfg, mrx_renderer **out)
 {
@@ -2297,7 +2361,15 @@ static int createOne(const mrx_config &cfg, mrx_renderer **out)
     r->mode = cfg.render_mode;
     r->flags = cfg.flags;
     r->variant = cfg.kernel_variant;
-    int rc = buildScene(cfg, *r);
+    // S12: a supersampled renderer is the renderer of the sample image -- buildScene sees ss * W x ss * H views, and
+    // everything it decides (constants, dispatch, placement) is that renderer's -- plus the native tensors behind it
+    r->ss = supersampleOf(cfg.flags);
+    mrx_config sampleCfg = cfg;
+    sampleCfg.view_width *= r->ss;
+    sampleCfg.view_height *= r->ss;
+    int rc = buildScene(sampleCfg, *r);
+    if (rc == MRX_OK && r->ss > 1)
+        rc = allocResolved(*r);
     if (rc == MRX_OK) {
         hipError_t e = hipEventCreate(&r->ev0);
         if (e == hipSuccess) e = hipEventCreate(&r->ev1);
@@ -2353,6 +2425,12 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
     if (cfg->view_width == 0 || cfg->view_height == 0 || cfg->view_width > 16384 ||
         cfg->view_height > 16384)
         return fail(MRX_E_INVALID, "bad view size");
+    {
+        const uint64_t s = supersampleOf(cfg->flags);
+        if (s * cfg->view_width > 16384 || s * cfg->view_height > 16384)
+            return fail(MRX_E_INVALID, "bad view size: the sample image of supersampling factor " + std::to_string(s) +
+                                           " is larger than 16384 pixels a side");
+    }
     if (cfg->num_worlds && !cfg->worlds)
         return fail(MRX_E_INVALID, "worlds is null");
     if ((cfg->num_instances && !cfg->instances) || (cfg->num_cameras && !cfg->cameras) ||
@@ -2406,6 +2484,7 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
     top->mode = cfg->render_mode;
     top->flags = cfg->flags;
     top->variant = cfg->kernel_variant;
+    top->ss = supersampleOf(cfg->flags);
     top->device = cfg->device_ids[0];
     const uint32_t n = cfg->num_devices;
     for (uint32_t i = 0; i < n; ++i) {
@@ -2638,8 +2717,9 @@ int mrx_set_stream(mrx_renderer *r, void *stream)
     return MRX_OK;
 }
 
-void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dtype,
-                 int *device)
+// mrx_buffer and mrx_sample_buffer: the tensor of `which` the caller sees (on a supersampled renderer the resolved one),
+// or, `sample`, the s * W x s * H tensor the render writes
+static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dtype, int *device, bool sample)
 {
     if (settle(r) != MRX_OK)
         return nullptr;
@@ -2648,19 +2728,37 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
         return nullptr;
     }
     if (!r->shards.empty()) {
-        wantsShard("mrx_buffer");
+        wantsShard(sample ? "mrx_sample_buffer" : "mrx_buffer");
+        return nullptr;
+    }
+    if (sample && r->ss == 1) {
+        fail(MRX_E_UNSUPPORTED, "no sample tensors: this renderer was created without supersampling");
+        return nullptr;
+    }
+    if (sample && which != MRX_BUF_RGB && which != MRX_BUF_DEPTH && which != MRX_BUF_SEGMASK &&
+        which != MRX_BUF_VISIBILITY && which != MRX_BUF_NORMAL) {
+        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT3 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
+             "not a rendered output: only rgb, depth, normals and the ids tensor have samples");
         return nullptr;
     }
     const bool rt = r->mode == MRX_MODE_RAYTRACER;
     const int64_t V = r->info.num_views, I = r->info.num_instances;
-    const int64_t S = r->info.storage_slow, F = r->info.storage_fast;
+    const int64_t S = (int64_t)r->info.storage_slow * (sample ? r->ss : 1u);
+    const int64_t F = (int64_t)r->info.storage_fast * (sample ? r->ss : 1u);
+    // (what the caller sees of a supersampled renderer are the resolved tensors; each exists exactly when its sample
+    // tensor does)
+    const bool resolved = r->ss > 1 && !sample;
+    void *const rgbPtr = resolved ? (void *)r->outRgb.ptr : (void *)r->rgb.ptr;
+    void *const depthPtr = resolved ? (void *)r->outDepth.ptr : (void *)r->depth.ptr;
+    void *const idsPtr = resolved ? (void *)r->outIds.ptr : (void *)r->ids.ptr;
+    void *const normalPtr = resolved ? (void *)r->outNormal.ptr : (void *)r->normal.ptr;
     void *ptr = nullptr;
     if (device)
         *device = r->device;
     switch (which) {
     case MRX_BUF_RGB:       // mgr.cpp:547-568
         dims[0] = V; dims[1] = S; dims[2] = F; dims[3] = 4;
-        *ndim = 4; *dtype = MRX_DTYPE_U8; ptr = r->rgb.ptr;
+        *ndim = 4; *dtype = MRX_DTYPE_U8; ptr = rgbPtr;
         if (!ptr) {
             fail(MRX_E_UNSUPPORTED, "rgb not rendered: this renderer was created depth-only (MRX_FLAG_NO_RGB)");
             return nullptr;
@@ -2668,7 +2766,7 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
         break;
     case MRX_BUF_NORMAL:    // the surface-normal output: storage as rgb's
         dims[0] = V; dims[1] = S; dims[2] = F; dims[3] = 4;
-        *ndim = 4; *dtype = MRX_DTYPE_U8; ptr = r->normal.ptr;
+        *ndim = 4; *dtype = MRX_DTYPE_U8; ptr = normalPtr;
         if (!ptr) {
             fail(MRX_E_UNSUPPORTED, "normals not rendered: this renderer was created without MRX_FLAG_NORMALS");
             return nullptr;
@@ -2676,7 +2774,7 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
         break;
     case MRX_BUF_DEPTH:     // mgr.cpp:570-590
         dims[0] = V; dims[1] = S; dims[2] = F; dims[3] = 1;
-        *ndim = rt ? 3 : 4; *dtype = MRX_DTYPE_F32; ptr = r->depth.ptr;
+        *ndim = rt ? 3 : 4; *dtype = MRX_DTYPE_F32; ptr = depthPtr;
         if (!ptr) {
             fail(MRX_E_UNSUPPORTED, "depth not rendered: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)");
             return nullptr;
@@ -2692,7 +2790,7 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
             return nullptr;
         }
         dims[0] = V; dims[1] = S; dims[2] = F;
-        *ndim = 3; *dtype = MRX_DTYPE_I32; ptr = r->ids.ptr;
+        *ndim = 3; *dtype = MRX_DTYPE_I32; ptr = idsPtr;
         break;
     case MRX_BUF_VISIBILITY:
         if (!r->ids.ptr || r->params.idsAreSegmask) {
@@ -2700,7 +2798,7 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
             return nullptr;
         }
         dims[0] = V; dims[1] = S; dims[2] = F;
-        *ndim = 3; *dtype = MRX_DTYPE_I32; ptr = r->ids.ptr;
+        *ndim = 3; *dtype = MRX_DTYPE_I32; ptr = idsPtr;
         break;
     case MRX_BUF_INSTANCE_POSITION:   // mgr.cpp:627-635
         dims[0] = I; dims[1] = 3; *ndim = 2; *dtype = MRX_DTYPE_F32; ptr = r->instPos.ptr;
@@ -2749,6 +2847,41 @@ void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dt
         return nullptr;
     }
     return ptr;
+}
+
+void *mrx_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dtype, int *device)
+{
+    return bufferOf(r, which, dims, ndim, dtype, device, false);
+}
+
+void *mrx_sample_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim, int *dtype, int *device)
+{
+    return bufferOf(r, which, dims, ndim, dtype, device, true);
+}
+
+int mrx_supersample(mrx_renderer *r)
+{
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    return (int)r->ss;
+}
+
+int mrx_resolve(mrx_renderer *r)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (r->ss == 1)
+        return fail(MRX_E_UNSUPPORTED, "nothing to resolve: this renderer was created without supersampling");
+    if (!r->shards.empty())
+        return shardsRun(r, kCmdResolve);
+    MRX_HIP(hipSetDevice(r->device));
+    MRX_HIP(r->launchResolve());
+    return MRX_OK;
 }
 
 int mrx_copy_to_host(mrx_renderer *r, int which, void *dst, uint64_t bytes)

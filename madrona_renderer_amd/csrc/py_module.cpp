@@ -187,6 +187,9 @@ PYBIND11_MODULE(madrona_renderer, m)
     m.attr("MRX_BUF_INSTANCE_LABEL") = (int)MRX_BUF_INSTANCE_LABEL;
     m.attr("MRX_NUM_BUFFERS_EXT3") = (int)MRX_NUM_BUFFERS_EXT3;
     m.attr("MRX_LABEL_OBJECT") = (int32_t)MRX_LABEL_OBJECT;
+    // ... and of the supersampling factor
+    m.attr("MRX_FLAG_SUPERSAMPLE_SHIFT") = (uint32_t)MRX_FLAG_SUPERSAMPLE_SHIFT;
+    m.attr("MRX_FLAG_SUPERSAMPLE_MASK") = (uint32_t)MRX_FLAG_SUPERSAMPLE_MASK;
     m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
     m.attr("MRX_CONFIG_SIZE") = (uint32_t)sizeof(mrx_config);
 
@@ -306,7 +309,9 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<Sim::WorldInit> &worlds,
                          const std::vector<int> &device_ids, int max_instances_per_world,
                          Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors,
-                         py::object instance_materials, bool normals, py::object instance_labels) {
+                         py::object instance_materials, bool normals, py::object instance_labels, int supersample) {
+                 if (supersample < 1 || supersample > 4)
+                     throw py::value_error("supersample must be 1, 2, 3 or 4");
                  if (mesh_vertices.size() && (mesh_vertices.ndim() != 2 || mesh_vertices.shape(1) != 3))
                      throw py::value_error("mesh_vertices must have shape [N, 3]");
                  if (mesh_uvs.size() && (mesh_uvs.ndim() != 2 || mesh_uvs.shape(1) != 2))
@@ -432,6 +437,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                      cfg.instanceLabels = labels.data();
                      cfg.instanceLabelColumn = true;
                  }
+                 cfg.supersample = (uint32_t)supersample;
                  return new Manager(cfg);
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -456,7 +462,9 @@ PYBIND11_MODULE(madrona_renderer, m)
              // normals = True: the surface-normal output, normal_tensor()
              py::arg("normals") = false,
              // instance_labels = True or a [num_instances] int32 array: the label column (the segmask in both modes)
-             py::arg("instance_labels") = py::none())
+             py::arg("instance_labels") = py::none(),
+             // supersample = s: every view rendered at s * width x s * height and resolved (sample_tensor, resolve)
+             py::arg("supersample") = 1)
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -470,6 +478,22 @@ PYBIND11_MODULE(madrona_renderer, m)
         .def("normal_tensor",
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().normalTensor(shardOf(self, shard))); },
              py::arg("shard") = py::none())
+        // supersampling: the factor; the s * W x s * H tensor the render writes for "rgb", "depth", "segmask",
+        // "visibility" or "normal" (RuntimeError at factor 1 or on an output that is not rendered); the resolve stage alone
+        .def_property_readonly("supersample", &Manager::supersample)
+        .def("sample_tensor",
+             [](py::object self, const std::string &name, py::object shard) {
+                 static const std::pair<const char *, int> ids[] = {
+                     { "rgb", MRX_BUF_RGB }, { "depth", MRX_BUF_DEPTH }, { "segmask", MRX_BUF_SEGMASK },
+                     { "visibility", MRX_BUF_VISIBILITY }, { "normal", MRX_BUF_NORMAL } };
+                 for (const auto &id : ids)
+                     if (name == id.first)
+                         return wrapTensor(self, self.cast<Manager &>().sampleTensor(id.second, shardOf(self, shard)));
+                 throw py::value_error("sample_tensor: no output named " + name +
+                                       " (rgb, depth, segmask, visibility, normal)");
+             },
+             py::arg("name"), py::arg("shard") = py::none())
+        .def("resolve", &Manager::resolve)
         .def("segmask_tensor",
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().segmaskTensor(shardOf(self, shard))); },
              py::arg("shard") = py::none())

@@ -64,6 +64,9 @@ class SceneDesc:
     instance_labels: object = None
     # the surface-normal output (normal_tensor()): view-space normals of the winning triangles, RGBA8-encoded
     normals: bool = False
+    # supersampled antialiasing: 1 ... 4; with s > 1 every view is rendered at s * width x s * height and resolved to
+    # width x height (rgb box-filtered; depth, normals and the ids tensor point-sampled)
+    supersample: int = 1
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -299,6 +302,8 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
             if labels.shape != (len(desc.instances),):
                 raise ValueError("instance_labels needs one label per instance")
             extra["instance_labels"] = labels
+    if desc.supersample != 1:
+        extra["supersample"] = int(desc.supersample)
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:

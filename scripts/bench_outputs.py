@@ -3,7 +3,7 @@
 that matter, one JSON line per (configuration, setting):
 
   python scripts/bench_outputs.py [--rounds 5] [--budget-ms 30] [--only headline,c2,...] [--normals] [--labels]
-                                  [--root TREE]
+                                  [--root TREE] [--supersample N[,N...]]
 
 --normals times RGBD+N, Depth+N and RGB+N (the surface-normal output beside each selection) beside the
 three settings, in the same alternation; without it the script does what it always did.
@@ -11,6 +11,12 @@ three settings, in the same alternation; without it the script does what it alwa
 12 B/px without labels) and RGBD+L (mixed labels in the label column, DESIGN.md 4.16: the segmask in both modes) beside
 them.  --root TREE imports madrona_renderer_amd from another checkout (a build of the parent commit, say); a tree
 whose SceneDesc has no instance_labels skips RGBD+L, so the same command line measures both builds.
+
+--supersample N measures the resolve stage instead, RGBD, on the configurations chosen (default:
+headline and c2): SS = time_renders of the renderer at supersample=N (render + resolve), PLAIN = time_renders of the
+plain renderer of the sample size N*W x N*H, in the same alternation, and RESOLVE = the resolve alone (mark, a batch of
+resolve(), mark) with its bytes -- bytes_per_step of SS minus that of PLAIN -- as a fraction of 8 TB/s; `placement`
+is what the sample tensors' placement search timed (candidates, kept).
 
 Every renderer of a configuration is created and warmed first; then the settings alternate within
 the process, `rounds` times, each measurement a batch of back-to-back renders between two events
@@ -77,6 +83,52 @@ def us_per_render(r, steps):
     return r.time_renders(steps) * 1000.0 / steps
 
 
+def supersample_main(a, scenes):
+    import dataclasses
+    only = set(filter(None, a.only.split(","))) or {"headline", "c2"}
+    for key, label, factory, variant in configs(scenes):
+        if key not in only:
+            continue
+        for n in [int(x) for x in a.supersample.split(",")]:
+            base = factory()
+            ss = scenes.make_renderer(dataclasses.replace(base, supersample=n))
+            plain = scenes.make_renderer(dataclasses.replace(base, width=base.width * n, height=base.height * n))
+
+            def resolve_us(steps, r=ss):
+                r.mark(0)
+                for _ in range(steps):
+                    r.resolve()
+                r.mark(1)
+                return r.elapsed_ms() * 1000.0 / steps
+
+            fns = {"SS": lambda steps, r=ss: us_per_render(r, steps), "PLAIN": lambda steps, r=plain: us_per_render(r, steps),
+                   "RESOLVE": resolve_us}
+            steps = {}
+            for s, fn in fns.items():
+                t0 = time.perf_counter()
+                while time.perf_counter() - t0 < 0.2:
+                    est = fn(20)
+                steps[s] = max(10, min(5000, int(a.budget_ms * 1000.0 / max(est, 1.0))))
+            times = {s: [] for s in fns}
+            for _ in range(a.rounds):
+                for s, fn in fns.items():
+                    times[s].append(fn(steps[s]))
+            nbytes = {"SS": int(ss.bytes_per_step()), "PLAIN": int(plain.bytes_per_step())}
+            nbytes["RESOLVE"] = nbytes["SS"] - nbytes["PLAIN"]
+            for s in fns:
+                med = statistics.median(times[s])
+                print(json.dumps({
+                    "config": key, "workload": label, "supersample": n, "setting": s, "views": base.num_views,
+                    "native": [base.width, base.height], "steps": steps[s], "rounds": a.rounds,
+                    "us_median": round(med, 3), "us_min": round(min(times[s]), 3), "us_max": round(max(times[s]), 3),
+                    "us_all": [round(t, 3) for t in times[s]],
+                    "ratio_to_plain": round(med / statistics.median(times["PLAIN"]), 4),
+                    "bytes": nbytes[s], "frac_8tbps": round(nbytes[s] / (med * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4),
+                    "placement": (ss if s != "PLAIN" else plain).placement(),
+                }), flush=True)
+            del ss, plain
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--rounds", type=int, default=5)
@@ -85,12 +137,15 @@ def main(argv=None):
     ap.add_argument("--normals", action="store_true", help="also time each setting with the surface-normal output")
     ap.add_argument("--labels", action="store_true", help="also time RGBD with visibility ids and with the label column")
     ap.add_argument("--root", default="", help="import madrona_renderer_amd from this checkout instead")
+    ap.add_argument("--supersample", default="", help="factors (2,3,4): measure the resolve stage instead (DESIGN.md 4.18)")
     a = ap.parse_args(argv)
     if a.rounds < 3:
         ap.error("--rounds must be at least 3")
     if a.root:
         sys.path.insert(0, os.path.abspath(a.root))
     from madrona_renderer_amd import scenes
+    if a.supersample:
+        return supersample_main(a, scenes)
     only = set(filter(None, a.only.split(",")))
     settings = SETTINGS + (NORMAL_SETTINGS if a.normals else ())
     if a.labels:
