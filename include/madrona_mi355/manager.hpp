@@ -115,6 +115,9 @@ public:
         // the width and height and resolved to the configured size -- rgb box-filtered, depth, normals and the ids
         // tensor point-sampled -- so every tensor getter keeps its shape.
         uint32_t supersample = 1;
+        // Position output (MRX_FLAG_POSITIONS / _VIEW): 0 none, 1 world space, 2 view space; positionTensor() then holds
+        // the point every pixel sees, computed from depth by a stage behind every render.  Needs depth rendered.
+        uint32_t positions = 0;
     };
     // the label that stands for the id of the object a row is bound to (MRX_LABEL_OBJECT)
     static constexpr int32_t kLabelObject = INT32_MIN;
@@ -167,6 +170,12 @@ public:
     uint32_t supersample() const;
     madrona::py::Tensor sampleTensor(int which, uint32_t shard = 0) const;
     void resolve();
+    // position output: 0 none / 1 world / 2 view; f32 [views, H, W, 4] (Raytracer: [views, res, res, 4] transposed, as
+    // rgb): (x, y, z, 1) of the point the pixel's depth stands for, (0, 0, 0, 0) on background (fatal without
+    // Config::positions); the unprojection stage alone
+    uint32_t positions() const;
+    madrona::py::Tensor positionTensor(uint32_t shard = 0) const;
+    void unproject();
     // binds every row to the (non-negative) object id its ObjectID column now holds: a spare
     // row gets its geometry, an existing row swaps it (makeEntityRenderable at run time,
     // src/sim.inl:5-8); waits for the device

@@ -140,7 +140,17 @@ enum {
      * column fail with MRX_E_UNSUPPORTED, Rasterizer-mode MRX_BUF_SEGMASK fails as it always did and every launch is
      * the one it always was.  Together with MRX_FLAG_VISIBILITY_IDS the one ids tensor holds visibility ids:
      * the column exists and is mutable, MRX_BUF_SEGMASK is refused. */
-    MRX_FLAG_INSTANCE_LABELS = 1u << 7
+    MRX_FLAG_INSTANCE_LABELS = 1u << 7,
+    /* (bits 8 and 9: the supersampling factor, MRX_FLAG_SUPERSAMPLE_MASK below) */
+    /* position output: allocates the MRX_BUF_POSITION tensor -- the 3-D point every pixel sees, xyzw, w = 0 where
+     * nothing was hit -- and enqueues an unprojection stage behind every render (and resolve) on the same stream
+     * (DESIGN.md S13, 4.19).  The points are in world space, or, with MRX_FLAG_POSITIONS_VIEW, in view space (+X right,
+     * +Y forward, +Z up); that flag implies this one and means nothing else.  The stage reads the depth tensor the
+     * caller sees, so MRX_FLAG_NO_DEPTH beside it is MRX_E_INVALID; it combines with everything else and changes no
+     * other output.  Without it nothing is allocated, mrx_buffer / mrx_buffer_shard / mrx_copy_to_host on the tensor
+     * fail with MRX_E_UNSUPPORTED and every launch is the one it always was. */
+    MRX_FLAG_POSITIONS = 1u << 10,
+    MRX_FLAG_POSITIONS_VIEW = 1u << 11
 };
 /* supersampled antialiasing: a two-bit field of the flags holds the factor,
  * s = 1 + ((flags >> MRX_FLAG_SUPERSAMPLE_SHIFT) & 3), so s = 1 ... 4 and MRX_FLAG_SUPERSAMPLE(s) sets it.  With s > 1
@@ -289,7 +299,16 @@ enum {
      * spare rows start at MRX_LABEL_OBJECT.  Written on the device, like a pose, on the renderer's stream; read under
      * every output selection, a depth-only renderer included. */
     MRX_BUF_INSTANCE_LABEL = 13,
-    MRX_NUM_BUFFERS_EXT3 = 14
+    MRX_NUM_BUFFERS_EXT3 = 14,
+    /* f32 [views,H,W,4] (Raytracer: [views,res,res,4], transposed like rgb), needs MRX_FLAG_POSITIONS: per pixel the
+     * point (x, y, z, 1) its depth stands for -- in world space, or in view space with MRX_FLAG_POSITIONS_VIEW -- and
+     * (0, 0, 0, 0) where depth is 0 (background).  Computed from the depth tensor, the camera pose tensors and the
+     * projection constants as they are when the stage runs: view space P = (d * rx, d, d * rz) with S5's
+     * ray of the pixel centre (on a supersampled renderer: of the sample depth was taken from), world space
+     * R(q) * P + c with the view's camRot / camPos rows -- the inverse of the camera transform for a unit quaternion
+     * only: the quaternion is used as given, as everywhere.  An allocation of its own, one per shard. */
+    MRX_BUF_POSITION = 14,
+    MRX_NUM_BUFFERS_EXT4 = 15
 };
 
 enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2 };
@@ -344,6 +363,15 @@ int mrx_supersample(mrx_renderer *r);
 void *mrx_sample_buffer(mrx_renderer *r, int which, int64_t dims[4], int *ndim,
                         int *dtype, int *device);
 int mrx_resolve(mrx_renderer *r);
+
+/* -- position output (MRX_FLAG_POSITIONS).  mrx_positions returns 0 (no position output), 1 (world space) or 2 (view
+ *    space); MRX_E_INVALID for a null renderer.  With the output, mrx_step / mrx_render / mrx_time_renders / the first
+ *    frame of mrx_create enqueue the render, the resolve where there is one, and then the unprojection stage.
+ *    mrx_unproject enqueues that stage alone on the renderer's stream (every shard's on its own), as mrx_resolve does
+ *    the resolve: what a caller that wrote depth, a camera pose or a projection itself, or timed the stage, calls.
+ *    MRX_E_UNSUPPORTED without the output. */
+int mrx_positions(mrx_renderer *r);
+int mrx_unproject(mrx_renderer *r);
 
 /* -- debug readback: waits for the stream, then copies the first `bytes`
  *    bytes of a buffer to host memory (what /root/reference/src/dump.cpp:53-70

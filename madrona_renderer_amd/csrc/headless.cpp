@@ -14,6 +14,8 @@
 //                                                 --dump-last-frame also writes NAME.labels.png)
 //                     [--supersample N]   (1 ... 4: every view rendered at N times the width and height and resolved;
 //                                          --dump-last-frame writes the resolved images)
+//                     [--positions [world|view]]   (the position output, world space unless `view`; --dump-last-frame
+//                                                   also writes NAME.points.ply, the hit pixels' points; needs depth)
 //
 // --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
 // renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
@@ -84,6 +86,9 @@ struct Args {
     uint64_t labelSeed = 0;
     // --supersample N: the supersampling factor, 1 ... 4 (the sample image at most 16384 pixels a side)
     uint32_t supersample = 1;
+    // --positions [world|view]: the position output (0 none, 1 world, 2 view); --dump-last-frame then also writes
+    // NAME.points.ply
+    uint32_t positions = 0;
 };
 
 // a number of the whole argument, finite
@@ -102,7 +107,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -202,6 +207,18 @@ Args parse(int argc, char **argv)
                 std::exit(EXIT_FAILURE);
             }
             a.supersample = (uint32_t)v;
+        } else if (!std::strcmp(argv[i], "--positions")) {
+            // the frame is optional: the next argument is taken for it unless it is another option
+            a.positions = 1;
+            if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
+                const char *f = argv[++i];
+                if (!std::strcmp(f, "view"))
+                    a.positions = 2;
+                else if (std::strcmp(f, "world") != 0) {
+                    std::fprintf(stderr, "--positions: the frame is world or view, not: %s\n", f);
+                    std::exit(EXIT_FAILURE);
+                }
+            }
         } else if (!std::strcmp(argv[i], "--znear") && i + 1 < argc) {
             a.znear = parseFloat("--znear", argv[++i]);
             if (!(a.znear > 0.0f)) {
@@ -231,6 +248,10 @@ Args parse(int argc, char **argv)
     }
     if (a.dumpDepth && a.outputs == Manager::RenderOutputs::RGB) {
         std::fprintf(stderr, "--depth: depth is not rendered with --outputs rgb\n");
+        std::exit(EXIT_FAILURE);
+    }
+    if (a.positions && a.outputs == Manager::RenderOutputs::RGB) {
+        std::fprintf(stderr, "--positions: positions are computed from depth, which is not rendered with --outputs rgb\n");
         std::exit(EXIT_FAILURE);
     }
     return a;
@@ -417,6 +438,43 @@ bool dumpTiled(const std::string &name, mrx_renderer *shard, uint32_t numImages,
     return true;
 }
 
+// NAME.ply of --positions: binary little-endian PLY, one vertex per hit pixel (w != 0) of the first `numImages` views
+// in storage order: float x y z, and uchar red green blue where rgb is rendered (its storage is the positions').
+bool dumpPly(const std::string &name, mrx_renderer *shard, uint32_t numImages, uint32_t resX, uint32_t resY, bool withRgb)
+{
+    const size_t px = (size_t)numImages * resX * resY;
+    std::vector<float> pos(px * 4);
+    std::vector<uint8_t> rgb(withRgb ? px * 4 : 0);
+    if (mrx_copy_to_host(shard, MRX_BUF_POSITION, pos.data(), pos.size() * sizeof(float)) != MRX_OK ||
+        (withRgb && mrx_copy_to_host(shard, MRX_BUF_RGB, rgb.data(), rgb.size()) != MRX_OK)) {
+        std::fprintf(stderr, "%s\n", mrx_last_error());
+        return false;
+    }
+    size_t hits = 0;
+    for (size_t i = 0; i < px; ++i)
+        hits += pos[4 * i + 3] != 0.0f ? 1 : 0;
+    std::string out = "ply\nformat binary_little_endian 1.0\nelement vertex " + std::to_string(hits) +
+                      "\nproperty float x\nproperty float y\nproperty float z\n";
+    if (withRgb)
+        out += "property uchar red\nproperty uchar green\nproperty uchar blue\n";
+    out += "end_header\n";
+    out.reserve(out.size() + hits * (withRgb ? 15 : 12));
+    for (size_t i = 0; i < px; ++i) {
+        if (pos[4 * i + 3] == 0.0f)
+            continue;
+        out.append(reinterpret_cast<const char *>(&pos[4 * i]), 12);   // (the hosts this runs on are little-endian)
+        if (withRgb)
+            out.append(reinterpret_cast<const char *>(&rgb[4 * i]), 3);
+    }
+    FILE *f = std::fopen((name + ".ply").c_str(), "wb");
+    const bool ok = f && std::fwrite(out.data(), 1, out.size(), f) == out.size();
+    if (f && std::fclose(f) != 0)
+        return false;
+    if (!ok)
+        std::fprintf(stderr, "cannot write %s.ply\n", name.c_str());
+    return ok;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -512,6 +570,7 @@ int main(int argc, char **argv)
     cfg.renderOutputs = args.outputs;
     cfg.normals = args.normals;
     cfg.supersample = args.supersample;
+    cfg.positions = args.positions;
 
     Manager mgr(cfg);              // aborts (FATAL) on failure, like the reference
     mgr.sync();
@@ -548,6 +607,9 @@ int main(int argc, char **argv)
                 ok = dumpTiled(name + ".normals", sh, hi - lo, args.width, resY, DumpWhat::Normal, rt) && ok;
             if (args.hasLabels)
                 ok = dumpTiled(name + ".labels", sh, hi - lo, args.width, resY, DumpWhat::Labels, rt) && ok;
+            if (args.positions)
+                ok = dumpPly(name + ".points", sh, hi - lo, args.width, resY,
+                             args.outputs != Manager::RenderOutputs::Depth) && ok;
         }
     }
     if (!ok)

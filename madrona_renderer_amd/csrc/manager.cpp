@@ -113,6 +113,10 @@ Manager::Manager(const Config &cfg)
     if (cfg.supersample < 1 || cfg.supersample > 4)
         detail::fatal("supersample " + std::to_string(cfg.supersample) + " is not in 1 ... 4");
     c.flags |= MRX_FLAG_SUPERSAMPLE(cfg.supersample);
+    if (cfg.positions > 2)
+        detail::fatal("positions " + std::to_string(cfg.positions) + " is not 0 (none), 1 (world) or 2 (view)");
+    if (cfg.positions)
+        c.flags |= cfg.positions == 2 ? MRX_FLAG_POSITIONS | MRX_FLAG_POSITIONS_VIEW : MRX_FLAG_POSITIONS;
     if (cfg.renderOutputs == RenderOutputs::Depth)
         c.flags |= MRX_FLAG_NO_RGB;
     else if (cfg.renderOutputs == RenderOutputs::RGB)
@@ -221,6 +225,16 @@ Tensor Manager::sampleTensor(int which, uint32_t shard) const { return impl_->wr
 void Manager::resolve()
 {
     if (mrx_resolve(impl_->r) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+uint32_t Manager::positions() const { return (uint32_t)mrx_positions(impl_->r); }
+
+Tensor Manager::positionTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_POSITION, shard); }
+
+void Manager::unproject()
+{
+    if (mrx_unproject(impl_->r) != MRX_OK)
         detail::fatal(mrx_last_error());
 }
 

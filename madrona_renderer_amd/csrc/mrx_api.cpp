@@ -27,6 +27,7 @@
 #include "bvh.hpp"
 #include "raster.hpp"
 #include "resolve.hpp"
+#include "unproject.hpp"
 
 namespace {
 
@@ -374,6 +375,11 @@ struct mrx_renderer {
     DevBuf<float> outDepth;
     DevBuf<int32_t> outIds;
     DevBuf<uint32_t> outNormal;
+    // position output: 0 none, 1 world space, 2 view space (mrx_positions); the xyzw tensor the
+    // unprojection stage writes from the depth tensor the caller sees -- an allocation of its own, outside allocOutputs
+    // and the placement search.  0: no pointer, no further launch.
+    uint32_t positions = 0;
+    DevBuf<float> position;
     DevBuf<unsigned long long> stamps;
     // XCD phase feedback (raster.hip): a host-mapped word workgroup 0 reports its XCC id to
     uint32_t *xccHost = nullptr, *xccDev = nullptr;
@@ -426,11 +432,36 @@ struct mrx_renderer {
     DevBuf<mrx::ViewLight> lightDev;
     mrx::ViewLight *lightStage = nullptr;
 
-    // a step's launches: the render and, on a supersampled renderer, the resolve behind it on the same stream
+    // a step's launches: the render, on a supersampled renderer the resolve behind it, and with the position output
+    // the unprojection stage behind both, all on the same stream
     hipError_t launch()
     {
-        const hipError_t e = launchRender();
-        return e == hipSuccess && ss > 1 ? launchResolve() : e;
+        hipError_t e = launchRender();
+        if (e == hipSuccess && ss > 1)
+            e = launchResolve();
+        return e == hipSuccess && positions ? launchUnproject() : e;
+    }
+
+    // (depth, the constants and the table pointer are read from the render's parameters at every launch: the placement
+    // search re-binds the first, mrx_set_view_projection the others; pose and table CONTENTS are read by the kernel)
+    hipError_t launchUnproject()
+    {
+        mrx::UnprojectParams q {};
+        q.depth = ss > 1 ? outDepth.ptr : params.depth;
+        q.pos = position.ptr;
+        q.camPos = params.camPos;
+        q.camRot = params.camRot;
+        q.viewProj = params.viewProj;
+        q.sx = params.sx; q.ox = params.ox; q.sz = params.sz; q.oz = params.oz;
+        q.numViews = params.numViews;
+        q.nfast = info.storage_fast;
+        q.nslow = info.storage_slow;
+        q.s = ss;
+        q.half = ss / 2;
+        q.frame = positions == 2 ? mrx::kFrameView : mrx::kFrameWorld;
+        q.transposed = params.transposed;
+        q.numCUs = params.numCUs;
+        return mrx::launchUnproject(q, stream);
     }
 
     // (the sample pointers are read from the render's parameters at every launch: the placement search re-binds them)
@@ -503,6 +534,7 @@ struct mrx_renderer {
         poseBlock.release(); geomBlock.release();
         rgb.release(); depth.release(); ids.release(); normal.release(); stamps.release();
         outRgb.release(); outDepth.release(); outIds.release(); outNormal.release();
+        position.release();
         if (xccHost) (void)hipHostFree(xccHost);
         bvhNodes.release(); bvhLeafTris.release(); worldInstStart.release();
         viewWorld.release(); instKBase.release(); objInfo.release();
@@ -525,7 +557,7 @@ struct mrx_renderer {
 // handshake.  Workers spin on their word for a while after a command (a simulation loop calls
 // step() every few tens of microseconds) and then sleep in a futex; MRX_SHARD_SPIN_US sets how
 // long (default 200), MRX_SHARD_THREADS=0 restores the serial form (startShardWorkers).
-enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdExit };
+enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdUnproject, kCmdExit };
 
 struct ShardWorker {
     std::vector<mrx_renderer *> shards;         // the shards of ONE device, launched in order
@@ -604,6 +636,10 @@ int groupRun(const std::vector<mrx_renderer *> &shards, int cmd, int steps, bool
     case kCmdResolve:
         for (mrx_renderer *sh : shards)
             MRX_HIP(sh->launchResolve());
+        return MRX_OK;
+    case kCmdUnproject:
+        for (mrx_renderer *sh : shards)
+            MRX_HIP(sh->launchUnproject());
         return MRX_OK;
     case kCmdSync:
         for (mrx_renderer *sh : shards)
@@ -2343,6 +2379,24 @@ static int allocResolved(mrx_renderer &r)
     return MRX_OK;
 }
 
+static uint32_t positionsOf(uint32_t flags)
+{
+    return (flags & MRX_FLAG_POSITIONS_VIEW) ? 2u : (flags & MRX_FLAG_POSITIONS) ? 1u : 0u;
+}
+
+// the position tensor of a renderer with the position output: one allocation of its own (hipMalloc: 16-byte aligned
+// and more), [views][storage_slow][storage_fast][4] floats of the NATIVE size; the stage's bytes on top of the rest:
+// 4 read and 16 written per native pixel
+static int allocPositions(mrx_renderer &r)
+{
+    const uint64_t px = (uint64_t)r.params.numViews * r.info.storage_fast * r.info.storage_slow;
+    if (px > mrx::kUnprojectMaxPixels)
+        return fail(MRX_E_INVALID, "positions: more than 2^32 - 1 native pixels");
+    MRX_HIP(r.position.alloc((size_t)px * 4));
+    r.info.bytes_per_step += px * (4ull + 16ull);
+    return MRX_OK;
+}
+
 // one renderer on one device (mrx_create proper, or one shard of a multi-device renderer)
 static int createOne(const mrx_config &cfg, mrx_renderer **out)
 {
@@ -2370,6 +2424,9 @@ static int createOne(const mrx_config &cfg, mrx_renderer **out)
     int rc = buildScene(sampleCfg, *r);
     if (rc == MRX_OK && r->ss > 1)
         rc = allocResolved(*r);
+    r->positions = positionsOf(cfg.flags);
+    if (rc == MRX_OK && r->positions)
+        rc = allocPositions(*r);
     if (rc == MRX_OK) {
         hipError_t e = hipEventCreate(&r->ev0);
         if (e == hipSuccess) e = hipEventCreate(&r->ev1);
@@ -2446,6 +2503,9 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
     if ((cfg->flags & MRX_FLAG_NO_RGB) && (cfg->flags & MRX_FLAG_NO_DEPTH))
         return fail(MRX_E_INVALID, "no output selected: MRX_FLAG_NO_RGB and MRX_FLAG_NO_DEPTH together leave "
                                    "neither rgb nor depth to render");
+    if (positionsOf(cfg->flags) && (cfg->flags & MRX_FLAG_NO_DEPTH))
+        return fail(MRX_E_INVALID, "MRX_FLAG_POSITIONS and MRX_FLAG_NO_DEPTH together: the position output is computed "
+                                   "from the depth tensor, which an rgb-only renderer does not have");
     if (cfg->max_instances_per_world > (1u << 20))
         return fail(MRX_E_INVALID, "max_instances_per_world out of range");
     if (cfg->camera_projections)
@@ -2485,6 +2545,7 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
     top->flags = cfg->flags;
     top->variant = cfg->kernel_variant;
     top->ss = supersampleOf(cfg->flags);
+    top->positions = positionsOf(cfg->flags);
     top->device = cfg->device_ids[0];
     const uint32_t n = cfg->num_devices;
     for (uint32_t i = 0; i < n; ++i) {
@@ -2737,7 +2798,7 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
     }
     if (sample && which != MRX_BUF_RGB && which != MRX_BUF_DEPTH && which != MRX_BUF_SEGMASK &&
         which != MRX_BUF_VISIBILITY && which != MRX_BUF_NORMAL) {
-        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT3 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
+        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT4 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
              "not a rendered output: only rgb, depth, normals and the ids tensor have samples");
         return nullptr;
     }
@@ -2769,6 +2830,14 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
         *ndim = 4; *dtype = MRX_DTYPE_U8; ptr = normalPtr;
         if (!ptr) {
             fail(MRX_E_UNSUPPORTED, "normals not rendered: this renderer was created without MRX_FLAG_NORMALS");
+            return nullptr;
+        }
+        break;
+    case MRX_BUF_POSITION:  // the position output: native size whatever the factor, no samples
+        dims[0] = V; dims[1] = r->info.storage_slow; dims[2] = r->info.storage_fast; dims[3] = 4;
+        *ndim = 4; *dtype = MRX_DTYPE_F32; ptr = r->position.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED, "positions not computed: this renderer was created without MRX_FLAG_POSITIONS");
             return nullptr;
         }
         break;
@@ -2881,6 +2950,31 @@ int mrx_resolve(mrx_renderer *r)
         return shardsRun(r, kCmdResolve);
     MRX_HIP(hipSetDevice(r->device));
     MRX_HIP(r->launchResolve());
+    return MRX_OK;
+}
+
+int mrx_positions(mrx_renderer *r)
+{
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    return (int)r->positions;
+}
+
+int mrx_unproject(mrx_renderer *r)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (!r->positions)
+        return fail(MRX_E_UNSUPPORTED, "nothing to unproject: this renderer was created without MRX_FLAG_POSITIONS");
+    if (!r->shards.empty())
+        return shardsRun(r, kCmdUnproject);
+    MRX_HIP(hipSetDevice(r->device));
+    MRX_HIP(r->launchUnproject());
     return MRX_OK;
 }
 

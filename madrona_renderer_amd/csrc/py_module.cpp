@@ -190,6 +190,11 @@ PYBIND11_MODULE(madrona_renderer, m)
     // ... and of the supersampling factor
     m.attr("MRX_FLAG_SUPERSAMPLE_SHIFT") = (uint32_t)MRX_FLAG_SUPERSAMPLE_SHIFT;
     m.attr("MRX_FLAG_SUPERSAMPLE_MASK") = (uint32_t)MRX_FLAG_SUPERSAMPLE_MASK;
+    // ... and of the position output
+    m.attr("MRX_FLAG_POSITIONS") = (uint32_t)MRX_FLAG_POSITIONS;
+    m.attr("MRX_FLAG_POSITIONS_VIEW") = (uint32_t)MRX_FLAG_POSITIONS_VIEW;
+    m.attr("MRX_BUF_POSITION") = (int)MRX_BUF_POSITION;
+    m.attr("MRX_NUM_BUFFERS_EXT4") = (int)MRX_NUM_BUFFERS_EXT4;
     m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
     m.attr("MRX_CONFIG_SIZE") = (uint32_t)sizeof(mrx_config);
 
@@ -309,9 +314,22 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<Sim::WorldInit> &worlds,
                          const std::vector<int> &device_ids, int max_instances_per_world,
                          Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors,
-                         py::object instance_materials, bool normals, py::object instance_labels, int supersample) {
+                         py::object instance_materials, bool normals, py::object instance_labels, int supersample,
+                         py::object positions) {
                  if (supersample < 1 || supersample > 4)
                      throw py::value_error("supersample must be 1, 2, 3 or 4");
+                 // positions: False / None (no output), True or "world", or "view"
+                 uint32_t positionFrame = 0;
+                 if (py::isinstance<py::bool_>(positions))
+                     positionFrame = positions.cast<bool>() ? 1u : 0u;
+                 else if (py::isinstance<py::str>(positions) && positions.cast<std::string>() == "world")
+                     positionFrame = 1;
+                 else if (py::isinstance<py::str>(positions) && positions.cast<std::string>() == "view")
+                     positionFrame = 2;
+                 else if (!positions.is_none())
+                     throw py::value_error("positions must be False, True, \"world\" or \"view\"");
+                 if (positionFrame && render_outputs == Manager::RenderOutputs::RGB)
+                     throw py::value_error("positions need depth: render_outputs RGB renders none");
                  if (mesh_vertices.size() && (mesh_vertices.ndim() != 2 || mesh_vertices.shape(1) != 3))
                      throw py::value_error("mesh_vertices must have shape [N, 3]");
                  if (mesh_uvs.size() && (mesh_uvs.ndim() != 2 || mesh_uvs.shape(1) != 2))
@@ -438,6 +456,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                      cfg.instanceLabelColumn = true;
                  }
                  cfg.supersample = (uint32_t)supersample;
+                 cfg.positions = positionFrame;
                  return new Manager(cfg);
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -464,7 +483,9 @@ PYBIND11_MODULE(madrona_renderer, m)
              // instance_labels = True or a [num_instances] int32 array: the label column (the segmask in both modes)
              py::arg("instance_labels") = py::none(),
              // supersample = s: every view rendered at s * width x s * height and resolved (sample_tensor, resolve)
-             py::arg("supersample") = 1)
+             py::arg("supersample") = 1,
+             // positions = True / "world" / "view": the point every pixel sees (position_tensor, unproject)
+             py::arg("positions") = false)
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -494,6 +515,17 @@ PYBIND11_MODULE(madrona_renderer, m)
              },
              py::arg("name"), py::arg("shard") = py::none())
         .def("resolve", &Manager::resolve)
+        // position output: None, "world" or "view"; f32 [views, H, W, 4], (x, y, z, 1) per hit pixel and zeros on
+        // background (RuntimeError without positions=); the unprojection stage alone
+        .def_property_readonly("positions",
+                               [](const Manager &self) -> py::object {
+                                   const uint32_t f = self.positions();
+                                   return f == 0 ? py::object(py::none()) : py::object(py::str(f == 2 ? "view" : "world"));
+                               })
+        .def("position_tensor",
+             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().positionTensor(shardOf(self, shard))); },
+             py::arg("shard") = py::none())
+        .def("unproject", &Manager::unproject)
         .def("segmask_tensor",
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().segmaskTensor(shardOf(self, shard))); },
              py::arg("shard") = py::none())

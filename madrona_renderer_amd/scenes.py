@@ -67,6 +67,9 @@ class SceneDesc:
     # supersampled antialiasing: 1 ... 4; with s > 1 every view is rendered at s * width x s * height and resolved to
     # width x height (rgb box-filtered; depth, normals and the ids tensor point-sampled)
     supersample: int = 1
+    # the position output (position_tensor()): None / False = none, True or "world" = the world-space point every pixel
+    # sees, "view" = the view-space one; xyzw, w = 0 where nothing was hit
+    positions: object = None
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -304,6 +307,8 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
             extra["instance_labels"] = labels
     if desc.supersample != 1:
         extra["supersample"] = int(desc.supersample)
+    if desc.positions is not None and desc.positions is not False:
+        extra["positions"] = desc.positions
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:

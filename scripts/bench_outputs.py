@@ -3,7 +3,7 @@
 that matter, one JSON line per (configuration, setting):
 
   python scripts/bench_outputs.py [--rounds 5] [--budget-ms 30] [--only headline,c2,...] [--normals] [--labels]
-                                  [--root TREE] [--supersample N[,N...]]
+                                  [--root TREE] [--supersample N[,N...]] [--positions]
 
 --normals times RGBD+N, Depth+N and RGB+N (the surface-normal output beside each selection) beside the
 three settings, in the same alternation; without it the script does what it always did.
@@ -17,6 +17,11 @@ headline and c2): SS = time_renders of the renderer at supersample=N (render + r
 plain renderer of the sample size N*W x N*H, in the same alternation, and RESOLVE = the resolve alone (mark, a batch of
 resolve(), mark) with its bytes -- bytes_per_step of SS minus that of PLAIN -- as a fraction of 8 TB/s; `placement`
 is what the sample tensors' placement search timed (candidates, kept).
+
+--positions measures the unprojection stage instead, RGBD, world frame, on the configurations chosen
+(default: headline and c2): POS = time_renders of the renderer with positions=True (render + unproject), PLAIN =
+time_renders of the renderer without, in the same alternation, and UNPROJECT = the stage alone (mark, a batch of
+unproject(), mark) with its bytes -- bytes_per_step of POS minus that of PLAIN, 20 per pixel -- as a fraction of 8 TB/s.
 
 Every renderer of a configuration is created and warmed first; then the settings alternate within
 the process, `rounds` times, each measurement a batch of back-to-back renders between two events
@@ -129,6 +134,50 @@ def supersample_main(a, scenes):
             del ss, plain
 
 
+def positions_main(a, scenes):
+    import dataclasses
+    only = set(filter(None, a.only.split(","))) or {"headline", "c2"}
+    for key, label, factory, variant in configs(scenes):
+        if key not in only:
+            continue
+        base = factory()
+        pos = scenes.make_renderer(dataclasses.replace(base, positions=True))
+        plain = scenes.make_renderer(base)
+
+        def unproject_us(steps, r=pos):
+            r.mark(0)
+            for _ in range(steps):
+                r.unproject()
+            r.mark(1)
+            return r.elapsed_ms() * 1000.0 / steps
+
+        fns = {"POS": lambda steps, r=pos: us_per_render(r, steps), "PLAIN": lambda steps, r=plain: us_per_render(r, steps),
+               "UNPROJECT": unproject_us}
+        steps = {}
+        for s, fn in fns.items():
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < 0.2:
+                est = fn(20)
+            steps[s] = max(10, min(5000, int(a.budget_ms * 1000.0 / max(est, 1.0))))
+        times = {s: [] for s in fns}
+        for _ in range(a.rounds):
+            for s, fn in fns.items():
+                times[s].append(fn(steps[s]))
+        nbytes = {"POS": int(pos.bytes_per_step()), "PLAIN": int(plain.bytes_per_step())}
+        nbytes["UNPROJECT"] = nbytes["POS"] - nbytes["PLAIN"]
+        for s in fns:
+            med = statistics.median(times[s])
+            print(json.dumps({
+                "config": key, "workload": label, "positions": "world", "setting": s, "views": base.num_views,
+                "native": [base.width, base.height], "steps": steps[s], "rounds": a.rounds,
+                "us_median": round(med, 3), "us_min": round(min(times[s]), 3), "us_max": round(max(times[s]), 3),
+                "us_all": [round(t, 3) for t in times[s]],
+                "ratio_to_plain": round(med / statistics.median(times["PLAIN"]), 4),
+                "bytes": nbytes[s], "frac_8tbps": round(nbytes[s] / (med * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4),
+            }), flush=True)
+        del pos, plain
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--rounds", type=int, default=5)
@@ -138,6 +187,7 @@ def main(argv=None):
     ap.add_argument("--labels", action="store_true", help="also time RGBD with visibility ids and with the label column")
     ap.add_argument("--root", default="", help="import madrona_renderer_amd from this checkout instead")
     ap.add_argument("--supersample", default="", help="factors (2,3,4): measure the resolve stage instead (DESIGN.md 4.18)")
+    ap.add_argument("--positions", action="store_true", help="measure the unprojection stage instead (DESIGN.md 4.19)")
     a = ap.parse_args(argv)
     if a.rounds < 3:
         ap.error("--rounds must be at least 3")
@@ -146,6 +196,8 @@ def main(argv=None):
     from madrona_renderer_amd import scenes
     if a.supersample:
         return supersample_main(a, scenes)
+    if a.positions:
+        return positions_main(a, scenes)
     only = set(filter(None, a.only.split(",")))
     settings = SETTINGS + (NORMAL_SETTINGS if a.normals else ())
     if a.labels:
