@@ -118,6 +118,10 @@ public:
         // Position output (MRX_FLAG_POSITIONS / _VIEW): 0 none, 1 world space, 2 view space; positionTensor() then holds
         // the point every pixel sees, computed from depth by a stage behind every render.  Needs depth rendered.
         uint32_t positions = 0;
+        // Box labels (MRX_FLAG_BOX_LABELS): K in 1 ... 1024, 0 none; boxTensor() then holds the 2-D bounding box and the
+        // pixel count of every label 0 ... K-1 in every view, computed from the segmask by a stage behind every render.
+        // Needs a segmask: Raytracer mode, or Rasterizer mode with the label column.
+        uint32_t boxLabels = 0;
     };
     // the label that stands for the id of the object a row is bound to (MRX_LABEL_OBJECT)
     static constexpr int32_t kLabelObject = INT32_MIN;
@@ -176,6 +180,11 @@ public:
     uint32_t positions() const;
     madrona::py::Tensor positionTensor(uint32_t shard = 0) const;
     void unproject();
+    // box labels: K or 0; i32 [views, K, 5] = (xmin, ymin, xmax, ymax, count) in image coordinates in both modes,
+    // (W, H, -1, -1, 0) for a label no pixel holds (fatal without Config::boxLabels); the box stage alone
+    uint32_t boxLabels() const;
+    madrona::py::Tensor boxTensor(uint32_t shard = 0) const;
+    void boxes();
     // binds every row to the (non-negative) object id its ObjectID column now holds: a spare
     // row gets its geometry, an existing row swaps it (makeEntityRenderable at run time,
     // src/sim.inl:5-8); waits for the device

@@ -151,6 +151,7 @@ enum {
      * fail with MRX_E_UNSUPPORTED and every launch is the one it always was. */
     MRX_FLAG_POSITIONS = 1u << 10,
     MRX_FLAG_POSITIONS_VIEW = 1u << 11
+    /* (bits 12 ... 22: the number of box labels, MRX_FLAG_BOX_LABELS_MASK below) */
 };
 /* supersampled antialiasing: a two-bit field of the flags holds the factor,
  * s = 1 + ((flags >> MRX_FLAG_SUPERSAMPLE_SHIFT) & 3), so s = 1 ... 4 and MRX_FLAG_SUPERSAMPLE(s) sets it.  With s > 1
@@ -163,6 +164,16 @@ enum {
 #define MRX_FLAG_SUPERSAMPLE_SHIFT 8
 #define MRX_FLAG_SUPERSAMPLE_MASK (3u << MRX_FLAG_SUPERSAMPLE_SHIFT)
 #define MRX_FLAG_SUPERSAMPLE(s) ((((uint32_t)(s) - 1u) & 3u) << MRX_FLAG_SUPERSAMPLE_SHIFT)
+/* box labels: an 11-bit field of the flags, bits 12 ... 22, holds K, the number of labels whose
+ * 2-D bounding box and pixel count the renderer computes; MRX_FLAG_BOX_LABELS(k) sets it.  With K in 1 ... 1024 the
+ * MRX_BUF_BOXES tensor is allocated and a box stage runs behind every render, resolve and unprojection on the same
+ * stream: it reads the ids tensor the caller sees, which must be a segmask -- Raytracer mode, or Rasterizer mode with
+ * MRX_FLAG_INSTANCE_LABELS, and in neither beside MRX_FLAG_VISIBILITY_IDS: MRX_E_INVALID otherwise, as is K > 1024.
+ * It combines with everything else and changes no other output.  With the field zero nothing is allocated and every
+ * launch is the one it always was. */
+#define MRX_FLAG_BOX_LABELS_SHIFT 12
+#define MRX_FLAG_BOX_LABELS_MASK (0x7FFu << MRX_FLAG_BOX_LABELS_SHIFT)
+#define MRX_FLAG_BOX_LABELS(k) (((uint32_t)(k) & 0x7FFu) << MRX_FLAG_BOX_LABELS_SHIFT)
 
 /* the label that stands for "the id of the object the row is bound to" (INT32_MIN): what the column starts at */
 #define MRX_LABEL_OBJECT ((int32_t)(-2147483647 - 1))
@@ -308,7 +319,16 @@ enum {
      * R(q) * P + c with the view's camRot / camPos rows -- the inverse of the camera transform for a unit quaternion
      * only: the quaternion is used as given, as everywhere.  An allocation of its own, one per shard. */
     MRX_BUF_POSITION = 14,
-    MRX_NUM_BUFFERS_EXT4 = 15
+    MRX_NUM_BUFFERS_EXT4 = 15,
+    /* i32 [views,K,5], needs the MRX_FLAG_BOX_LABELS field: row (v, l) is (xmin, ymin, xmax, ymax, count) of the pixels
+     * of view v whose value in the ids tensor the caller sees (MRX_BUF_SEGMASK; the resolved one on a supersampled
+     * renderer) equals l -- the smallest and largest image column and image row (row 0 up), all four inclusive, and the
+     * number of pixels; (W, H, -1, -1, 0) where there is none (Raytracer mode: W = H = res).  Image coordinates in both
+     * modes: the stage undoes the Raytracer transposition.  Ids outside 0 ... K-1 -- the background -1, negative
+     * labels, labels >= K -- belong to no row.  An allocation of its own, one per shard; it has no
+     * sample tensor. */
+    MRX_BUF_BOXES = 15,
+    MRX_NUM_BUFFERS_EXT5 = 16
 };
 
 enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2 };
@@ -372,6 +392,20 @@ int mrx_resolve(mrx_renderer *r);
  *    MRX_E_UNSUPPORTED without the output. */
 int mrx_positions(mrx_renderer *r);
 int mrx_unproject(mrx_renderer *r);
+
+/* -- box labels (MRX_FLAG_BOX_LABELS).  mrx_box_labels returns K, or 0 without the output; MRX_E_INVALID for a null
+ *    renderer.  With the output, mrx_step / mrx_render / mrx_time_renders / the first frame of mrx_create enqueue the
+ *    render, the resolve and the unprojection where there are any, and then the box stage.  mrx_boxes enqueues that
+ *    stage alone on the renderer's stream (every shard's on its own), as mrx_unproject does: what a caller that wrote
+ *    the ids tensor itself, or timed the stage, calls.  MRX_E_UNSUPPORTED without the output.
+ *    mrx_box_plan is host arithmetic, for tests: the answer of the stage's launch checks for a tensor of `views` views
+ *    of nslow rows of nfast pixels and K labels on num_cus compute units (null_pointers != 0: with a null tensor) --
+ *    MRX_E_INVALID where the launch would be refused, 0 where it would enqueue nothing, otherwise the number of
+ *    workgroups per view (forced_parts: MRX_BOX_PARTS, 0 = the automatic rule).  It touches no device. */
+int mrx_box_labels(mrx_renderer *r);
+int mrx_boxes(mrx_renderer *r);
+int mrx_box_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t k, uint32_t num_cus, uint32_t forced_parts,
+                 int null_pointers);
 
 /* -- debug readback: waits for the stream, then copies the first `bytes`
  *    bytes of a buffer to host memory (what /root/reference/src/dump.cpp:53-70

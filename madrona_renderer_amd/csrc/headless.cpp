@@ -16,6 +16,10 @@
 //                                          --dump-last-frame writes the resolved images)
 //                     [--positions [world|view]]   (the position output, world space unless `view`; --dump-last-frame
 //                                                   also writes NAME.points.ply, the hit pixels' points; needs depth)
+//                     [--boxes K]   (1 ... 1024: the bounding box and pixel count of labels 0 ... K-1 in every view;
+//                                    --dump-last-frame also writes NAME.boxes.txt, one line
+//                                    `view label xmin ymin xmax ymax count` per non-empty row; needs a segmask: rt, or
+//                                    rast with --instance-labels)
 //
 // --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
 // renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
@@ -89,6 +93,8 @@ struct Args {
     // --positions [world|view]: the position output (0 none, 1 world, 2 view); --dump-last-frame then also writes
     // NAME.points.ply
     uint32_t positions = 0;
+    // --boxes K: box labels, 1 ... 1024; --dump-last-frame then also writes NAME.boxes.txt
+    uint32_t boxes = 0;
 };
 
 // a number of the whole argument, finite
@@ -107,7 +113,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]] [--boxes K]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -207,6 +213,16 @@ Args parse(int argc, char **argv)
                 std::exit(EXIT_FAILURE);
             }
             a.supersample = (uint32_t)v;
+        } else if (!std::strcmp(argv[i], "--boxes") && i + 1 < argc) {
+            const char *s = argv[++i];
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long v = std::strtoull(s, &end, 10);
+            if (!*s || *s == '-' || *s == '+' || *end || errno != 0 || v < 1 || v > 1024) {
+                std::fprintf(stderr, "--boxes: not a number of labels from 1 to 1024: %s\n", s);
+                std::exit(EXIT_FAILURE);
+            }
+            a.boxes = (uint32_t)v;
         } else if (!std::strcmp(argv[i], "--positions")) {
             // the frame is optional: the next argument is taken for it unless it is another option
             a.positions = 1;
@@ -252,6 +268,10 @@ Args parse(int argc, char **argv)
     }
     if (a.positions && a.outputs == Manager::RenderOutputs::RGB) {
         std::fprintf(stderr, "--positions: positions are computed from depth, which is not rendered with --outputs rgb\n");
+        std::exit(EXIT_FAILURE);
+    }
+    if (a.boxes && a.mode == Mode::Rasterizer && !a.hasLabels) {
+        std::fprintf(stderr, "--boxes: boxes are computed from the segmask, which rast has only with --instance-labels\n");
         std::exit(EXIT_FAILURE);
     }
     return a;
@@ -475,6 +495,29 @@ bool dumpPly(const std::string &name, mrx_renderer *shard, uint32_t numImages, u
     return ok;
 }
 
+// NAME.boxes.txt of --boxes: one line `view label xmin ymin xmax ymax count` per non-empty row of the box tensor of
+// the first `numImages` views, in the tensor's order
+bool dumpBoxes(const std::string &name, mrx_renderer *shard, uint32_t numImages, uint32_t K)
+{
+    std::vector<int32_t> rows((size_t)numImages * K * 5);
+    if (mrx_copy_to_host(shard, MRX_BUF_BOXES, rows.data(), rows.size() * sizeof(int32_t)) != MRX_OK) {
+        std::fprintf(stderr, "%s\n", mrx_last_error());
+        return false;
+    }
+    FILE *f = std::fopen((name + ".boxes.txt").c_str(), "w");
+    bool ok = f != nullptr;
+    for (size_t i = 0; ok && i < (size_t)numImages * K; ++i) {
+        const int32_t *b = &rows[5 * i];
+        if (b[4] > 0)
+            ok = std::fprintf(f, "%zu %zu %d %d %d %d %d\n", i / K, i % K, b[0], b[1], b[2], b[3], b[4]) > 0;
+    }
+    if (f && std::fclose(f) != 0)
+        ok = false;
+    if (!ok)
+        std::fprintf(stderr, "cannot write %s.boxes.txt\n", name.c_str());
+    return ok;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -571,6 +614,7 @@ int main(int argc, char **argv)
     cfg.normals = args.normals;
     cfg.supersample = args.supersample;
     cfg.positions = args.positions;
+    cfg.boxLabels = args.boxes;
 
     Manager mgr(cfg);              // aborts (FATAL) on failure, like the reference
     mgr.sync();
@@ -610,6 +654,8 @@ int main(int argc, char **argv)
             if (args.positions)
                 ok = dumpPly(name + ".points", sh, hi - lo, args.width, resY,
                              args.outputs != Manager::RenderOutputs::Depth) && ok;
+            if (args.boxes)
+                ok = dumpBoxes(name, sh, hi - lo, args.boxes) && ok;
         }
     }
     if (!ok)

@@ -117,6 +117,9 @@ Manager::Manager(const Config &cfg)
         detail::fatal("positions " + std::to_string(cfg.positions) + " is not 0 (none), 1 (world) or 2 (view)");
     if (cfg.positions)
         c.flags |= cfg.positions == 2 ? MRX_FLAG_POSITIONS | MRX_FLAG_POSITIONS_VIEW : MRX_FLAG_POSITIONS;
+    if (cfg.boxLabels > 1024)
+        detail::fatal("boxLabels " + std::to_string(cfg.boxLabels) + " is not in 0 ... 1024");
+    c.flags |= MRX_FLAG_BOX_LABELS(cfg.boxLabels);
     if (cfg.renderOutputs == RenderOutputs::Depth)
         c.flags |= MRX_FLAG_NO_RGB;
     else if (cfg.renderOutputs == RenderOutputs::RGB)
@@ -235,6 +238,16 @@ Tensor Manager::positionTensor(uint32_t shard) const { return impl_->wrap(MRX_BU
 void Manager::unproject()
 {
     if (mrx_unproject(impl_->r) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+uint32_t Manager::boxLabels() const { return (uint32_t)mrx_box_labels(impl_->r); }
+
+Tensor Manager::boxTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_BOXES, shard); }
+
+void Manager::boxes()
+{
+    if (mrx_boxes(impl_->r) != MRX_OK)
         detail::fatal(mrx_last_error());
 }
 

@@ -28,6 +28,7 @@
 #include "raster.hpp"
 #include "resolve.hpp"
 #include "unproject.hpp"
+#include "boxes.hpp"
 
 namespace {
 
@@ -380,6 +381,11 @@ struct mrx_renderer {
     // and the placement search.  0: no pointer, no further launch.
     uint32_t positions = 0;
     DevBuf<float> position;
+    // box labels: K (mrx_box_labels) and the [views][K][5] tensor the box stage writes from the
+    // ids tensor the caller sees -- an allocation of its own, outside allocOutputs and the placement search.  0: no
+    // pointer, no further launch.  boxParts: MRX_BOX_PARTS, the forced number of workgroups per view (0: automatic).
+    uint32_t boxLabels = 0, boxParts = 0;
+    DevBuf<int32_t> boxes;
     DevBuf<unsigned long long> stamps;
     // XCD phase feedback (raster.hip): a host-mapped word workgroup 0 reports its XCC id to
     uint32_t *xccHost = nullptr, *xccDev = nullptr;
@@ -432,14 +438,32 @@ struct mrx_renderer {
     DevBuf<mrx::ViewLight> lightDev;
     mrx::ViewLight *lightStage = nullptr;
 
-    // a step's launches: the render, on a supersampled renderer the resolve behind it, and with the position output
-    // the unprojection stage behind both, all on the same stream
+    // a step's launches: the render, on a supersampled renderer the resolve behind it, with the position output the
+    // unprojection stage behind both and with box labels the box stage last, all on the same stream
     hipError_t launch()
     {
         hipError_t e = launchRender();
         if (e == hipSuccess && ss > 1)
             e = launchResolve();
-        return e == hipSuccess && positions ? launchUnproject() : e;
+        if (e == hipSuccess && positions)
+            e = launchUnproject();
+        return e == hipSuccess && boxLabels ? launchBoxes() : e;
+    }
+
+    // (the ids pointer is read from the render's parameters at every launch: the placement search re-binds it)
+    hipError_t launchBoxes()
+    {
+        mrx::BoxParams q {};
+        q.ids = ss > 1 ? outIds.ptr : params.ids;
+        q.out = boxes.ptr;
+        q.numViews = params.numViews;
+        q.nfast = info.storage_fast;
+        q.nslow = info.storage_slow;
+        q.K = boxLabels;
+        q.transposed = params.transposed;
+        q.numCUs = params.numCUs;
+        q.forcedParts = boxParts;
+        return mrx::launchBoxes(q, stream);
     }
 
     // (depth, the constants and the table pointer are read from the render's parameters at every launch: the placement
@@ -535,6 +559,7 @@ struct mrx_renderer {
         rgb.release(); depth.release(); ids.release(); normal.release(); stamps.release();
         outRgb.release(); outDepth.release(); outIds.release(); outNormal.release();
         position.release();
+        boxes.release();
         if (xccHost) (void)hipHostFree(xccHost);
         bvhNodes.release(); bvhLeafTris.release(); worldInstStart.release();
         viewWorld.release(); instKBase.release(); objInfo.release();
@@ -557,7 +582,7 @@ struct mrx_renderer {
 // handshake.  Workers spin on their word for a while after a command (a simulation loop calls
 // step() every few tens of microseconds) and then sleep in a futex; MRX_SHARD_SPIN_US sets how
 // long (default 200), MRX_SHARD_THREADS=0 restores the serial form (startShardWorkers).
-enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdUnproject, kCmdExit };
+enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdUnproject, kCmdBoxes, kCmdExit };
 
 struct ShardWorker {
     std::vector<mrx_renderer *> shards;         // the shards of ONE device, launched in order
@@ -640,6 +665,10 @@ int groupRun(const std::vector<mrx_renderer *> &shards, int cmd, int steps, bool
     case kCmdUnproject:
         for (mrx_renderer *sh : shards)
             MRX_HIP(sh->launchUnproject());
+        return MRX_OK;
+    case kCmdBoxes:
+        for (mrx_renderer *sh : shards)
+            MRX_HIP(sh->launchBoxes());
         return MRX_OK;
     case kCmdSync:
         for (mrx_renderer *sh : shards)
@@ -2397,6 +2426,26 @@ static int allocPositions(mrx_renderer &r)
     return MRX_OK;
 }
 
+static uint32_t boxLabelsOf(uint32_t flags)
+{
+    return (flags & MRX_FLAG_BOX_LABELS_MASK) >> MRX_FLAG_BOX_LABELS_SHIFT;
+}
+
+// the box tensor of a renderer with box labels: one allocation of its own, [views][K][5] int32; the stage's bytes on
+// top of the rest: 4 read per native pixel and the tensor written
+static int allocBoxes(mrx_renderer &r)
+{
+    const uint64_t px = (uint64_t)r.params.numViews * r.info.storage_fast * r.info.storage_slow;
+    if (px > mrx::kBoxMaxPixels)
+        return fail(MRX_E_INVALID, "box labels: more than 2^32 - 1 native pixels");
+    const uint64_t cells = (uint64_t)r.params.numViews * r.boxLabels * 5u;
+    MRX_HIP(r.boxes.alloc((size_t)cells));
+    r.info.bytes_per_step += px * 4ull + cells * 4ull;
+    if (const char *dbg = std::getenv("MRX_BOX_PARTS"))     // tests: the merge path at tiny sizes
+        r.boxParts = (uint32_t)std::max(0, std::atoi(dbg));
+    return MRX_OK;
+}
+
 // one renderer on one device (mrx_create proper, or one shard of a multi-device renderer)
 static int createOne(const mrx_config &cfg, mrx_renderer **out)
 {
@@ -2427,6 +2476,9 @@ static int createOne(const mrx_config &cfg, mrx_renderer **out)
     r->positions = positionsOf(cfg.flags);
     if (rc == MRX_OK && r->positions)
         rc = allocPositions(*r);
+    r->boxLabels = boxLabelsOf(cfg.flags);
+    if (rc == MRX_OK && r->boxLabels)
+        rc = allocBoxes(*r);
     if (rc == MRX_OK) {
         hipError_t e = hipEventCreate(&r->ev0);
         if (e == hipSuccess) e = hipEventCreate(&r->ev1);
@@ -2506,6 +2558,23 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
     if (positionsOf(cfg->flags) && (cfg->flags & MRX_FLAG_NO_DEPTH))
         return fail(MRX_E_INVALID, "MRX_FLAG_POSITIONS and MRX_FLAG_NO_DEPTH together: the position output is computed "
                                    "from the depth tensor, which an rgb-only renderer does not have");
+    if (const uint32_t k = boxLabelsOf(cfg->flags)) {
+        if (k > mrx::kBoxMaxLabels)
+            return fail(MRX_E_INVALID, "MRX_FLAG_BOX_LABELS: " + std::to_string(k) + " labels, more than 1024");
+        if (cfg->flags & MRX_FLAG_VISIBILITY_IDS)
+            return fail(MRX_E_INVALID, "MRX_FLAG_BOX_LABELS and MRX_FLAG_VISIBILITY_IDS together: the box stage reads "
+                                       "the segmask, and the ids tensor of this renderer holds visibility ids");
+        if (cfg->render_mode == MRX_MODE_RASTERIZER && !(cfg->flags & MRX_FLAG_INSTANCE_LABELS))
+            return fail(MRX_E_INVALID, "MRX_FLAG_BOX_LABELS in Rasterizer mode needs MRX_FLAG_INSTANCE_LABELS: the box "
+                                       "stage reads the segmask, which this renderer does not have");
+        // (mrx_info's storage is the native size: the resolved tensor is what the stage reads)
+        const uint64_t side = cfg->render_mode == MRX_MODE_RAYTRACER ? cfg->view_width : cfg->view_height;
+        uint64_t views = 0;
+        for (uint32_t w = 0; w < cfg->num_worlds; ++w)
+            views += cfg->worlds[w].num_cameras;
+        if (views * cfg->view_width * side > mrx::kBoxMaxPixels)
+            return fail(MRX_E_INVALID, "MRX_FLAG_BOX_LABELS: more than 2^32 - 1 native pixels");
+    }
     if (cfg->max_instances_per_world > (1u << 20))
         return fail(MRX_E_INVALID, "max_instances_per_world out of range");
     if (cfg->camera_projections)
@@ -2546,6 +2615,7 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
     top->variant = cfg->kernel_variant;
     top->ss = supersampleOf(cfg->flags);
     top->positions = positionsOf(cfg->flags);
+    top->boxLabels = boxLabelsOf(cfg->flags);
     top->device = cfg->device_ids[0];
     const uint32_t n = cfg->num_devices;
     for (uint32_t i = 0; i < n; ++i) {
@@ -2798,7 +2868,7 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
     }
     if (sample && which != MRX_BUF_RGB && which != MRX_BUF_DEPTH && which != MRX_BUF_SEGMASK &&
         which != MRX_BUF_VISIBILITY && which != MRX_BUF_NORMAL) {
-        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT4 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
+        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT5 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
              "not a rendered output: only rgb, depth, normals and the ids tensor have samples");
         return nullptr;
     }
@@ -2838,6 +2908,14 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
         *ndim = 4; *dtype = MRX_DTYPE_F32; ptr = r->position.ptr;
         if (!ptr) {
             fail(MRX_E_UNSUPPORTED, "positions not computed: this renderer was created without MRX_FLAG_POSITIONS");
+            return nullptr;
+        }
+        break;
+    case MRX_BUF_BOXES:     // box labels: (xmin, ymin, xmax, ymax, count) per view and label
+        dims[0] = V; dims[1] = r->boxLabels; dims[2] = 5;
+        *ndim = 3; *dtype = MRX_DTYPE_I32; ptr = r->boxes.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED, "boxes not computed: this renderer was created without MRX_FLAG_BOX_LABELS");
             return nullptr;
         }
         break;
@@ -2976,6 +3054,50 @@ int mrx_unproject(mrx_renderer *r)
     MRX_HIP(hipSetDevice(r->device));
     MRX_HIP(r->launchUnproject());
     return MRX_OK;
+}
+
+int mrx_box_labels(mrx_renderer *r)
+{
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    return (int)r->boxLabels;
+}
+
+int mrx_boxes(mrx_renderer *r)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (!r->boxLabels)
+        return fail(MRX_E_UNSUPPORTED, "no boxes to compute: this renderer was created without MRX_FLAG_BOX_LABELS");
+    if (!r->shards.empty())
+        return shardsRun(r, kCmdBoxes);
+    MRX_HIP(hipSetDevice(r->device));
+    MRX_HIP(r->launchBoxes());
+    return MRX_OK;
+}
+
+int mrx_box_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t k, uint32_t num_cus, uint32_t forced_parts,
+                 int null_pointers)
+{
+    static const int32_t in = 0;
+    static int32_t outCell = 0;             // (never dereferenced: checkBoxes looks at the pointers' values only)
+    mrx::BoxParams q {};
+    q.ids = null_pointers ? nullptr : &in;
+    q.out = null_pointers ? nullptr : &outCell;
+    q.numViews = views; q.nfast = nfast; q.nslow = nslow;
+    q.K = k;
+    q.numCUs = num_cus;
+    q.forcedParts = forced_parts;
+    if (mrx::checkBoxes(q) != hipSuccess)
+        return fail(MRX_E_INVALID, "the box stage refuses these arguments");
+    if ((uint64_t)views * nfast * nslow == 0)
+        return 0;
+    return (int)mrx::boxParts(views, nslow, num_cus, forced_parts);
 }
 
 int mrx_copy_to_host(mrx_renderer *r, int which, void *dst, uint64_t bytes)

@@ -195,6 +195,11 @@ PYBIND11_MODULE(madrona_renderer, m)
     m.attr("MRX_FLAG_POSITIONS_VIEW") = (uint32_t)MRX_FLAG_POSITIONS_VIEW;
     m.attr("MRX_BUF_POSITION") = (int)MRX_BUF_POSITION;
     m.attr("MRX_NUM_BUFFERS_EXT4") = (int)MRX_NUM_BUFFERS_EXT4;
+    // ... and of the box labels
+    m.attr("MRX_FLAG_BOX_LABELS_SHIFT") = (uint32_t)MRX_FLAG_BOX_LABELS_SHIFT;
+    m.attr("MRX_FLAG_BOX_LABELS_MASK") = (uint32_t)MRX_FLAG_BOX_LABELS_MASK;
+    m.attr("MRX_BUF_BOXES") = (int)MRX_BUF_BOXES;
+    m.attr("MRX_NUM_BUFFERS_EXT5") = (int)MRX_NUM_BUFFERS_EXT5;
     m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
     m.attr("MRX_CONFIG_SIZE") = (uint32_t)sizeof(mrx_config);
 
@@ -315,7 +320,19 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<int> &device_ids, int max_instances_per_world,
                          Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors,
                          py::object instance_materials, bool normals, py::object instance_labels, int supersample,
-                         py::object positions) {
+                         py::object positions, py::object boxes) {
+                 // boxes: None / 0 / False (no output) or K, an int in 1 ... 1024
+                 uint32_t boxLabels = 0;
+                 if (py::isinstance<py::bool_>(boxes)) {
+                     if (boxes.cast<bool>())
+                         throw py::value_error("boxes must be None or an int in 1 ... 1024 (the number of labels)");
+                 } else if (py::isinstance<py::int_>(boxes)) {
+                     const long long k = boxes.cast<long long>();   // (an int beyond long long: pybind's cast error)
+                     if (k < 0 || k > 1024)
+                         throw py::value_error("boxes must be None or an int in 1 ... 1024 (the number of labels)");
+                     boxLabels = (uint32_t)k;
+                 } else if (!boxes.is_none())
+                     throw py::value_error("boxes must be None or an int in 1 ... 1024 (the number of labels)");
                  if (supersample < 1 || supersample > 4)
                      throw py::value_error("supersample must be 1, 2, 3 or 4");
                  // positions: False / None (no output), True or "world", or "view"
@@ -457,6 +474,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                  }
                  cfg.supersample = (uint32_t)supersample;
                  cfg.positions = positionFrame;
+                 cfg.boxLabels = boxLabels;
                  return new Manager(cfg);
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -485,7 +503,9 @@ PYBIND11_MODULE(madrona_renderer, m)
              // supersample = s: every view rendered at s * width x s * height and resolved (sample_tensor, resolve)
              py::arg("supersample") = 1,
              // positions = True / "world" / "view": the point every pixel sees (position_tensor, unproject)
-             py::arg("positions") = false)
+             py::arg("positions") = false,
+             // boxes = K: the bounding box and pixel count of labels 0 ... K-1 in every view (box_tensor, boxes)
+             py::arg("boxes") = py::none())
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -526,6 +546,13 @@ PYBIND11_MODULE(madrona_renderer, m)
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().positionTensor(shardOf(self, shard))); },
              py::arg("shard") = py::none())
         .def("unproject", &Manager::unproject)
+        // box labels: K or 0; i32 [views, K, 5] = (xmin, ymin, xmax, ymax, count) (RuntimeError without boxes=); the
+        // box stage alone
+        .def_property_readonly("box_labels", &Manager::boxLabels)
+        .def("box_tensor",
+             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().boxTensor(shardOf(self, shard))); },
+             py::arg("shard") = py::none())
+        .def("boxes", &Manager::boxes)
         .def("segmask_tensor",
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().segmaskTensor(shardOf(self, shard))); },
              py::arg("shard") = py::none())

@@ -70,6 +70,9 @@ class SceneDesc:
     # the position output (position_tensor()): None / False = none, True or "world" = the world-space point every pixel
     # sees, "view" = the view-space one; xyzw, w = 0 where nothing was hit
     positions: object = None
+    # box labels (box_tensor()): None / 0 / False = none, K = the 2-D bounding box and the pixel count of every label
+    # 0 ... K-1 in every view; needs a segmask (Raytracer mode, or instance_labels)
+    boxes: object = None
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -309,6 +312,8 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
         extra["supersample"] = int(desc.supersample)
     if desc.positions is not None and desc.positions is not False:
         extra["positions"] = desc.positions
+    if desc.boxes is not None and desc.boxes is not False:
+        extra["boxes"] = desc.boxes
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:
