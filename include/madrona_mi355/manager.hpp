@@ -122,6 +122,11 @@ public:
         // pixel count of every label 0 ... K-1 in every view, computed from the segmask by a stage behind every render.
         // Needs a segmask: Raytracer mode, or Rasterizer mode with the label column.
         uint32_t boxLabels = 0;
+        // Packed observation output (MRX_FLAG_OBSERVATIONS): the field's value, MRX_FLAG_OBSERVATIONS(layout, dtype,
+        // stack), 0 none; observationTensor() then holds the channel-first tensor a policy takes -- [views, S * C, H, W]
+        // in float32, float16, bfloat16 or uint8 -- packed from rgb and depth by a stage behind every render.  A
+        // layout needs the outputs it reads rendered.
+        uint32_t observations = 0;
     };
     // the label that stands for the id of the object a row is bound to (MRX_LABEL_OBJECT)
     static constexpr int32_t kLabelObject = INT32_MIN;
@@ -185,6 +190,16 @@ public:
     uint32_t boxLabels() const;
     madrona::py::Tensor boxTensor(uint32_t shard = 0) const;
     void boxes();
+    // packed observation output: the field or 0; [views, S * C, H, W] in the field's element type, image rows and
+    // columns in both modes, frame 0 the oldest (fatal without Config::observations); the reset column u8 [views]
+    // (fatal with a stack of 1); the observation stage alone -- on a stacked renderer one more frame; the depth range
+    // (lo = hi = 0: none), whose setter restarts every stack
+    uint32_t observations() const;
+    madrona::py::Tensor observationTensor(uint32_t shard = 0) const;
+    madrona::py::Tensor observationResetTensor(uint32_t shard = 0) const;
+    void observe();
+    void setObservationDepthRange(float lo, float hi);
+    void observationDepthRange(float *lo, float *hi) const;
     // binds every row to the (non-negative) object id its ObjectID column now holds: a spare
     // row gets its geometry, an existing row swaps it (makeEntityRenderable at run time,
     // src/sim.inl:5-8); waits for the device

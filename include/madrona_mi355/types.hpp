@@ -36,7 +36,7 @@ struct GPUDevice;
 
 namespace py {
 
-enum class TensorElementType { UInt8, Int8, Int16, Int32, Int64, Float16, Float32 };
+enum class TensorElementType { UInt8, Int8, Int16, Int32, Int64, Float16, Float32, BFloat16 };
 
 // Non-owning view of a device buffer (stand-in for madrona::py::Tensor as the
 // reference uses it: /root/reference/src/mgr.cpp:192,552-557,609).
@@ -66,7 +66,7 @@ public:
     {
         switch (type_) {
         case TensorElementType::UInt8: case TensorElementType::Int8: return 1;
-        case TensorElementType::Int16: case TensorElementType::Float16: return 2;
+        case TensorElementType::Int16: case TensorElementType::Float16: case TensorElementType::BFloat16: return 2;
         case TensorElementType::Int64: return 8;
         default: return 4;
         }

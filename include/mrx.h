@@ -152,6 +152,7 @@ enum {
     MRX_FLAG_POSITIONS = 1u << 10,
     MRX_FLAG_POSITIONS_VIEW = 1u << 11
     /* (bits 12 ... 22: the number of box labels, MRX_FLAG_BOX_LABELS_MASK below) */
+    /* (bits 23 ... 30: the packed observation output, MRX_FLAG_OBS_MASK below) */
 };
 /* supersampled antialiasing: a two-bit field of the flags holds the factor,
  * s = 1 + ((flags >> MRX_FLAG_SUPERSAMPLE_SHIFT) & 3), so s = 1 ... 4 and MRX_FLAG_SUPERSAMPLE(s) sets it.  With s > 1
@@ -174,6 +175,30 @@ enum {
 #define MRX_FLAG_BOX_LABELS_SHIFT 12
 #define MRX_FLAG_BOX_LABELS_MASK (0x7FFu << MRX_FLAG_BOX_LABELS_SHIFT)
 #define MRX_FLAG_BOX_LABELS(k) (((uint32_t)(k) & 0x7FFu) << MRX_FLAG_BOX_LABELS_SHIFT)
+/* packed observation output: an 8-bit field of the flags, bits 23 ... 30 -- the layout in bits
+ * 23 ... 25 (MRX_OBS_RGB ... MRX_OBS_YD, 0: no output), the element type in bits 26 and 27 (MRX_OBS_F32 ... MRX_OBS_U8)
+ * and S - 1 in bits 28 ... 30, S = 1 ... 8 the number of stacked frames; MRX_FLAG_OBSERVATIONS(layout, dtype, stack)
+ * sets it.  With a layout the MRX_BUF_OBSERVATION tensor [views, S * C, H, W] is allocated -- and, with S > 1, the
+ * MRX_BUF_OBSERVATION_RESET column -- and an observation stage runs last behind every render on the same stream: it
+ * reads the rgb and depth tensors the caller sees and writes the tensor a policy takes, channel first.  MRX_E_INVALID:
+ * a layout with colour beside MRX_FLAG_NO_RGB, a layout with depth beside MRX_FLAG_NO_DEPTH, layout values 6 and 7,
+ * element type or stack bits with layout 0.  It combines with everything else and changes no other output.  With the
+ * field zero nothing is allocated and every launch is the one it always was. */
+#define MRX_FLAG_OBS_SHIFT 23
+#define MRX_FLAG_OBS_MASK (0xFFu << MRX_FLAG_OBS_SHIFT)
+#define MRX_FLAG_OBS_LAYOUT_MASK (7u << MRX_FLAG_OBS_SHIFT)
+#define MRX_FLAG_OBS_DTYPE_SHIFT 26
+#define MRX_FLAG_OBS_DTYPE_MASK (3u << MRX_FLAG_OBS_DTYPE_SHIFT)
+#define MRX_FLAG_OBS_STACK_SHIFT 28
+#define MRX_FLAG_OBS_STACK_MASK (7u << MRX_FLAG_OBS_STACK_SHIFT)
+#define MRX_FLAG_OBSERVATIONS(layout, dtype, stack)                                                                      \
+    ((((uint32_t)(layout) & 7u) << MRX_FLAG_OBS_SHIFT) | (((uint32_t)(dtype) & 3u) << MRX_FLAG_OBS_DTYPE_SHIFT) |        \
+     ((((uint32_t)(stack) - 1u) & 7u) << MRX_FLAG_OBS_STACK_SHIFT))
+/* layouts: the channels of one frame -- rgb (C = 3), rgb and depth (4), depth (1), luma (1), luma and depth (2); luma
+ * is y = (77 r + 150 g + 29 b + 128) >> 8 */
+enum { MRX_OBS_NONE = 0, MRX_OBS_RGB = 1, MRX_OBS_RGBD = 2, MRX_OBS_D = 3, MRX_OBS_Y = 4, MRX_OBS_YD = 5 };
+/* element types: float32, float16, bfloat16 (round to nearest even), uint8 */
+enum { MRX_OBS_F32 = 0, MRX_OBS_F16 = 1, MRX_OBS_BF16 = 2, MRX_OBS_U8 = 3 };
 
 /* the label that stands for "the id of the object the row is bound to" (INT32_MIN): what the column starts at */
 #define MRX_LABEL_OBJECT ((int32_t)(-2147483647 - 1))
@@ -328,10 +353,23 @@ enum {
      * labels, labels >= K -- belong to no row.  An allocation of its own, one per shard; it has no
      * sample tensor. */
     MRX_BUF_BOXES = 15,
-    MRX_NUM_BUFFERS_EXT5 = 16
+    MRX_NUM_BUFFERS_EXT5 = 16,
+    /* f32 / f16 / bf16 / u8 [views, S*C, H, W], needs the MRX_FLAG_OBSERVATIONS field: channel f * C + c is channel c of
+     * frame f, frame 0 the oldest and S - 1 the one just rendered; (H, W) are image rows and columns in both modes
+     * (Raytracer: H = W = res, the stage undoes the transposition).  A colour byte b is (float)b * (1.0f / 255.0f)
+     * (u8: b itself); depth is the depth tensor's value, or with a range (mrx_set_observation_depth_range)
+     * d == 0 ? 1 : clamp((d - lo) * inv, 0, 1); u8 stores (uint32)(clamp(o, 0, 1) * 255.0f + 0.5f).
+     * With S > 1 the tensor is state: every run of the stage pushes a frame.  An allocation of its own, one per shard;
+     * it has no sample tensor. */
+    MRX_BUF_OBSERVATION = 16,
+    /* u8 [views], needs S > 1: a view whose byte is not zero when the stage runs has every frame of its stack set to
+     * the current one.  Written on the device, like a pose, on the renderer's stream; starts at 1, and the renderer
+     * clears it behind every run of the stage, so a flag is consumed by exactly the next run. */
+    MRX_BUF_OBSERVATION_RESET = 17,
+    MRX_NUM_BUFFERS_EXT6 = 18
 };
 
-enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2 };
+enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2, MRX_DTYPE_F16 = 3, MRX_DTYPE_BF16 = 4 };
 
 typedef struct {
     uint32_t num_worlds, num_views, num_instances;
@@ -406,6 +444,21 @@ int mrx_box_labels(mrx_renderer *r);
 int mrx_boxes(mrx_renderer *r);
 int mrx_box_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t k, uint32_t num_cus, uint32_t forced_parts,
                  int null_pointers);
+
+/* -- packed observation output (MRX_FLAG_OBSERVATIONS).  mrx_observations returns the field as it lies in the flags
+ *    (flags & MRX_FLAG_OBS_MASK: a positive int, read with the mask macros), or 0 without the output; MRX_E_INVALID for a null renderer.  With the
+ *    output, mrx_step / mrx_render / mrx_time_renders / the first frame of mrx_create enqueue the render, the resolve,
+ *    the unprojection and the boxes where there are any, and then the observation stage.  mrx_observe enqueues that
+ *    stage alone on the renderer's stream (every shard's on its own), as mrx_unproject does; on a stacked renderer it
+ *    pushes one more frame.  mrx_set_observation_depth_range stores the range depth is normalised to, 0 <= lo < hi,
+ *    both finite (lo = hi = 0: no range, depth is stored raw; anything else MRX_E_INVALID) -- the stage then uses
+ *    inv = 1.0f / (hi - lo) -- marks every view reset and enqueues the stage: frames packed under another range are
+ *    meaningless.  A renderer starts without a range.  MRX_E_INVALID for a layout without depth beside a range.
+ *    mrx_observation_depth_range reads it back (0, 0 without).  MRX_E_UNSUPPORTED without the output. */
+int mrx_observations(mrx_renderer *r);
+int mrx_observe(mrx_renderer *r);
+int mrx_set_observation_depth_range(mrx_renderer *r, float lo, float hi);
+int mrx_observation_depth_range(mrx_renderer *r, float *lo, float *hi);
 
 /* -- debug readback: waits for the stream, then copies the first `bytes`
  *    bytes of a buffer to host memory (what /root/reference/src/dump.cpp:53-70

@@ -18,8 +18,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "bvh.cpp", "mrx_api.cpp", "assets.cpp", "ktx2.cpp"]
-HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "assets.hpp", "bc7_tables.inc",
+HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "observe.hip", "bvh.cpp", "mrx_api.cpp", "assets.cpp", "ktx2.cpp"]
+HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "observe.hpp", "assets.hpp", "bc7_tables.inc",
                           "../../include/mrx.h"]
 MGR_SOURCES = ["manager.cpp"]
 MGR_DEPS = MGR_SOURCES + ["../../include/madrona_mi355/manager.hpp",

@@ -20,6 +20,11 @@
 //                                    --dump-last-frame also writes NAME.boxes.txt, one line
 //                                    `view label xmin ymin xmax ymax count` per non-empty row; needs a segmask: rt, or
 //                                    rast with --instance-labels)
+//                     [--observations CHANNELS[,DTYPE[,STACK]]]   (the packed observation output: rgb, rgbd, d, y or yd;
+//                                    float32 (default), float16, bfloat16 or uint8; 1 ... 8 stacked frames;
+//                                    --dump-last-frame also writes NAME.obs.npy, shape (views, STACK * C, H, W), descr
+//                                    <f4, <f2, |u1 or, for bfloat16, <u2 holding the bit patterns)
+//                     [--obs-depth-range LO,HI]   (depth channels normalised to 0 <= LO < HI; needs --observations with d)
 //
 // --outputs (no counterpart upstream, where the render config's RenderMode is pinned to RGBD)
 // renders only depth or only rgb (Config::renderOutputs); --dump-last-frame then writes the
@@ -95,7 +100,25 @@ struct Args {
     uint32_t positions = 0;
     // --boxes K: box labels, 1 ... 1024; --dump-last-frame then also writes NAME.boxes.txt
     uint32_t boxes = 0;
+    // --observations CHANNELS[,DTYPE[,STACK]]: the packed observation output (layout 0: none); --dump-last-frame then
+    // also writes NAME.obs.npy.  --obs-depth-range LO,HI: the range its depth channels are normalised to
+    uint32_t obsLayout = 0, obsDtype = 0, obsStack = 1;
+    bool hasObsRange = false;
+    float obsLo = 0.0f, obsHi = 0.0f;
 };
+
+// the comma-separated fields of an option's value
+std::vector<std::string> splitCommas(const char *s)
+{
+    std::vector<std::string> fields(1);
+    for (const char *ch = s; *ch; ++ch) {
+        if (*ch == ',')
+            fields.emplace_back();
+        else
+            fields.back() += *ch;
+    }
+    return fields;
+}
 
 // a number of the whole argument, finite
 float parseFloat(const char *flag, const char *s)
@@ -113,7 +136,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]] [--boxes K]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]] [--boxes K] [--observations CHANNELS[,DTYPE[,STACK]]] [--obs-depth-range LO,HI]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -223,6 +246,42 @@ Args parse(int argc, char **argv)
                 std::exit(EXIT_FAILURE);
             }
             a.boxes = (uint32_t)v;
+        } else if (!std::strcmp(argv[i], "--observations") && i + 1 < argc) {
+            static const char *const layouts[] = { "", "rgb", "rgbd", "d", "y", "yd" };
+            static const char *const dtypes[] = { "float32", "float16", "bfloat16", "uint8" };
+            const char *v = argv[++i];
+            const std::vector<std::string> f = splitCommas(v);
+            uint32_t layout = 0, dtype = f.size() > 1 ? 4u : 0u, stack = 1;
+            for (uint32_t k = 1; k <= 5; ++k)
+                if (f[0] == layouts[k])
+                    layout = k;
+            for (uint32_t k = 0; f.size() > 1 && k < 4; ++k)
+                if (f[1] == dtypes[k])
+                    dtype = k;
+            if (f.size() > 2) {
+                const char *t = f[2].c_str();
+                stack = t[0] >= '1' && t[0] <= '8' && !t[1] ? (uint32_t)(t[0] - '0') : 0u;
+            }
+            if (!layout || dtype == 4 || !stack || f.size() > 3) {
+                std::fprintf(stderr, "--observations: wants CHANNELS[,DTYPE[,STACK]] -- rgb|rgbd|d|y|yd, "
+                                     "float32|float16|bfloat16|uint8, 1 ... 8 -- got: %s\n", v);
+                std::exit(EXIT_FAILURE);
+            }
+            a.obsLayout = layout; a.obsDtype = dtype; a.obsStack = stack;
+        } else if (!std::strcmp(argv[i], "--obs-depth-range") && i + 1 < argc) {
+            const char *v = argv[++i];
+            const std::vector<std::string> f = splitCommas(v);
+            if (f.size() != 2) {
+                std::fprintf(stderr, "--obs-depth-range: wants LO,HI, got: %s\n", v);
+                std::exit(EXIT_FAILURE);
+            }
+            a.obsLo = parseFloat("--obs-depth-range", f[0].c_str());
+            a.obsHi = parseFloat("--obs-depth-range", f[1].c_str());
+            if (!(a.obsLo >= 0.0f && a.obsLo < a.obsHi)) {
+                std::fprintf(stderr, "--obs-depth-range: wants 0 <= LO < HI, got: %s\n", v);
+                std::exit(EXIT_FAILURE);
+            }
+            a.hasObsRange = true;
         } else if (!std::strcmp(argv[i], "--positions")) {
             // the frame is optional: the next argument is taken for it unless it is another option
             a.positions = 1;
@@ -273,6 +332,22 @@ Args parse(int argc, char **argv)
     if (a.boxes && a.mode == Mode::Rasterizer && !a.hasLabels) {
         std::fprintf(stderr, "--boxes: boxes are computed from the segmask, which rast has only with --instance-labels\n");
         std::exit(EXIT_FAILURE);
+    }
+    {
+        const bool colour = a.obsLayout && a.obsLayout != MRX_OBS_D;
+        const bool depth = a.obsLayout == MRX_OBS_RGBD || a.obsLayout == MRX_OBS_D || a.obsLayout == MRX_OBS_YD;
+        if (colour && a.outputs == Manager::RenderOutputs::Depth) {
+            std::fprintf(stderr, "--observations: these channels need rgb, which is not rendered with --outputs depth\n");
+            std::exit(EXIT_FAILURE);
+        }
+        if (depth && a.outputs == Manager::RenderOutputs::RGB) {
+            std::fprintf(stderr, "--observations: these channels need depth, which is not rendered with --outputs rgb\n");
+            std::exit(EXIT_FAILURE);
+        }
+        if (a.hasObsRange && !depth) {
+            std::fprintf(stderr, "--obs-depth-range: needs --observations with a depth channel (rgbd, d or yd)\n");
+            std::exit(EXIT_FAILURE);
+        }
     }
     return a;
 }
@@ -518,6 +593,44 @@ bool dumpBoxes(const std::string &name, mrx_renderer *shard, uint32_t numImages,
     return ok;
 }
 
+// NAME.obs.npy of --observations: the observation tensor of the shard as a NumPy file (format 1.0), shape
+// (views, S * C, H, W); bfloat16 has no NumPy type and goes out as <u2, the bit patterns
+bool dumpObsNpy(const std::string &name, mrx_renderer *shard)
+{
+    int64_t dims[4] = { 0, 0, 0, 0 };
+    int nd = 0, dt = 0, dev = 0;
+    if (!mrx_buffer(shard, MRX_BUF_OBSERVATION, dims, &nd, &dt, &dev) || nd != 4) {
+        std::fprintf(stderr, "%s\n", mrx_last_error());
+        return false;
+    }
+    const char *descr = dt == MRX_DTYPE_F32 ? "<f4" : dt == MRX_DTYPE_F16 ? "<f2" : dt == MRX_DTYPE_BF16 ? "<u2" : "|u1";
+    const size_t elem = dt == MRX_DTYPE_F32 ? 4 : dt == MRX_DTYPE_U8 ? 1 : 2;
+    std::vector<uint8_t> data((size_t)(dims[0] * dims[1] * dims[2] * dims[3]) * elem);
+    if (mrx_copy_to_host(shard, MRX_BUF_OBSERVATION, data.data(), data.size()) != MRX_OK) {
+        std::fprintf(stderr, "%s\n", mrx_last_error());
+        return false;
+    }
+    char dict[160];
+    std::snprintf(dict, sizeof dict, "{'descr': '%s', 'fortran_order': False, 'shape': (%lld, %lld, %lld, %lld), }", descr,
+                  (long long)dims[0], (long long)dims[1], (long long)dims[2], (long long)dims[3]);
+    std::string header = dict;
+    while ((10 + header.size() + 1) % 64 != 0)      // magic, version and length are 10 bytes; the data starts 64-aligned
+        header += ' ';
+    header += '\n';
+    std::string out("\x93NUMPY\x01\x00", 8);
+    out += (char)(header.size() & 0xFF);
+    out += (char)(header.size() >> 8);
+    out += header;
+    FILE *f = std::fopen((name + ".obs.npy").c_str(), "wb");
+    const bool ok = f && std::fwrite(out.data(), 1, out.size(), f) == out.size() &&
+                    std::fwrite(data.data(), 1, data.size(), f) == data.size();
+    if (f && std::fclose(f) != 0)
+        return false;
+    if (!ok)
+        std::fprintf(stderr, "cannot write %s.obs.npy\n", name.c_str());
+    return ok;
+}
+
 }  // namespace
 
 int main(int argc, char **argv)
@@ -615,8 +728,12 @@ int main(int argc, char **argv)
     cfg.supersample = args.supersample;
     cfg.positions = args.positions;
     cfg.boxLabels = args.boxes;
+    if (args.obsLayout)
+        cfg.observations = MRX_FLAG_OBSERVATIONS(args.obsLayout, args.obsDtype, args.obsStack);
 
     Manager mgr(cfg);              // aborts (FATAL) on failure, like the reference
+    if (args.hasObsRange)
+        mgr.setObservationDepthRange(args.obsLo, args.obsHi);
     mgr.sync();
 
     const auto start = std::chrono::system_clock::now();
@@ -656,6 +773,8 @@ int main(int argc, char **argv)
                              args.outputs != Manager::RenderOutputs::Depth) && ok;
             if (args.boxes)
                 ok = dumpBoxes(name, sh, hi - lo, args.boxes) && ok;
+            if (args.obsLayout)
+                ok = dumpObsNpy(name, sh) && ok;
         }
     }
     if (!ok)

@@ -49,7 +49,9 @@ struct Manager::Impl {
             detail::fatal(mrx_last_error());
         TensorElementType t = dtype == MRX_DTYPE_U8 ? TensorElementType::UInt8
                             : dtype == MRX_DTYPE_I32 ? TensorElementType::Int32
-                                                     : TensorElementType::Float32;
+                            : dtype == MRX_DTYPE_F16 ? TensorElementType::Float16
+                            : dtype == MRX_DTYPE_BF16 ? TensorElementType::BFloat16
+                                                      : TensorElementType::Float32;
         return Tensor(p, t, dims, ndim, dev);
     }
 };
@@ -120,6 +122,9 @@ Manager::Manager(const Config &cfg)
     if (cfg.boxLabels > 1024)
         detail::fatal("boxLabels " + std::to_string(cfg.boxLabels) + " is not in 0 ... 1024");
     c.flags |= MRX_FLAG_BOX_LABELS(cfg.boxLabels);
+    if (cfg.observations & ~MRX_FLAG_OBS_MASK)
+        detail::fatal("observations " + std::to_string(cfg.observations) + " has bits outside MRX_FLAG_OBS_MASK");
+    c.flags |= cfg.observations;
     if (cfg.renderOutputs == RenderOutputs::Depth)
         c.flags |= MRX_FLAG_NO_RGB;
     else if (cfg.renderOutputs == RenderOutputs::RGB)
@@ -248,6 +253,30 @@ Tensor Manager::boxTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_BOX
 void Manager::boxes()
 {
     if (mrx_boxes(impl_->r) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+uint32_t Manager::observations() const { return (uint32_t)mrx_observations(impl_->r); }
+
+Tensor Manager::observationTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_OBSERVATION, shard); }
+
+Tensor Manager::observationResetTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_OBSERVATION_RESET, shard); }
+
+void Manager::observe()
+{
+    if (mrx_observe(impl_->r) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+void Manager::setObservationDepthRange(float lo, float hi)
+{
+    if (mrx_set_observation_depth_range(impl_->r, lo, hi) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+void Manager::observationDepthRange(float *lo, float *hi) const
+{
+    if (mrx_observation_depth_range(impl_->r, lo, hi) != MRX_OK)
         detail::fatal(mrx_last_error());
 }
 

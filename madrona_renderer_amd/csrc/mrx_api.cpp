@@ -29,6 +29,7 @@
 #include "resolve.hpp"
 #include "unproject.hpp"
 #include "boxes.hpp"
+#include "observe.hpp"
 
 namespace {
 
@@ -386,6 +387,13 @@ struct mrx_renderer {
     // pointer, no further launch.  boxParts: MRX_BOX_PARTS, the forced number of workgroups per view (0: automatic).
     uint32_t boxLabels = 0, boxParts = 0;
     DevBuf<int32_t> boxes;
+    // packed observation output: the field of the flags (mrx_observations), its parts, the
+    // [views][S * C][H][W] tensor the observation stage writes from the rgb and depth tensors the caller sees and, with
+    // S > 1, the reset column -- allocations of their own, outside allocOutputs and the placement search.  obsLayout 0:
+    // no pointer, no further launch.  obsLo / obsHi: the depth range, both 0 without one; obsInv = 1.0f / (hi - lo).
+    uint32_t obsLayout = 0, obsDtype = 0, obsStack = 1;
+    float obsLo = 0.0f, obsHi = 0.0f, obsInv = 0.0f;
+    DevBuf<uint8_t> obs, obsReset;
     DevBuf<unsigned long long> stamps;
     // XCD phase feedback (raster.hip): a host-mapped word workgroup 0 reports its XCC id to
     uint32_t *xccHost = nullptr, *xccDev = nullptr;
@@ -447,7 +455,37 @@ struct mrx_renderer {
             e = launchResolve();
         if (e == hipSuccess && positions)
             e = launchUnproject();
-        return e == hipSuccess && boxLabels ? launchBoxes() : e;
+        if (e == hipSuccess && boxLabels)
+            e = launchBoxes();
+        return e == hipSuccess && obsLayout ? launchObserve() : e;
+    }
+
+    // (rgb and depth are read from the render's parameters at every launch: the placement search re-binds them)
+    hipError_t launchObserve()
+    {
+        mrx::ObserveParams q {};
+        q.rgb = ss > 1 ? outRgb.ptr : params.rgb;
+        q.depth = ss > 1 ? outDepth.ptr : params.depth;
+        q.obs = obs.ptr;
+        q.reset = obsReset.ptr;
+        q.numViews = params.numViews;
+        q.nfast = info.storage_fast;
+        q.nslow = info.storage_slow;
+        q.layout = obsLayout;
+        q.dtype = obsDtype;
+        q.stack = obsStack;
+        q.hasRange = obsHi > 0.0f ? 1 : 0;
+        q.lo = obsLo;
+        q.inv = obsInv;
+        q.transposed = params.transposed;
+        q.numCUs = params.numCUs;
+        return mrx::launchObserve(q, stream);
+    }
+
+    // every view's stack restarts at the next run of the stage
+    hipError_t markObservationsReset()
+    {
+        return obsReset.ptr ? hipMemsetAsync(obsReset.ptr, 1, params.numViews, stream) : hipSuccess;
     }
 
     // (the ids pointer is read from the render's parameters at every launch: the placement search re-binds it)
@@ -560,6 +598,7 @@ struct mrx_renderer {
         outRgb.release(); outDepth.release(); outIds.release(); outNormal.release();
         position.release();
         boxes.release();
+        obs.release(); obsReset.release();
         if (xccHost) (void)hipHostFree(xccHost);
         bvhNodes.release(); bvhLeafTris.release(); worldInstStart.release();
         viewWorld.release(); instKBase.release(); objInfo.release();
@@ -582,7 +621,7 @@ struct mrx_renderer {
 // handshake.  Workers spin on their word for a while after a command (a simulation loop calls
 // step() every few tens of microseconds) and then sleep in a futex; MRX_SHARD_SPIN_US sets how
 // long (default 200), MRX_SHARD_THREADS=0 restores the serial form (startShardWorkers).
-enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdUnproject, kCmdBoxes, kCmdExit };
+enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdUnproject, kCmdBoxes, kCmdObserve, kCmdObserveRestart, kCmdExit };
 
 struct ShardWorker {
     std::vector<mrx_renderer *> shards;         // the shards of ONE device, launched in order
@@ -669,6 +708,16 @@ int groupRun(const std::vector<mrx_renderer *> &shards, int cmd, int steps, bool
     case kCmdBoxes:
         for (mrx_renderer *sh : shards)
             MRX_HIP(sh->launchBoxes());
+        return MRX_OK;
+    case kCmdObserve:
+        for (mrx_renderer *sh : shards)
+            MRX_HIP(sh->launchObserve());
+        return MRX_OK;
+    case kCmdObserveRestart:
+        for (mrx_renderer *sh : shards) {
+            MRX_HIP(sh->markObservationsReset());
+            MRX_HIP(sh->launchObserve());
+        }
         return MRX_OK;
     case kCmdSync:
         for (mrx_renderer *sh : shards)
@@ -2446,6 +2495,37 @@ static int allocBoxes(mrx_renderer &r)
     return MRX_OK;
 }
 
+static uint32_t obsLayoutOf(uint32_t flags) { return (flags & MRX_FLAG_OBS_LAYOUT_MASK) >> MRX_FLAG_OBS_SHIFT; }
+static uint32_t obsDtypeOf(uint32_t flags) { return (flags & MRX_FLAG_OBS_DTYPE_MASK) >> MRX_FLAG_OBS_DTYPE_SHIFT; }
+static uint32_t obsStackOf(uint32_t flags) { return 1u + ((flags & MRX_FLAG_OBS_STACK_MASK) >> MRX_FLAG_OBS_STACK_SHIFT); }
+
+static_assert(MRX_OBS_RGB == mrx::kObsRgb && MRX_OBS_RGBD == mrx::kObsRgbd && MRX_OBS_D == mrx::kObsD &&
+                  MRX_OBS_Y == mrx::kObsY && MRX_OBS_YD == mrx::kObsYd && MRX_OBS_F32 == mrx::kObsF32 &&
+                  MRX_OBS_F16 == mrx::kObsF16 && MRX_OBS_BF16 == mrx::kObsBf16 && MRX_OBS_U8 == mrx::kObsU8,
+              "observe.hpp and mrx.h MRX_OBS_* disagree");
+
+// the tensors of a renderer with the packed observation output: the [views][S * C][H][W] tensor, zeroed, and with
+// S > 1 the reset column, which starts at 1 -- the first frame fills every stack; the stage's bytes on top of the
+// rest, per native pixel: the inputs the layout reads (4 for rgb, 4 for depth), the current frame written (C * e) and
+// S - 1 frames read and written (2 * (S - 1) * C * e)
+static int allocObservations(mrx_renderer &r)
+{
+    const uint64_t px = (uint64_t)r.params.numViews * r.info.storage_fast * r.info.storage_slow;
+    if (px > mrx::kObserveMaxPixels)
+        return fail(MRX_E_INVALID, "observations: more than 2^32 - 1 native pixels");
+    const uint64_t C = mrx::observeChannels(r.obsLayout), e = mrx::observeElemBytes(r.obsDtype), S = r.obsStack;
+    const uint64_t bytes = px * S * C * e;
+    MRX_HIP(r.obs.alloc((size_t)std::max<uint64_t>(bytes, 1)));
+    MRX_HIP(hipMemsetAsync(r.obs.ptr, 0, (size_t)bytes, r.stream));      // (ahead of the first frame, on its stream)
+    if (S > 1) {
+        MRX_HIP(r.obsReset.alloc((size_t)std::max<uint32_t>(r.params.numViews, 1)));
+        MRX_HIP(hipMemsetAsync(r.obsReset.ptr, 1, r.params.numViews, r.stream));
+    }
+    r.info.bytes_per_step += px * ((mrx::observeReadsColour(r.obsLayout) ? 4ull : 0ull) +
+                                   (mrx::observeReadsDepth(r.obsLayout) ? 4ull : 0ull) + (2ull * S - 1ull) * C * e);
+    return MRX_OK;
+}
+
 // one renderer on one device (mrx_create proper, or one shard of a multi-device renderer)
 static int createOne(const mrx_config &cfg, mrx_renderer **out)
 {
@@ -2479,6 +2559,11 @@ static int createOne(const mrx_config &cfg, mrx_renderer **out)
     r->boxLabels = boxLabelsOf(cfg.flags);
     if (rc == MRX_OK && r->boxLabels)
         rc = allocBoxes(*r);
+    r->obsLayout = obsLayoutOf(cfg.flags);
+    r->obsDtype = obsDtypeOf(cfg.flags);
+    r->obsStack = obsStackOf(cfg.flags);
+    if (rc == MRX_OK && r->obsLayout)
+        rc = allocObservations(*r);
     if (rc == MRX_OK) {
         hipError_t e = hipEventCreate(&r->ev0);
         if (e == hipSuccess) e = hipEventCreate(&r->ev1);
@@ -2575,6 +2660,26 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
         if (views * cfg->view_width * side > mrx::kBoxMaxPixels)
             return fail(MRX_E_INVALID, "MRX_FLAG_BOX_LABELS: more than 2^32 - 1 native pixels");
     }
+    if (const uint32_t layout = obsLayoutOf(cfg->flags)) {
+        if (mrx::observeChannels(layout) == 0)
+            return fail(MRX_E_INVALID, "MRX_FLAG_OBSERVATIONS: layout " + std::to_string(layout) + " is not one of "
+                                       "MRX_OBS_RGB ... MRX_OBS_YD (1 ... 5)");
+        if (mrx::observeReadsColour(layout) && (cfg->flags & MRX_FLAG_NO_RGB))
+            return fail(MRX_E_INVALID, "MRX_FLAG_OBSERVATIONS with a colour layout and MRX_FLAG_NO_RGB together: the "
+                                       "observation stage reads the rgb tensor, which a depth-only renderer does not have");
+        if (mrx::observeReadsDepth(layout) && (cfg->flags & MRX_FLAG_NO_DEPTH))
+            return fail(MRX_E_INVALID, "MRX_FLAG_OBSERVATIONS with a depth layout and MRX_FLAG_NO_DEPTH together: the "
+                                       "observation stage reads the depth tensor, which an rgb-only renderer does not have");
+        // (as the unprojection stage limits it: mrx_info's storage is the native size)
+        const uint64_t side = cfg->render_mode == MRX_MODE_RAYTRACER ? cfg->view_width : cfg->view_height;
+        uint64_t views = 0;
+        for (uint32_t w = 0; w < cfg->num_worlds; ++w)
+            views += cfg->worlds[w].num_cameras;
+        if (views * cfg->view_width * side > mrx::kObserveMaxPixels)
+            return fail(MRX_E_INVALID, "MRX_FLAG_OBSERVATIONS: more than 2^32 - 1 native pixels");
+    } else if (cfg->flags & MRX_FLAG_OBS_MASK) {
+        return fail(MRX_E_INVALID, "MRX_FLAG_OBSERVATIONS: element type or stack bits without a layout");
+    }
     if (cfg->max_instances_per_world > (1u << 20))
         return fail(MRX_E_INVALID, "max_instances_per_world out of range");
     if (cfg->camera_projections)
@@ -2616,6 +2721,9 @@ int mrx_create(const mrx_config *cfgIn, mrx_renderer **out)
     top->ss = supersampleOf(cfg->flags);
     top->positions = positionsOf(cfg->flags);
     top->boxLabels = boxLabelsOf(cfg->flags);
+    top->obsLayout = obsLayoutOf(cfg->flags);
+    top->obsDtype = obsDtypeOf(cfg->flags);
+    top->obsStack = obsStackOf(cfg->flags);
     top->device = cfg->device_ids[0];
     const uint32_t n = cfg->num_devices;
     for (uint32_t i = 0; i < n; ++i) {
@@ -2868,7 +2976,7 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
     }
     if (sample && which != MRX_BUF_RGB && which != MRX_BUF_DEPTH && which != MRX_BUF_SEGMASK &&
         which != MRX_BUF_VISIBILITY && which != MRX_BUF_NORMAL) {
-        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT5 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
+        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT6 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
              "not a rendered output: only rgb, depth, normals and the ids tensor have samples");
         return nullptr;
     }
@@ -2916,6 +3024,27 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
         *ndim = 3; *dtype = MRX_DTYPE_I32; ptr = r->boxes.ptr;
         if (!ptr) {
             fail(MRX_E_UNSUPPORTED, "boxes not computed: this renderer was created without MRX_FLAG_BOX_LABELS");
+            return nullptr;
+        }
+        break;
+    case MRX_BUF_OBSERVATION: {   // the packed observation: channel first, image order in both modes
+        const int64_t H = rt ? r->info.storage_fast : r->info.storage_slow, W = rt ? r->info.storage_slow : r->info.storage_fast;
+        dims[0] = V; dims[1] = (int64_t)r->obsStack * mrx::observeChannels(r->obsLayout); dims[2] = H; dims[3] = W;
+        *ndim = 4;
+        *dtype = r->obsDtype == MRX_OBS_F32 ? MRX_DTYPE_F32 : r->obsDtype == MRX_OBS_F16 ? MRX_DTYPE_F16
+               : r->obsDtype == MRX_OBS_BF16 ? MRX_DTYPE_BF16 : MRX_DTYPE_U8;
+        ptr = r->obs.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED, "observations not packed: this renderer was created without MRX_FLAG_OBSERVATIONS");
+            return nullptr;
+        }
+        break;
+    }
+    case MRX_BUF_OBSERVATION_RESET:   // the reset column: a non-zero byte restarts the view's stack at the next run
+        dims[0] = V; *ndim = 1; *dtype = MRX_DTYPE_U8; ptr = r->obsReset.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED, r->obsLayout ? "no reset column: this renderer's MRX_FLAG_OBSERVATIONS field has a stack of 1"
+                                                 : "no reset column: this renderer was created without MRX_FLAG_OBSERVATIONS");
             return nullptr;
         }
         break;
@@ -3100,6 +3229,79 @@ int mrx_box_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t k, uin
     return (int)mrx::boxParts(views, nslow, num_cus, forced_parts);
 }
 
+int mrx_observations(mrx_renderer *r)
+{
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    return r->obsLayout ? (int)MRX_FLAG_OBSERVATIONS(r->obsLayout, r->obsDtype, r->obsStack) : 0;
+}
+
+int mrx_observe(mrx_renderer *r)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (!r->obsLayout)
+        return fail(MRX_E_UNSUPPORTED, "nothing to observe: this renderer was created without MRX_FLAG_OBSERVATIONS");
+    if (!r->shards.empty())
+        return shardsRun(r, kCmdObserve);
+    MRX_HIP(hipSetDevice(r->device));
+    MRX_HIP(r->launchObserve());
+    return MRX_OK;
+}
+
+int mrx_set_observation_depth_range(mrx_renderer *r, float lo, float hi)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (!r->obsLayout)
+        return fail(MRX_E_UNSUPPORTED, "no observation depth range: this renderer was created without MRX_FLAG_OBSERVATIONS");
+    const bool unset = lo == 0.0f && hi == 0.0f;
+    if (!unset && !(std::isfinite(lo) && std::isfinite(hi) && lo >= 0.0f && lo < hi))
+        return fail(MRX_E_INVALID, "observation depth range: 0 <= lo < hi, both finite (0, 0: no range)");
+    if (!unset && !mrx::observeReadsDepth(r->obsLayout))
+        return fail(MRX_E_INVALID, "observation depth range: this renderer's layout has no depth channel");
+    // S15: a float32 subtract and a float32 divide
+    const float span = hi - lo;
+    const float inv = unset ? 0.0f : 1.0f / span;
+    const auto store = [&](mrx_renderer &sh) {
+        sh.obsLo = unset ? 0.0f : lo;
+        sh.obsHi = unset ? 0.0f : hi;
+        sh.obsInv = inv;
+    };
+    store(*r);
+    // frames packed under another range are meaningless: every stack restarts from the frame packed now
+    if (!r->shards.empty()) {
+        for (mrx_renderer *sh : r->shards)
+            store(*sh);
+        return shardsRun(r, kCmdObserveRestart);
+    }
+    MRX_HIP(hipSetDevice(r->device));
+    MRX_HIP(r->markObservationsReset());
+    MRX_HIP(r->launchObserve());
+    return MRX_OK;
+}
+
+int mrx_observation_depth_range(mrx_renderer *r, float *lo, float *hi)
+{
+    if (!r || !lo || !hi)
+        return fail(MRX_E_INVALID, "null argument");
+    if (!r->obsLayout)
+        return fail(MRX_E_UNSUPPORTED, "no observation depth range: this renderer was created without MRX_FLAG_OBSERVATIONS");
+    *lo = r->obsLo;
+    *hi = r->obsHi;
+    return MRX_OK;
+}
+
 int mrx_copy_to_host(mrx_renderer *r, int which, void *dst, uint64_t bytes)
 {
     {
@@ -3116,7 +3318,7 @@ int mrx_copy_to_host(mrx_renderer *r, int which, void *dst, uint64_t bytes)
     void *src = mrx_buffer(r, which, dims, &nd, &dt, &dev);
     if (!src)
         return MRX_E_UNSUPPORTED;
-    uint64_t total = dt == MRX_DTYPE_U8 ? 1 : 4;
+    uint64_t total = dt == MRX_DTYPE_U8 ? 1 : dt == MRX_DTYPE_F16 || dt == MRX_DTYPE_BF16 ? 2 : 4;
     for (int i = 0; i < nd; ++i)
         total *= (uint64_t)dims[i];
     if (bytes > total)

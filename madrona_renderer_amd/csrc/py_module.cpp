@@ -10,6 +10,7 @@
 #include <array>
 #include <cmath>
 #include <cstdio>
+#include <memory>
 #include <string>
 #include <vector>
 
@@ -62,7 +63,7 @@ using madrona::py::TensorElementType;
 
 // ---- minimal DLPack (v0.8 ABI) ------------------------------------------
 enum { kDLCPU = 1, kDLROCM = 10 };
-enum { kDLInt = 0, kDLUInt = 1, kDLFloat = 2 };
+enum { kDLInt = 0, kDLUInt = 1, kDLFloat = 2, kDLBfloat = 4 };
 struct DLDevice { int32_t device_type; int32_t device_id; };
 struct DLDataType { uint8_t code; uint8_t bits; uint16_t lanes; };
 struct DLTensor {
@@ -123,6 +124,8 @@ py::object makeCapsule(const PyTensor &self)
     switch (t.type()) {
     case TensorElementType::UInt8: d.dtype = DLDataType { kDLUInt, 8, 1 }; break;
     case TensorElementType::Int32: d.dtype = DLDataType { kDLInt, 32, 1 }; break;
+    case TensorElementType::Float16: d.dtype = DLDataType { kDLFloat, 16, 1 }; break;
+    case TensorElementType::BFloat16: d.dtype = DLDataType { kDLBfloat, 16, 1 }; break;
     default: d.dtype = DLDataType { kDLFloat, 32, 1 }; break;
     }
     for (int i = 0; i < d.ndim; ++i)
@@ -164,6 +167,104 @@ uint32_t shardOf(const py::object &self, const py::object &shard)
     return (uint32_t)i;
 }
 
+// observations= of the constructor: None / False (no output), a string -- the channels, float32, no stack -- or a dict
+// with the keys channels (required), dtype, stack and depth_range
+struct ObsArg {
+    uint32_t field = 0;             // MRX_FLAG_OBSERVATIONS(...), 0: no output
+    bool hasRange = false;
+    float lo = 0.0f, hi = 0.0f;
+};
+
+const char *const kObsChannels[] = { nullptr, "rgb", "rgbd", "d", "y", "yd" };
+const char *const kObsDtypes[] = { "float32", "float16", "bfloat16", "uint8" };
+
+// (lo, hi) with 0 <= lo < hi, both finite, as float32
+void parseObsRange(const py::object &range, float &lo, float &hi)
+{
+    const char *msg = "observations: depth_range must be None or (lo, hi) with 0 <= lo < hi, both finite";
+    if (!py::isinstance<py::tuple>(range) && !py::isinstance<py::list>(range))
+        throw py::value_error(msg);
+    const py::sequence seq = range.cast<py::sequence>();
+    if (seq.size() != 2)
+        throw py::value_error(msg);
+    double v[2];
+    for (int i = 0; i < 2; ++i) {
+        const py::object o = seq[i];
+        if (py::isinstance<py::bool_>(o) || (!py::isinstance<py::float_>(o) && !py::isinstance<py::int_>(o)))
+            throw py::value_error(msg);
+        v[i] = o.cast<double>();
+    }
+    lo = (float)v[0];
+    hi = (float)v[1];
+    if (!(std::isfinite(lo) && std::isfinite(hi) && lo >= 0.0f && lo < hi))
+        throw py::value_error(msg);
+}
+
+ObsArg parseObservations(const py::object &arg, Manager::RenderOutputs outputs)
+{
+    ObsArg out;
+    if (arg.is_none() || (py::isinstance<py::bool_>(arg) && !arg.cast<bool>()))
+        return out;
+    std::string channels, dtype = "float32";
+    long long stack = 1;
+    py::object range = py::none();
+    if (py::isinstance<py::str>(arg)) {
+        channels = arg.cast<std::string>();
+    } else if (py::isinstance<py::dict>(arg)) {
+        bool haveChannels = false;
+        for (const auto &kv : arg.cast<py::dict>()) {
+            if (!py::isinstance<py::str>(kv.first))
+                throw py::value_error("observations: the keys are channels, dtype, stack and depth_range");
+            const std::string key = kv.first.cast<std::string>();
+            const py::object val = py::reinterpret_borrow<py::object>(kv.second);
+            if (key == "channels" || key == "dtype") {
+                if (!py::isinstance<py::str>(val))
+                    throw py::value_error("observations: " + key + " must be a string");
+                (key == "channels" ? channels : dtype) = val.cast<std::string>();
+                haveChannels = haveChannels || key == "channels";
+            } else if (key == "stack") {
+                if (py::isinstance<py::bool_>(val) || !py::isinstance<py::int_>(val))
+                    throw py::value_error("observations: stack must be an int in 1 ... 8");
+                stack = val.cast<long long>();
+            } else if (key == "depth_range") {
+                range = val;
+            } else {
+                throw py::value_error("observations: unknown key " + key + " (channels, dtype, stack, depth_range)");
+            }
+        }
+        if (!haveChannels)
+            throw py::value_error("observations: the dict needs channels (rgb, rgbd, d, y, yd)");
+    } else {
+        throw py::value_error("observations must be None, a channels string or a dict (channels, dtype, stack, depth_range)");
+    }
+    uint32_t layout = 0, dt = 4;
+    for (uint32_t i = 1; i <= 5; ++i)
+        if (channels == kObsChannels[i])
+            layout = i;
+    for (uint32_t i = 0; i < 4; ++i)
+        if (dtype == kObsDtypes[i])
+            dt = i;
+    if (!layout)
+        throw py::value_error("observations: unknown channels " + channels + " (rgb, rgbd, d, y, yd)");
+    if (dt == 4)
+        throw py::value_error("observations: unknown dtype " + dtype + " (float32, float16, bfloat16, uint8)");
+    if (stack < 1 || stack > 8)
+        throw py::value_error("observations: stack must be an int in 1 ... 8");
+    const bool colour = layout != MRX_OBS_D, depth = layout == MRX_OBS_RGBD || layout == MRX_OBS_D || layout == MRX_OBS_YD;
+    if (colour && outputs == Manager::RenderOutputs::Depth)
+        throw py::value_error("observations: channels " + channels + " need rgb: render_outputs Depth renders none");
+    if (depth && outputs == Manager::RenderOutputs::RGB)
+        throw py::value_error("observations: channels " + channels + " need depth: render_outputs RGB renders none");
+    if (!range.is_none()) {
+        parseObsRange(range, out.lo, out.hi);
+        if (!depth)
+            throw py::value_error("observations: depth_range with channels " + channels + ", which have no depth");
+        out.hasRange = true;
+    }
+    out.field = MRX_FLAG_OBSERVATIONS(layout, dt, (uint32_t)stack);
+    return out;
+}
+
 }  // namespace
 
 PYBIND11_MODULE(madrona_renderer, m)
@@ -200,6 +301,20 @@ PYBIND11_MODULE(madrona_renderer, m)
     m.attr("MRX_FLAG_BOX_LABELS_MASK") = (uint32_t)MRX_FLAG_BOX_LABELS_MASK;
     m.attr("MRX_BUF_BOXES") = (int)MRX_BUF_BOXES;
     m.attr("MRX_NUM_BUFFERS_EXT5") = (int)MRX_NUM_BUFFERS_EXT5;
+    // ... and of the packed observation output
+    m.attr("MRX_FLAG_OBS_SHIFT") = (uint32_t)MRX_FLAG_OBS_SHIFT;
+    m.attr("MRX_FLAG_OBS_MASK") = (uint32_t)MRX_FLAG_OBS_MASK;
+    m.attr("MRX_FLAG_OBS_LAYOUT_MASK") = (uint32_t)MRX_FLAG_OBS_LAYOUT_MASK;
+    m.attr("MRX_FLAG_OBS_DTYPE_MASK") = (uint32_t)MRX_FLAG_OBS_DTYPE_MASK;
+    m.attr("MRX_FLAG_OBS_STACK_MASK") = (uint32_t)MRX_FLAG_OBS_STACK_MASK;
+    m.def("MRX_FLAG_OBSERVATIONS", [](uint32_t layout, uint32_t dtype, uint32_t stack) {
+        return (uint32_t)MRX_FLAG_OBSERVATIONS(layout, dtype, stack);
+    });
+    m.attr("MRX_BUF_OBSERVATION") = (int)MRX_BUF_OBSERVATION;
+    m.attr("MRX_BUF_OBSERVATION_RESET") = (int)MRX_BUF_OBSERVATION_RESET;
+    m.attr("MRX_NUM_BUFFERS_EXT6") = (int)MRX_NUM_BUFFERS_EXT6;
+    m.attr("MRX_DTYPE_F16") = (int)MRX_DTYPE_F16;
+    m.attr("MRX_DTYPE_BF16") = (int)MRX_DTYPE_BF16;
     m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
     m.attr("MRX_CONFIG_SIZE") = (uint32_t)sizeof(mrx_config);
 
@@ -320,7 +435,8 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<int> &device_ids, int max_instances_per_world,
                          Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors,
                          py::object instance_materials, bool normals, py::object instance_labels, int supersample,
-                         py::object positions, py::object boxes) {
+                         py::object positions, py::object boxes, py::object observations) {
+                 const ObsArg obsArg = parseObservations(observations, render_outputs);
                  // boxes: None / 0 / False (no output) or K, an int in 1 ... 1024
                  uint32_t boxLabels = 0;
                  if (py::isinstance<py::bool_>(boxes)) {
@@ -475,7 +591,12 @@ PYBIND11_MODULE(madrona_renderer, m)
                  cfg.supersample = (uint32_t)supersample;
                  cfg.positions = positionFrame;
                  cfg.boxLabels = boxLabels;
-                 return new Manager(cfg);
+                 cfg.observations = obsArg.field;
+                 std::unique_ptr<Manager> mgr(new Manager(cfg));
+                 // (mrx_config cannot carry the range: the first frame is packed raw and restarted under it here)
+                 if (obsArg.hasRange)
+                     mgr->setObservationDepthRange(obsArg.lo, obsArg.hi);
+                 return mgr.release();
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
              py::arg("batch_render_view_width"), py::arg("batch_render_view_height"),
@@ -505,7 +626,10 @@ PYBIND11_MODULE(madrona_renderer, m)
              // positions = True / "world" / "view": the point every pixel sees (position_tensor, unproject)
              py::arg("positions") = false,
              // boxes = K: the bounding box and pixel count of labels 0 ... K-1 in every view (box_tensor, boxes)
-             py::arg("boxes") = py::none())
+             py::arg("boxes") = py::none(),
+             // observations = "rgbd" or dict(channels=, dtype=, stack=, depth_range=): the packed channel-first tensor a
+             // policy takes (observation_tensor, observation_reset_tensor, observe, set_observation_depth_range)
+             py::arg("observations") = py::none())
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -553,6 +677,42 @@ PYBIND11_MODULE(madrona_renderer, m)
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().boxTensor(shardOf(self, shard))); },
              py::arg("shard") = py::none())
         .def("boxes", &Manager::boxes)
+        // packed observation output: the option as a dict or None; [views, S * C, H, W] in the dtype asked for, frame 0
+        // the oldest (RuntimeError without observations=); the reset column u8 [views] (RuntimeError with stack 1); the
+        // observation stage alone -- on a stacked renderer one more frame; the depth range, whose setter restarts
+        // every stack
+        .def_property_readonly("observations",
+                               [](const Manager &self) -> py::object {
+                                   const uint32_t f = self.observations();
+                                   if (!f)
+                                       return py::none();
+                                   float lo = 0.0f, hi = 0.0f;
+                                   self.observationDepthRange(&lo, &hi);
+                                   py::dict d;
+                                   d["channels"] = kObsChannels[(f & MRX_FLAG_OBS_LAYOUT_MASK) >> MRX_FLAG_OBS_SHIFT];
+                                   d["dtype"] = kObsDtypes[(f & MRX_FLAG_OBS_DTYPE_MASK) >> MRX_FLAG_OBS_DTYPE_SHIFT];
+                                   d["stack"] = 1u + ((f & MRX_FLAG_OBS_STACK_MASK) >> MRX_FLAG_OBS_STACK_SHIFT);
+                                   d["depth_range"] = hi > 0.0f ? py::object(py::make_tuple(lo, hi)) : py::object(py::none());
+                                   return d;
+                               })
+        .def("observation_tensor",
+             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().observationTensor(shardOf(self, shard))); },
+             py::arg("shard") = py::none())
+        .def("observation_reset_tensor",
+             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().observationResetTensor(shardOf(self, shard))); },
+             py::arg("shard") = py::none())
+        .def("observe", &Manager::observe)
+        .def("set_observation_depth_range",
+             [](Manager &self, py::object lo, py::object hi) {
+                 if (lo.is_none() && hi.is_none()) {
+                     self.setObservationDepthRange(0.0f, 0.0f);
+                     return;
+                 }
+                 float l = 0.0f, h = 0.0f;
+                 parseObsRange(py::make_tuple(lo, hi), l, h);
+                 self.setObservationDepthRange(l, h);
+             },
+             py::arg("lo"), py::arg("hi") = py::none())
         .def("segmask_tensor",
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().segmaskTensor(shardOf(self, shard))); },
              py::arg("shard") = py::none())

@@ -73,6 +73,9 @@ class SceneDesc:
     # box labels (box_tensor()): None / 0 / False = none, K = the 2-D bounding box and the pixel count of every label
     # 0 ... K-1 in every view; needs a segmask (Raytracer mode, or instance_labels)
     boxes: object = None
+    # the packed observation output (observation_tensor()): None = none, a channels string ("rgb", "rgbd", "d", "y",
+    # "yd": float32, no stack) or a dict(channels=, dtype=, stack=, depth_range=): the channel-first tensor a policy takes
+    observations: object = None
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -314,6 +317,8 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
         extra["positions"] = desc.positions
     if desc.boxes is not None and desc.boxes is not False:
         extra["boxes"] = desc.boxes
+    if desc.observations is not None and desc.observations is not False:
+        extra["observations"] = desc.observations
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:

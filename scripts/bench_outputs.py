@@ -4,6 +4,7 @@ that matter, one JSON line per (configuration, setting):
 
   python scripts/bench_outputs.py [--rounds 5] [--budget-ms 30] [--only headline,c2,...] [--normals] [--labels]
                                   [--root TREE] [--supersample N[,N...]] [--positions]
+                                  [--observations CHANNELS[,DTYPE[,STACK]]]
 
 --normals times RGBD+N, Depth+N and RGB+N (the surface-normal output beside each selection) beside the
 three settings, in the same alternation; without it the script does what it always did.
@@ -22,6 +23,12 @@ is what the sample tensors' placement search timed (candidates, kept).
 (default: headline and c2): POS = time_renders of the renderer with positions=True (render + unproject), PLAIN =
 time_renders of the renderer without, in the same alternation, and UNPROJECT = the stage alone (mark, a batch of
 unproject(), mark) with its bytes -- bytes_per_step of POS minus that of PLAIN, 20 per pixel -- as a fraction of 8 TB/s.
+
+--observations CHANNELS[,DTYPE[,STACK]] measures the observation stage instead, on the configurations
+chosen (default: headline and c2), depth channels normalised to (0.1, 20): OBS = time_renders of the renderer with the
+option (render + observe), PLAIN = time_renders of the renderer without, in the same alternation, and OBSERVE = the
+stage alone (mark, a batch of observe(), mark) with its bytes -- bytes_per_step of OBS minus that of PLAIN -- as a
+fraction of 8 TB/s.
 
 Every renderer of a configuration is created and warmed first; then the settings alternate within
 the process, `rounds` times, each measurement a batch of back-to-back renders between two events
@@ -178,6 +185,54 @@ def positions_main(a, scenes):
         del pos, plain
 
 
+def observations_main(a, scenes):
+    import dataclasses
+    only = set(filter(None, a.only.split(","))) or {"headline", "c2"}
+    f = a.observations.split(",")
+    opt = dict(channels=f[0], dtype=f[1] if len(f) > 1 else "float32", stack=int(f[2]) if len(f) > 2 else 1)
+    if opt["channels"] in ("rgbd", "d", "yd"):
+        opt["depth_range"] = (0.1, 20.0)
+    for key, label, factory, variant in configs(scenes):
+        if key not in only:
+            continue
+        base = factory()
+        obs = scenes.make_renderer(dataclasses.replace(base, observations=opt))
+        plain = scenes.make_renderer(base)
+
+        def observe_us(steps, r=obs):
+            r.mark(0)
+            for _ in range(steps):
+                r.observe()
+            r.mark(1)
+            return r.elapsed_ms() * 1000.0 / steps
+
+        fns = {"OBS": lambda steps, r=obs: us_per_render(r, steps), "PLAIN": lambda steps, r=plain: us_per_render(r, steps),
+               "OBSERVE": observe_us}
+        steps = {}
+        for s, fn in fns.items():
+            t0 = time.perf_counter()
+            while time.perf_counter() - t0 < 0.2:
+                est = fn(20)
+            steps[s] = max(10, min(5000, int(a.budget_ms * 1000.0 / max(est, 1.0))))
+        times = {s: [] for s in fns}
+        for _ in range(a.rounds):
+            for s, fn in fns.items():
+                times[s].append(fn(steps[s]))
+        nbytes = {"OBS": int(obs.bytes_per_step()), "PLAIN": int(plain.bytes_per_step())}
+        nbytes["OBSERVE"] = nbytes["OBS"] - nbytes["PLAIN"]
+        for s in fns:
+            med = statistics.median(times[s])
+            print(json.dumps({
+                "config": key, "workload": label, "observations": opt, "setting": s, "views": base.num_views,
+                "native": [base.width, base.height], "steps": steps[s], "rounds": a.rounds,
+                "us_median": round(med, 3), "us_min": round(min(times[s]), 3), "us_max": round(max(times[s]), 3),
+                "us_all": [round(t, 3) for t in times[s]],
+                "ratio_to_plain": round(med / statistics.median(times["PLAIN"]), 4),
+                "bytes": nbytes[s], "frac_8tbps": round(nbytes[s] / (med * 1e-6) / 1e9 / HBM_PEAK_GBPS, 4),
+            }), flush=True)
+        del obs, plain
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--rounds", type=int, default=5)
@@ -188,6 +243,7 @@ def main(argv=None):
     ap.add_argument("--root", default="", help="import madrona_renderer_amd from this checkout instead")
     ap.add_argument("--supersample", default="", help="factors (2,3,4): measure the resolve stage instead (DESIGN.md 4.18)")
     ap.add_argument("--positions", action="store_true", help="measure the unprojection stage instead (DESIGN.md 4.19)")
+    ap.add_argument("--observations", default="", help="CHANNELS[,DTYPE[,STACK]]: measure the observation stage instead (DESIGN.md 4.21)")
     a = ap.parse_args(argv)
     if a.rounds < 3:
         ap.error("--rounds must be at least 3")
@@ -198,6 +254,8 @@ def main(argv=None):
         return supersample_main(a, scenes)
     if a.positions:
         return positions_main(a, scenes)
+    if a.observations:
+        return observations_main(a, scenes)
     only = set(filter(None, a.only.split(",")))
     settings = SETTINGS + (NORMAL_SETTINGS if a.normals else ())
     if a.labels:
