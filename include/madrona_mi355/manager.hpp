@@ -221,6 +221,14 @@ public:
     // the kernel the last render launched (mrx_raster_entry): "group-fast", "group", "chunked", "brute",
     // "bvh", or "none" before the first render
     const char *rasterEntry() const;
+    // the instantiation of that kernel (mrx_kernel_form): the form's name -- "Uniform", "PV", "PVL", "C", "PVLC", "M",
+    // "PVLM", "N", "NPV", "L", "LN", "PVM"  -- and the group kernel's triangle slots per view (0 for
+    // every other kernel)
+    struct KernelFormInfo {
+        const char *form;
+        int32_t slots;
+    };
+    KernelFormInfo kernelForm() const;
     // per-view projection (views of the whole job): set views [first, first + count) -- stream-ordered, the next
     // step renders with them; false (and nothing changed) when a value is out of range -- and read them back
     bool setViewProjection(uint32_t first, uint32_t count, const CameraProjection *proj);

@@ -508,6 +508,20 @@ enum {
     MRX_ENTRY_BRUTE = 4, MRX_ENTRY_BVH = 5
 };
 int mrx_raster_entry(mrx_renderer *r);
+/* -- which instantiation of that kernel: the form the launcher picked from the renderer's per-view tables, columns and
+ *    extra outputs (MRX_FORM_UNIFORM: the uniform kernels, and before the first render) and, for the
+ *    group kernel, the triangle slots per view it launched with (16 ... 256; 0 for every other kernel).  Read-only,
+ *    host side: no kernel sees either value.  A renderer that spans several devices reports its first shard's;
+ *    MRX_E_INVALID for a null renderer or output. */
+enum {
+    MRX_FORM_UNIFORM = 0, MRX_FORM_PV = 1, MRX_FORM_PVL = 2, MRX_FORM_C = 3, MRX_FORM_PVLC = 4, MRX_FORM_M = 5,
+    MRX_FORM_PVLM = 6, MRX_FORM_N = 7, MRX_FORM_NPV = 8, MRX_FORM_L = 9, MRX_FORM_LN = 10, MRX_FORM_PVM = 11
+};
+typedef struct {
+    int32_t form;              /* MRX_FORM_* */
+    int32_t slots;             /* group kernel: triangle slots per view; else 0 */
+} mrx_kernel_form_t;
+int mrx_kernel_form(mrx_renderer *r, mrx_kernel_form_t *out);
 /* -- the BVH path's launch shape as the host chose it for the bound geometry (mrx_create, mrx_refresh_objects):
  *    what the next BVH render launches.  kernel is MRX_BVH_KERNEL_NONE when the raster kernels render; the other
  *    fields are filled in all the same.  The flat kernel has no record table or large-triangle list (their caps

@@ -2114,7 +2114,7 @@ BvhLaunchShape bvhLaunchShape(const RasterParams &p)
     return s;
 }
 
-hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
+hipError_t launchBvh(const RasterParams &p, hipStream_t stream, LaunchForm *took)
 {
     if (p.numViews == 0)
         return hipSuccess;
@@ -2136,6 +2136,7 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
         // output selection: one instantiation per setting (kOutRGBD = the kernel as it always was); the forms
         //  have one instantiation each that selects by pointer
         const KernelForm form = bvhForm(p, false);
+        if (took) *took = LaunchForm { (int32_t)form, 0 };
         const OutSel out = outSelOf(p.rgb, p.depth);
         return withValue<int, 2, 1, 0>(ids, [&](auto IDS) {
             return withBool(tex, [&](auto TEX) {
@@ -2190,6 +2191,7 @@ hipError_t launchBvh(const RasterParams &p, hipStream_t stream)
     // Instantiation choice: the form (bvhForm), then ids x textured x tile shape.  The per-view normals form of a
     // textured scene has no CLS instantiation (tileFormClassifies; `cls` is false for it: classifiesPerStrip).
     const KernelForm form = bvhForm(p, true);
+    if (took) *took = LaunchForm { (int32_t)form, 0 };
     return withValue<int, 2, 1, 0>(ids, [&](auto IDS) {
         return withBool(tex, [&](auto TEX) {
             const auto launch = [&](auto TW, auto TH, auto CLS, auto MULTI) {

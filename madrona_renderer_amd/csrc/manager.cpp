@@ -446,6 +446,17 @@ const char *Manager::rasterEntry() const
     return names[e];
 }
 
+Manager::KernelFormInfo Manager::kernelForm() const
+{
+    static const char *const names[] = {"Uniform", "PV", "PVL", "C", "PVLC", "M", "PVLM", "N", "NPV", "L", "LN", "PVM"};
+    mrx_kernel_form_t f {};
+    if (mrx_kernel_form(impl_->r, &f) != MRX_OK)
+        detail::fatal(mrx_last_error());
+    if (f.form < 0 || f.form >= (int)(sizeof names / sizeof names[0]))
+        detail::fatal("mrx_kernel_form: unknown form");
+    return KernelFormInfo { names[f.form], f.slots };
+}
+
 void Manager::setStream(void *hipStream)
 {
     if (mrx_set_stream(impl_->r, hipStream) != MRX_OK)

@@ -405,6 +405,7 @@ struct mrx_renderer {
     DevBuf<mrx::ObjInfo> objInfo;
     bool useBvh = false;
     int32_t lastEntry = mrx::kEntryNone;        // the kernel the last launch() ran (mrx_raster_entry)
+    mrx::LaunchForm lastForm;                   // ... and its instantiation: form and group slots (mrx_kernel_form)
     // host copies the geometry binding is (re)built from (bindGeometry): the object each
     // instance row is bound to, the world -> row and view -> world tables, the BLAS set
     std::vector<int32_t> boundObj;
@@ -558,9 +559,9 @@ struct mrx_renderer {
         params.xccReport = (xccDev && (launches <= 4 || (launches & 31u) == 0)) ? xccDev : nullptr;
         if (useBvh) {
             lastEntry = mrx::kEntryBvh;
-            return mrx::launchBvh(params, stream);
+            return mrx::launchBvh(params, stream, &lastForm);
         }
-        return mrx::launchRaster(params, info.max_world_triangles, variant, stream, &lastEntry);
+        return mrx::launchRaster(params, info.max_world_triangles, variant, stream, &lastEntry, &lastForm);
     }
 
     ~mrx_renderer()
@@ -2831,6 +2832,25 @@ int mrx_raster_entry(mrx_renderer *r)
     if (!r)
         return fail(MRX_E_INVALID, "null renderer");
     return r->shards.empty() ? r->lastEntry : r->shards[0]->lastEntry;
+}
+
+#define MRX_FORM_SAME(name, NAME) ((int)mrx::KernelForm::name == MRX_FORM_##NAME)
+static_assert(MRX_FORM_SAME(Uniform, UNIFORM) && MRX_FORM_SAME(PV, PV) && MRX_FORM_SAME(PVL, PVL) && MRX_FORM_SAME(C, C) &&
+                  MRX_FORM_SAME(PVLC, PVLC) && MRX_FORM_SAME(M, M) && MRX_FORM_SAME(PVLM, PVLM) && MRX_FORM_SAME(N, N) &&
+                  MRX_FORM_SAME(NPV, NPV) && MRX_FORM_SAME(L, L) && MRX_FORM_SAME(LN, LN) && MRX_FORM_SAME(PVM, PVM),
+              "raster.hpp KernelForm and mrx.h MRX_FORM_* disagree");
+#undef MRX_FORM_SAME
+
+int mrx_kernel_form(mrx_renderer *r, mrx_kernel_form_t *out)
+{
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (!out)
+        return fail(MRX_E_INVALID, "null output");
+    const mrx_renderer &sh = r->shards.empty() ? *r : *r->shards[0];
+    out->form = sh.lastForm.form;
+    out->slots = sh.lastForm.slots;
+    return MRX_OK;
 }
 
 int mrx_bvh_launch(mrx_renderer *r, mrx_bvh_launch_t *out)

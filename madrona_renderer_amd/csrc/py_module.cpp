@@ -784,6 +784,15 @@ PYBIND11_MODULE(madrona_renderer, m)
         .def("bytes_per_step", &Manager::bytesPerStep)
         .def("render_path", [](Manager &self) { return std::string(self.renderPath()); })
         .def("raster_entry", [](Manager &self) { return std::string(self.rasterEntry()); })
+        .def("kernel_form",
+             [](Manager &self) {
+                 // mrx_kernel_form: the instantiation the last render launched
+                 const Manager::KernelFormInfo f = self.kernelForm();
+                 py::dict d;
+                 d["form"] = std::string(f.form);
+                 d["slots"] = f.slots;
+                 return d;
+             })
         .def("bvh_launch",
              [](Manager &self) {
                  // mrx_bvh_launch: the BVH path's launch shape for the bound geometry

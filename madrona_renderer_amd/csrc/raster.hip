@@ -1480,7 +1480,7 @@ KernelForm groupForm(const RasterParams &p)
 }  // namespace
 
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
-                        int32_t variant, hipStream_t stream, int32_t *entry)
+                        int32_t variant, hipStream_t stream, int32_t *entry, LaunchForm *took)
 {
     const uint32_t items = p.numViews * p.tilesFast * p.tilesSlow;
     if (items == 0)
@@ -1494,6 +1494,7 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
         if (entry) *entry = kEntryBrute;
         const dim3 grid((items + kWavesPerBlock - 1) / kWavesPerBlock);
         const KernelForm form = tileForm(p);
+        if (took) *took = LaunchForm { (int32_t)form, 0 };
         const OutSel out = outSelOf(p.rgb, p.depth);
         const auto byIdsMulti = [&](auto f) {
             withBool(ids, [&](auto IDS) { withBool(multi, [&](auto MULTI) { f(IDS, MULTI); }); });
@@ -1514,6 +1515,7 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
         // more triangles per world than the group kernel holds: one workgroup per tile
         if (entry) *entry = kEntryChunked;
         const KernelForm form = tileForm(p);
+        if (took) *took = LaunchForm { (int32_t)form, 0 };
         withBool(ids, [&](auto IDS) {
             constexpr bool kIds = decltype(IDS)::value;
             if (form != KernelForm::Uniform)
@@ -1615,6 +1617,7 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
         // Instantiation choice: the form (groupForm), then slots x ids x textured; the uniform kernels by XMODE and OUT
         // too.  FAST and XMODE 1..3 exist with 16 slots only, the label forms with ids only.
         const KernelForm form = groupForm(p);
+        if (took) *took = LaunchForm { (int32_t)form, slots };
         const bool tex = p.anyTextured != 0;
         // output selection: one instantiation per setting (kOutRGBD = the kernels as they always were)
         const OutSel out = outSelOf(p.rgb, p.depth);

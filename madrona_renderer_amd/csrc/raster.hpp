@@ -420,12 +420,19 @@ inline bool bvhDispatchFlat(bool raytracer, uint32_t numViews, uint32_t nfast, u
 enum RasterEntry : int32_t {
     kEntryNone = 0, kEntryGroupFast = 1, kEntryGroup = 2, kEntryChunked = 3, kEntryBrute = 4, kEntryBvh = 5,
 };
+// Which instantiation it ran (mrx_kernel_form; include/mrx.h's MRX_FORM_* are the KernelForm values): the form the
+// launcher picked and, for the group kernel, the triangle slots per view it launched with (0 in every other family).
+// Written next to *entry, host side; no kernel sees either.
+struct LaunchForm {
+    int32_t form = 0;     // KernelForm
+    int32_t slots = 0;
+};
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
-                        int32_t variant, hipStream_t stream, int32_t *entry = nullptr);
+                        int32_t variant, hipStream_t stream, int32_t *entry = nullptr, LaunchForm *took = nullptr);
 
 // BVH path: per-step TLAS in LDS, wave-packet traversal of TLAS + BLAS,
 // exact S6 leaf test (bvh.hip).  p.bvhPassInst is filled in by the caller.
-hipError_t launchBvh(const RasterParams &p, hipStream_t stream);
+hipError_t launchBvh(const RasterParams &p, hipStream_t stream, LaunchForm *took = nullptr);
 constexpr uint32_t kBvhMaxWorldTris = 0x1FFFFEu;   // the depth buffer's key holds 21 bits of triangle index
 // dynamic LDS bytes one workgroup of the BVH kernel needs for `passInst` instance records
 size_t bvhLdsBytes(uint32_t passInst, bool textured, bool classify, uint32_t groupViews, uint32_t texCap);

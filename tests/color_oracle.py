@@ -42,6 +42,12 @@ def apply(fs, row_colors):
     mat_color, mat_tex = [fs.mat_color.reshape(-1, 4)], list(fs.mat_tex)
     inst_obj, inst_obj0 = fs.inst_obj.copy(), fs.inst_obj0.copy()
     ntri, nmat, nobj = len(fs.tri_pos), len(fs.mat_tex), len(fs.obj_first_tri)
+    # A row bound to an object id outside the table draws nothing and has no triangle slots (setup_view).  The clones
+    # are appended behind the table, where such an id would come to name one: the row becomes an unbound row first,
+    # which numbers the triangles of its world as before.
+    outside = (inst_obj0 < 0) | (inst_obj0 >= nobj)
+    inst_obj0[outside] = -1
+    inst_obj[outside] = -1
     clones, back = {}, {}
     for row in np.nonzero(rc[:, 3])[0]:
         obj = int(fs.inst_obj0[row])

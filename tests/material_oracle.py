@@ -46,6 +46,12 @@ def apply(fs, row_mats):
     first, count = list(fs.obj_first_tri), list(fs.obj_num_tris)
     inst_obj, inst_obj0 = fs.inst_obj.copy(), fs.inst_obj0.copy()
     ntri, nmat, nobj = len(fs.tri_pos), len(fs.mat_tex), len(fs.obj_first_tri)
+    # A row bound to an object id outside the table draws nothing and has no triangle slots (setup_view).  The clones
+    # are appended behind the table, where such an id would come to name one: the row becomes an unbound row first,
+    # which numbers the triangles of its world as before.
+    outside = (inst_obj0 < 0) | (inst_obj0 >= nobj)
+    inst_obj0[outside] = -1
+    inst_obj[outside] = -1
     clones, back = {}, {}
     for row in np.nonzero((rm >= 0) & (rm < nmat))[0]:
         obj, m = int(fs.inst_obj0[row]), int(rm[row])
