@@ -127,6 +127,10 @@ public:
         // in float32, float16, bfloat16 or uint8 -- packed from rgb and depth by a stage behind every render.  A
         // layout needs the outputs it reads rendered.
         uint32_t observations = 0;
+        // Ray-cast sensor (mrx_rays_create): R rays per world in 1 ... 65536, 0 none; rayTensor() / rayFrameTensor() then
+        // take the rays and the row they are mounted on, and a trace stage behind every render writes
+        // rayDistanceTensor() and rayIdTensor().
+        uint32_t raysPerWorld = 0;
     };
     // the label that stands for the id of the object a row is bound to (MRX_LABEL_OBJECT)
     static constexpr int32_t kLabelObject = INT32_MIN;
@@ -200,6 +204,16 @@ public:
     void observe();
     void setObservationDepthRange(float lo, float hi);
     void observationDepthRange(float *lo, float *hi) const;
+    // ray-cast sensor: R or 0; f32 [worlds, R, 8] rays (ox, oy, oz, tmin, dx, dy, dz, tmax) and i32 [worlds] mount rows
+    // (-1: world frame), both mutable; f32 [worlds, R] the parameter t of the nearest hit (tmax on a miss) and i32
+    // [worlds, R] the segmask value of the row that was hit (-1 on a miss) (fatal without Config::raysPerWorld); the
+    // trace stage alone
+    uint32_t rays() const;
+    madrona::py::Tensor rayTensor(uint32_t shard = 0) const;
+    madrona::py::Tensor rayFrameTensor(uint32_t shard = 0) const;
+    madrona::py::Tensor rayDistanceTensor(uint32_t shard = 0) const;
+    madrona::py::Tensor rayIdTensor(uint32_t shard = 0) const;
+    void trace();
     // binds every row to the (non-negative) object id its ObjectID column now holds: a spare
     // row gets its geometry, an existing row swaps it (makeEntityRenderable at run time,
     // src/sim.inl:5-8); waits for the device

@@ -366,7 +366,23 @@ enum {
      * the current one.  Written on the device, like a pose, on the renderer's stream; starts at 1, and the renderer
      * clears it behind every run of the stage, so a flag is consumed by exactly the next run. */
     MRX_BUF_OBSERVATION_RESET = 17,
-    MRX_NUM_BUFFERS_EXT6 = 18
+    MRX_NUM_BUFFERS_EXT6 = 18,
+    /* The ray-cast sensor (mrx_rays_create); all four need it, are indexed by world and are per
+     * shard, like the other outputs.
+     * f32 [worlds,R,8], mutable, written like a pose: ray r of world w is (ox, oy, oz, tmin, dx, dy, dz, tmax), two
+     * aligned 16-byte halves.  Zero-filled at creation: the zero ray misses. */
+    MRX_BUF_RAYS = 18,
+    /* i32 [worlds], mutable, written like a pose: the world-local instance row the world's rays are mounted on -- they
+     * are then given in that row's frame, o = R(q) ol + p, d = R(q) dl with the row's live pose; its scale and ObjectID
+     * are not read.  Any value outside 0 ... rows of the world - 1 means the world frame.  Starts at -1. */
+    MRX_BUF_RAY_FRAME = 19,
+    /* f32 [worlds,R]: the parameter t of the nearest hit, hit = o + t d (a distance when d has unit length); the ray's
+     * own tmax, bit for bit, where nothing is hit. */
+    MRX_BUF_RAY_DISTANCE = 20,
+    /* i32 [worlds,R]: the segmask value of the instance row that was hit -- its label, or the id
+     * of the object it is bound to -- and -1 on a miss. */
+    MRX_BUF_RAY_ID = 21,
+    MRX_NUM_BUFFERS_EXT7 = 22
 };
 
 enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2, MRX_DTYPE_F16 = 3, MRX_DTYPE_BF16 = 4 };
@@ -459,6 +475,43 @@ int mrx_observations(mrx_renderer *r);
 int mrx_observe(mrx_renderer *r);
 int mrx_set_observation_depth_range(mrx_renderer *r, float lo, float hi);
 int mrx_observation_depth_range(mrx_renderer *r, float *lo, float *hi);
+
+/* -- ray-cast sensor.  The flag word is full and mrx_config keeps its size, so the sensor is
+ *    attached after creation: mrx_rays_create(r, R) allocates the four MRX_BUF_RAY* tensors for R rays per world, 1 ...
+ *    65536 with worlds * R < 2^31, and from then on mrx_step / mrx_render / mrx_time_renders enqueue the trace stage
+ *    last on the render's stream, behind the render, the resolve, the unprojection, the boxes and the observation.  It
+ *    is called once: a second call, or R out of range, returns MRX_E_INVALID; on a renderer of several shards it fans
+ *    out (a shard cannot be given a sensor on its own).  MRX_RAYS_BRUTE=1 in the environment at that call selects the
+ *    form of the kernel that skips every cull, MRX_RAY_PASS_ROWS=n stages n rows of a world at a time (tests).
+ *    mrx_rays returns R, or 0 without the sensor; MRX_E_INVALID for a null renderer.  mrx_trace enqueues the stage
+ *    alone on the renderer's stream (every shard's on its own), as mrx_boxes does: what a caller that only wrote rays
+ *    or poses calls.  MRX_E_UNSUPPORTED without the sensor.  The stage reads the ray tensors, the live pose, scale,
+ *    ObjectID and label columns and the geometry tables; it writes MRX_BUF_RAY_DISTANCE and MRX_BUF_RAY_ID only.
+ *    mrx_set_rays copies `count` worlds of rays, [count][R][8] host floats, into MRX_BUF_RAYS from world first_world on,
+ *    on the renderer's stream, and waits for the copy: what a host program without the HIP runtime at hand calls
+ *    (a caller with device tensors writes the buffer itself).  One shard at a time, like mrx_copy_to_host.
+ *    mrx_ray_plan is host arithmetic, for tests: the answer of the stage's launch checks for `worlds` worlds of R rays
+ *    over a scene whose deepest BLAS has bvh_depth levels, on num_cus compute units (null_pointers != 0: with null
+ *    tensors; pass_rows: MRX_RAY_PASS_ROWS, 0 = the default) -- MRX_E_INVALID where the launch would be refused,
+ *    otherwise the number of workgroups (0: nothing is enqueued), and out[0 ... 3], when not null, = workgroups per
+ *    world, stack entries per lane, rows per staging pass, dynamic LDS bytes.  It touches no device.
+ *    mrx_trace_rays_host runs the stage's source on the CPU, for tests; it touches no device and sets no error text.
+ *    tri_pos [num_tris][9] are the triangles of num_objects objects (obj_first / obj_count index them); `instances`
+ *    are the rows of all worlds, world-major (world_inst_start [num_worlds + 1]) -- a row draws object object_id, a
+ *    negative id hides it --; labels_or_null [num_instances] is the label column, frame_or_null [num_worlds] the mount
+ *    rows (null: world frame), rays [num_worlds][rays_per_world][8]; brute != 0 skips every cull.  It builds the BLAS
+ *    as mrx_create does and writes out_t / out_id [num_worlds][rays_per_world]. */
+int mrx_rays_create(mrx_renderer *r, uint32_t rays_per_world);
+int mrx_rays(mrx_renderer *r);
+int mrx_trace(mrx_renderer *r);
+int mrx_set_rays(mrx_renderer *r, uint32_t first_world, uint32_t count, const float *rays);
+int mrx_ray_plan(uint32_t worlds, uint32_t rays_per_world, uint32_t bvh_depth, uint32_t num_cus, uint32_t pass_rows,
+                 int null_pointers, uint32_t out[4]);
+int mrx_trace_rays_host(const float *tri_pos, uint32_t num_tris, const int32_t *obj_first, const int32_t *obj_count,
+                        uint32_t num_objects, const mrx_instance *instances, uint32_t num_instances,
+                        const int32_t *labels_or_null, const uint32_t *world_inst_start, uint32_t num_worlds,
+                        const int32_t *frame_or_null, const float *rays, uint32_t rays_per_world, int brute,
+                        float *out_t, int32_t *out_id);
 
 /* -- debug readback: waits for the stream, then copies the first `bytes`
  *    bytes of a buffer to host memory (what /root/reference/src/dump.cpp:53-70

@@ -20,6 +20,9 @@
 //                                    --dump-last-frame also writes NAME.boxes.txt, one line
 //                                    `view label xmin ymin xmax ymax count` per non-empty row; needs a segmask: rt, or
 //                                    rast with --instance-labels)
+//                     [--rays R]   (1 ... 65536: a ray-cast sensor of R rays per world, a horizontal fan of unit rays from
+//                                   the world's first camera position; --dump-last-frame also writes NAME.rays.txt, one
+//                                   line `world ray t id` per ray)
 //                     [--observations CHANNELS[,DTYPE[,STACK]]]   (the packed observation output: rgb, rgbd, d, y or yd;
 //                                    float32 (default), float16, bfloat16 or uint8; 1 ... 8 stacked frames;
 //                                    --dump-last-frame also writes NAME.obs.npy, shape (views, STACK * C, H, W), descr
@@ -100,6 +103,9 @@ struct Args {
     uint32_t positions = 0;
     // --boxes K: box labels, 1 ... 1024; --dump-last-frame then also writes NAME.boxes.txt
     uint32_t boxes = 0;
+    // --rays R: a ray-cast sensor of R rays per world, 1 ... 65536: a horizontal fan of unit rays from the world's first
+    // camera position; --dump-last-frame then also writes NAME.rays.txt
+    uint32_t rays = 0;
     // --observations CHANNELS[,DTYPE[,STACK]]: the packed observation output (layout 0: none); --dump-last-frame then
     // also writes NAME.obs.npy.  --obs-depth-range LO,HI: the range its depth channels are normalised to
     uint32_t obsLayout = 0, obsDtype = 0, obsStack = 1;
@@ -136,7 +142,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]] [--boxes K] [--observations CHANNELS[,DTYPE[,STACK]]] [--obs-depth-range LO,HI]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]] [--boxes K] [--rays R] [--observations CHANNELS[,DTYPE[,STACK]]] [--obs-depth-range LO,HI]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -246,6 +252,16 @@ Args parse(int argc, char **argv)
                 std::exit(EXIT_FAILURE);
             }
             a.boxes = (uint32_t)v;
+        } else if (!std::strcmp(argv[i], "--rays") && i + 1 < argc) {
+            const char *s = argv[++i];
+            char *end = nullptr;
+            errno = 0;
+            const unsigned long long v = std::strtoull(s, &end, 10);
+            if (!*s || *s == '-' || *s == '+' || *end || errno != 0 || v < 1 || v > 65536) {
+                std::fprintf(stderr, "--rays: not a number of rays per world from 1 to 65536: %s\n", s);
+                std::exit(EXIT_FAILURE);
+            }
+            a.rays = (uint32_t)v;
         } else if (!std::strcmp(argv[i], "--observations") && i + 1 < argc) {
             static const char *const layouts[] = { "", "rgb", "rgbd", "d", "y", "yd" };
             static const char *const dtypes[] = { "float32", "float16", "bfloat16", "uint8" };
@@ -593,6 +609,28 @@ bool dumpBoxes(const std::string &name, mrx_renderer *shard, uint32_t numImages,
     return ok;
 }
 
+// NAME.rays.txt of --rays: one line `world ray t id` per ray of the shard's worlds (world numbers are the job's), t with
+// nine significant digits
+bool dumpRays(const std::string &name, mrx_renderer *shard, uint32_t firstWorld, uint32_t numWorlds, uint32_t R)
+{
+    std::vector<float> t((size_t)numWorlds * R);
+    std::vector<int32_t> id((size_t)numWorlds * R);
+    if (mrx_copy_to_host(shard, MRX_BUF_RAY_DISTANCE, t.data(), t.size() * sizeof(float)) != MRX_OK ||
+        mrx_copy_to_host(shard, MRX_BUF_RAY_ID, id.data(), id.size() * sizeof(int32_t)) != MRX_OK) {
+        std::fprintf(stderr, "%s\n", mrx_last_error());
+        return false;
+    }
+    FILE *f = std::fopen((name + ".rays.txt").c_str(), "w");
+    bool ok = f != nullptr;
+    for (size_t i = 0; ok && i < t.size(); ++i)
+        ok = std::fprintf(f, "%zu %zu %.9g %d\n", firstWorld + i / R, i % R, (double)t[i], id[i]) > 0;
+    if (f && std::fclose(f) != 0)
+        ok = false;
+    if (!ok)
+        std::fprintf(stderr, "cannot write %s.rays.txt\n", name.c_str());
+    return ok;
+}
+
 // NAME.obs.npy of --observations: the observation tensor of the shard as a NumPy file (format 1.0), shape
 // (views, S * C, H, W); bfloat16 has no NumPy type and goes out as <u2, the bit patterns
 bool dumpObsNpy(const std::string &name, mrx_renderer *shard)
@@ -728,12 +766,34 @@ int main(int argc, char **argv)
     cfg.supersample = args.supersample;
     cfg.positions = args.positions;
     cfg.boxLabels = args.boxes;
+    cfg.raysPerWorld = args.rays;
     if (args.obsLayout)
         cfg.observations = MRX_FLAG_OBSERVATIONS(args.obsLayout, args.obsDtype, args.obsStack);
 
     Manager mgr(cfg);              // aborts (FATAL) on failure, like the reference
     if (args.hasObsRange)
         mgr.setObservationDepthRange(args.obsLo, args.obsHi);
+    // --rays: ray i of a world leaves its first camera's position at angle 2 pi i / R in the XY plane, t in (0, 1000]
+    if (args.rays) {
+        mrx_renderer *top = (mrx_renderer *)mgr.nativeHandle();
+        for (uint32_t g = 0; g < mgr.numShards(); ++g) {
+            const uint32_t lo = mgr.shardFirstWorld(g), hi = mgr.shardFirstWorld(g + 1);
+            std::vector<float> fan((size_t)(hi - lo) * args.rays * 8u);
+            for (uint32_t w = lo; w < hi; ++w) {
+                const ImportedCamera &cam = s.cameras[s.worlds[w].camerasOffset];
+                for (uint32_t i = 0; i < args.rays; ++i) {
+                    const double a = 2.0 * M_PI * (double)i / (double)args.rays;
+                    float *ray = &fan[((size_t)(w - lo) * args.rays + i) * 8u];
+                    ray[0] = cam.position.x; ray[1] = cam.position.y; ray[2] = cam.position.z; ray[3] = 0.0f;
+                    ray[4] = (float)std::cos(a); ray[5] = (float)std::sin(a); ray[6] = 0.0f; ray[7] = 1000.0f;
+                }
+            }
+            if (mrx_set_rays(mrx_shard(top, (int)g), 0, hi - lo, fan.data()) != MRX_OK) {
+                std::fprintf(stderr, "%s\n", mrx_last_error());
+                return EXIT_FAILURE;
+            }
+        }
+    }
     mgr.sync();
 
     const auto start = std::chrono::system_clock::now();
@@ -773,6 +833,8 @@ int main(int argc, char **argv)
                              args.outputs != Manager::RenderOutputs::Depth) && ok;
             if (args.boxes)
                 ok = dumpBoxes(name, sh, hi - lo, args.boxes) && ok;
+            if (args.rays)
+                ok = dumpRays(name, sh, lo, hi - lo, args.rays) && ok;
             if (args.obsLayout)
                 ok = dumpObsNpy(name, sh) && ok;
         }

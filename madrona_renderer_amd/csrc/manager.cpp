@@ -136,7 +136,12 @@ Manager::Manager(const Config &cfg)
     if (const char *k = std::getenv("MADRONA_MI355_KERNEL"))
         c.kernel_variant = std::atoi(k);
 
+    if (cfg.raysPerWorld > 65536)
+        detail::fatal("raysPerWorld " + std::to_string(cfg.raysPerWorld) + " is not in 0 ... 65536");
     if (mrx_create(&c, &impl_->r) != MRX_OK)
+        detail::fatal(mrx_last_error());
+    // (the flag word is full: the sensor is attached to the renderer once it exists)
+    if (cfg.raysPerWorld && mrx_rays_create(impl_->r, cfg.raysPerWorld) != MRX_OK)
         detail::fatal(mrx_last_error());
     // the initial values of an int32 column, world-major as mrx_create lays the rows out (spare rows `spare`)
     const auto expand = [&](const int32_t *perInstance, int32_t spare) {
@@ -277,6 +282,19 @@ void Manager::setObservationDepthRange(float lo, float hi)
 void Manager::observationDepthRange(float *lo, float *hi) const
 {
     if (mrx_observation_depth_range(impl_->r, lo, hi) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+uint32_t Manager::rays() const { return (uint32_t)mrx_rays(impl_->r); }
+
+Tensor Manager::rayTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_RAYS, shard); }
+Tensor Manager::rayFrameTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_RAY_FRAME, shard); }
+Tensor Manager::rayDistanceTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_RAY_DISTANCE, shard); }
+Tensor Manager::rayIdTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_RAY_ID, shard); }
+
+void Manager::trace()
+{
+    if (mrx_trace(impl_->r) != MRX_OK)
         detail::fatal(mrx_last_error());
 }
 

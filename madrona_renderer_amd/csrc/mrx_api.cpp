@@ -29,6 +29,7 @@
 #include "resolve.hpp"
 #include "unproject.hpp"
 #include "boxes.hpp"
+#include "rays.hpp"
 #include "observe.hpp"
 
 namespace {
@@ -394,6 +395,14 @@ struct mrx_renderer {
     uint32_t obsLayout = 0, obsDtype = 0, obsStack = 1;
     float obsLo = 0.0f, obsHi = 0.0f, obsInv = 0.0f;
     DevBuf<uint8_t> obs, obsReset;
+    // ray-cast sensor (mrx_rays_create): R rays per world, the two input tensors, the two outputs
+    // and the per-row table of bound object ids the stage stores -- allocations of their own, outside allocOutputs and
+    // the placement search.  R == 0: no pointer, no further launch.  rayBrute: MRX_RAYS_BRUTE, the form without culls;
+    // rayPassRows: MRX_RAY_PASS_ROWS, the forced number of rows per staging pass (0: the default).
+    uint32_t raysPerWorld = 0, rayPassRows = 0;
+    bool rayBrute = false;
+    DevBuf<float> rays, rayT;
+    DevBuf<int32_t> rayFrame, rayId, rayBound;
     DevBuf<unsigned long long> stamps;
     // XCD phase feedback (raster.hip): a host-mapped word workgroup 0 reports its XCC id to
     uint32_t *xccHost = nullptr, *xccDev = nullptr;
@@ -458,7 +467,39 @@ struct mrx_renderer {
             e = launchUnproject();
         if (e == hipSuccess && boxLabels)
             e = launchBoxes();
-        return e == hipSuccess && obsLayout ? launchObserve() : e;
+        if (e == hipSuccess && obsLayout)
+            e = launchObserve();
+        return e == hipSuccess && raysPerWorld ? launchRays() : e;
+    }
+
+    // (every table pointer is read from the render's parameters at every launch: bindGeometry re-binds them; pose, scale,
+    // ObjectID, label, ray and frame CONTENTS are read by the kernel)
+    hipError_t launchRays()
+    {
+        mrx::RayParams q {};
+        q.s.tris = params.tris;
+        q.s.nodes = params.bvhNodes;
+        q.s.leafTris = params.bvhLeafTris;
+        q.s.instInfo = params.instInfo;
+        q.s.instKBase = params.instKBase;
+        q.s.boundObj = rayBound.ptr;
+        q.s.worldInstStart = params.worldInstStart;
+        q.s.instPos = params.instPos;
+        q.s.instRot = params.instRot;
+        q.s.instScale = params.instScale;
+        q.s.instObj = params.instObj;
+        q.s.instLabel = instLabel.ptr;
+        q.rays = rays.ptr;
+        q.frame = rayFrame.ptr;
+        q.outT = rayT.ptr;
+        q.outId = rayId.ptr;
+        q.numWorlds = info.num_worlds;
+        q.R = raysPerWorld;
+        q.bvhDepth = info.bvh_depth;
+        q.numCUs = params.numCUs;
+        q.passRows = rayPassRows;
+        q.brute = rayBrute ? 1 : 0;
+        return mrx::launchRays(q, stream);
     }
 
     // (rgb and depth are read from the render's parameters at every launch: the placement search re-binds them)
@@ -600,6 +641,7 @@ struct mrx_renderer {
         position.release();
         boxes.release();
         obs.release(); obsReset.release();
+        rays.release(); rayT.release(); rayFrame.release(); rayId.release(); rayBound.release();
         if (xccHost) (void)hipHostFree(xccHost);
         bvhNodes.release(); bvhLeafTris.release(); worldInstStart.release();
         viewWorld.release(); instKBase.release(); objInfo.release();
@@ -622,7 +664,7 @@ struct mrx_renderer {
 // handshake.  Workers spin on their word for a while after a command (a simulation loop calls
 // step() every few tens of microseconds) and then sleep in a futex; MRX_SHARD_SPIN_US sets how
 // long (default 200), MRX_SHARD_THREADS=0 restores the serial form (startShardWorkers).
-enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdUnproject, kCmdBoxes, kCmdObserve, kCmdObserveRestart, kCmdExit };
+enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdUnproject, kCmdBoxes, kCmdObserve, kCmdObserveRestart, kCmdTrace, kCmdExit };
 
 struct ShardWorker {
     std::vector<mrx_renderer *> shards;         // the shards of ONE device, launched in order
@@ -713,6 +755,10 @@ int groupRun(const std::vector<mrx_renderer *> &shards, int cmd, int steps, bool
     case kCmdObserve:
         for (mrx_renderer *sh : shards)
             MRX_HIP(sh->launchObserve());
+        return MRX_OK;
+    case kCmdTrace:
+        for (mrx_renderer *sh : shards)
+            MRX_HIP(sh->launchRays());
         return MRX_OK;
     case kCmdObserveRestart:
         for (mrx_renderer *sh : shards) {
@@ -1198,6 +1244,15 @@ int chooseBvhGroups(mrx_renderer &r)
 // per-instance BLAS records of the BVH path, which kernel renders, the uniform-world fast
 // paths.  Runs at creation and again from mrx_refresh_objects; the pose tensors, the
 // outputs and the object pool are untouched.
+// [I] the object each row is bound to, as the trace stage reads it (one spare word: idle lanes read row 0)
+hipError_t uploadRayBound(mrx_renderer &r)
+{
+    std::vector<int32_t> bound(r.boundObj);
+    if (bound.empty())
+        bound.push_back(-1);
+    return r.rayBound.reupload(bound);
+}
+
 int bindGeometry(mrx_renderer &r)
 {
     using namespace mrx;
@@ -1288,6 +1343,9 @@ int bindGeometry(mrx_renderer &r)
         instInfo.emplace_back();                      // idle lanes read row 0
     MRX_HIP(r.objInfo.reupload(instInfo));
     MRX_HIP(r.instKBase.reupload(instKBase));
+    // the ray-cast sensor stores the bound object's id of the row it hits
+    if (r.raysPerWorld)
+        MRX_HIP(uploadRayBound(r));
 
     RasterParams &p = r.params;
     // (the material column, DESIGN.md 4.14: decided here, never by what the column holds)
@@ -2996,7 +3054,7 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
     }
     if (sample && which != MRX_BUF_RGB && which != MRX_BUF_DEPTH && which != MRX_BUF_SEGMASK &&
         which != MRX_BUF_VISIBILITY && which != MRX_BUF_NORMAL) {
-        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT6 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
+        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT7 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
              "not a rendered output: only rgb, depth, normals and the ids tensor have samples");
         return nullptr;
     }
@@ -3067,6 +3125,20 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
                                                  : "no reset column: this renderer was created without MRX_FLAG_OBSERVATIONS");
             return nullptr;
         }
+        break;
+    case MRX_BUF_RAYS:          // the ray-cast sensor: indexed by world
+    case MRX_BUF_RAY_FRAME:
+    case MRX_BUF_RAY_DISTANCE:
+    case MRX_BUF_RAY_ID:
+        if (!r->raysPerWorld) {
+            fail(MRX_E_UNSUPPORTED, "no ray-cast sensor: mrx_rays_create was not called on this renderer");
+            return nullptr;
+        }
+        dims[0] = r->info.num_worlds; dims[1] = r->raysPerWorld; dims[2] = 8;
+        *ndim = which == MRX_BUF_RAYS ? 3 : which == MRX_BUF_RAY_FRAME ? 1 : 2;
+        *dtype = which == MRX_BUF_RAYS || which == MRX_BUF_RAY_DISTANCE ? MRX_DTYPE_F32 : MRX_DTYPE_I32;
+        ptr = which == MRX_BUF_RAYS ? (void *)r->rays.ptr : which == MRX_BUF_RAY_FRAME ? (void *)r->rayFrame.ptr
+            : which == MRX_BUF_RAY_DISTANCE ? (void *)r->rayT.ptr : (void *)r->rayId.ptr;
         break;
     case MRX_BUF_DEPTH:     // mgr.cpp:570-590
         dims[0] = V; dims[1] = S; dims[2] = F; dims[3] = 1;
@@ -3247,6 +3319,183 @@ int mrx_box_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t k, uin
     if ((uint64_t)views * nfast * nslow == 0)
         return 0;
     return (int)mrx::boxParts(views, nslow, num_cus, forced_parts);
+}
+
+static int infoFull(mrx_renderer *r, mrx_info_t *out);
+
+// the sensor of one renderer on one device: the four tensors, the bound-object table, the first trace
+static int raysCreateOne(mrx_renderer *r, uint32_t R)
+{
+    MRX_HIP(hipSetDevice(r->device));
+    const uint64_t worlds = r->info.num_worlds, n = worlds * R;
+    // (a failure leaves the renderer without a sensor: raysPerWorld is set last)
+    auto undo = [&](hipError_t e) {
+        r->rays.release(); r->rayT.release(); r->rayFrame.release(); r->rayId.release(); r->rayBound.release();
+        return fail(MRX_E_HIP, std::string("ray-cast sensor: ") + hipGetErrorString(e));
+    };
+    hipError_t e = r->rays.alloc((size_t)n * 8u);
+    if (e == hipSuccess) e = r->rayT.alloc((size_t)n);
+    if (e == hipSuccess) e = r->rayId.alloc((size_t)n);
+    if (e == hipSuccess) e = r->rayFrame.alloc((size_t)worlds);
+    if (e == hipSuccess) e = uploadRayBound(*r);
+    if (e == hipSuccess) e = mrx::prepareRays();
+    // zero rays, world frame (-1 is all bytes 0xFF), and what the zero ray gives: tmax = 0, id -1
+    if (e == hipSuccess) e = hipMemsetAsync(r->rays.ptr, 0, (size_t)n * 32u, r->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r->rayT.ptr, 0, (size_t)n * 4u, r->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r->rayId.ptr, 0xFF, (size_t)n * 4u, r->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r->rayFrame.ptr, 0xFF, (size_t)worlds * 4u, r->stream);
+    if (e != hipSuccess)
+        return undo(e);
+    const char *brute = std::getenv("MRX_RAYS_BRUTE");
+    r->rayBrute = brute && std::atoi(brute) != 0;
+    if (const char *dbg = std::getenv("MRX_RAY_PASS_ROWS"))     // tests: several staging passes at tiny sizes
+        r->rayPassRows = (uint32_t)std::max(0, std::atoi(dbg));
+    r->raysPerWorld = R;
+    e = r->launchRays();
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess) {
+        r->raysPerWorld = 0;
+        return undo(e);
+    }
+    // per ray 32 bytes read, 8 written (the tables it walks depend on the rays)
+    r->info.bytes_per_step += n * 40ull;
+    return MRX_OK;
+}
+
+// takes the sensor off a shard again (mrx_rays_create failed on a later one)
+static void raysDestroyOne(mrx_renderer *r)
+{
+    (void)hipSetDevice(r->device);
+    (void)hipStreamSynchronize(r->stream);
+    r->info.bytes_per_step -= (uint64_t)r->info.num_worlds * r->raysPerWorld * 40ull;
+    r->raysPerWorld = 0;
+    r->rays.release(); r->rayT.release(); r->rayFrame.release(); r->rayId.release(); r->rayBound.release();
+}
+
+int mrx_rays_create(mrx_renderer *r, uint32_t rays_per_world)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (r->parent)
+        return fail(MRX_E_INVALID, "mrx_rays_create on a shard: attach the sensor to the renderer it belongs to");
+    if (r->raysPerWorld)
+        return fail(MRX_E_INVALID, "this renderer already has a ray-cast sensor");
+    if (rays_per_world < 1 || rays_per_world > mrx::kRayMaxPerWorld)
+        return fail(MRX_E_INVALID, "rays_per_world " + std::to_string(rays_per_world) + " is not in 1 ... 65536");
+    mrx_info_t whole {};
+    if (infoFull(r, &whole) != MRX_OK)
+        return MRX_E_INVALID;
+    if ((uint64_t)whole.num_worlds * rays_per_world >= (1ull << 31))
+        return fail(MRX_E_INVALID, "ray-cast sensor: worlds * rays_per_world reaches 2^31");
+    if (r->shards.empty())
+        return raysCreateOne(r, rays_per_world);
+    // all or nothing: a shard that fails takes the sensor of the shards before it along
+    for (size_t i = 0; i < r->shards.size(); ++i) {
+        const int rc = raysCreateOne(r->shards[i], rays_per_world);
+        if (rc != MRX_OK) {
+            const std::string why = g_err;
+            for (size_t k = 0; k < i; ++k)
+                raysDestroyOne(r->shards[k]);
+            return fail(rc, why);
+        }
+    }
+    r->raysPerWorld = rays_per_world;
+    return MRX_OK;
+}
+
+int mrx_rays(mrx_renderer *r)
+{
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    return (int)r->raysPerWorld;
+}
+
+int mrx_trace(mrx_renderer *r)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (!r->raysPerWorld)
+        return fail(MRX_E_UNSUPPORTED, "nothing to trace: mrx_rays_create was not called on this renderer");
+    if (!r->shards.empty())
+        return shardsRun(r, kCmdTrace);
+    MRX_HIP(hipSetDevice(r->device));
+    MRX_HIP(r->launchRays());
+    return MRX_OK;
+}
+
+int mrx_set_rays(mrx_renderer *r, uint32_t first_world, uint32_t count, const float *rays)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r || !rays)
+        return fail(MRX_E_INVALID, "null argument");
+    if (!r->shards.empty())
+        return wantsShard("mrx_set_rays");
+    if (!r->raysPerWorld)
+        return fail(MRX_E_UNSUPPORTED, "no ray-cast sensor: mrx_rays_create was not called on this renderer");
+    if ((uint64_t)first_world + count > r->info.num_worlds)
+        return fail(MRX_E_INVALID, "mrx_set_rays: worlds past the renderer's last");
+    if (count == 0)
+        return MRX_OK;
+    MRX_HIP(hipSetDevice(r->device));
+    const size_t perWorld = (size_t)r->raysPerWorld * 8u;
+    MRX_HIP(hipMemcpyAsync(r->rays.ptr + first_world * perWorld, rays, count * perWorld * sizeof(float),
+                           hipMemcpyHostToDevice, r->stream));
+    MRX_HIP(hipStreamSynchronize(r->stream));
+    return MRX_OK;
+}
+
+int mrx_ray_plan(uint32_t worlds, uint32_t rays_per_world, uint32_t bvh_depth, uint32_t num_cus, uint32_t pass_rows,
+                 int null_pointers, uint32_t out[4])
+{
+    // (never dereferenced: planRays looks at the pointers' values only)
+    static float f = 0.0f;
+    static int32_t i = 0;
+    static uint32_t u = 0;
+    mrx::RayParams q {};
+    if (!null_pointers) {
+        q.s.tris = reinterpret_cast<const mrx::ObjTri *>(&f);
+        q.s.nodes = reinterpret_cast<const mrx::BvhNode *>(&f);
+        q.s.leafTris = &u;
+        q.s.instInfo = reinterpret_cast<const mrx::ObjInfo *>(&f);
+        q.s.instKBase = &u;
+        q.s.boundObj = &i;
+        q.s.worldInstStart = &u;
+        q.s.instPos = q.s.instRot = q.s.instScale = &f;
+        q.s.instObj = &i;
+        q.rays = &f;
+        q.frame = &i;
+        q.outT = &f;
+        q.outId = &i;
+    }
+    q.numWorlds = worlds;
+    q.R = rays_per_world;
+    q.bvhDepth = bvh_depth;
+    q.numCUs = num_cus;
+    q.passRows = pass_rows;
+    mrx::RayPlan plan;
+    if (mrx::planRays(q, plan) != hipSuccess)
+        return fail(MRX_E_INVALID, "the trace stage refuses these arguments");
+    if (out) {
+        out[0] = plan.blocksPerWorld;
+        out[1] = plan.stackEntries;
+        out[2] = plan.passRows;
+        out[3] = plan.ldsBytes;
+    }
+    return (int)plan.workgroups;
 }
 
 int mrx_observations(mrx_renderer *r)

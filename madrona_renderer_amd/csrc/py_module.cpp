@@ -313,6 +313,12 @@ PYBIND11_MODULE(madrona_renderer, m)
     m.attr("MRX_BUF_OBSERVATION") = (int)MRX_BUF_OBSERVATION;
     m.attr("MRX_BUF_OBSERVATION_RESET") = (int)MRX_BUF_OBSERVATION_RESET;
     m.attr("MRX_NUM_BUFFERS_EXT6") = (int)MRX_NUM_BUFFERS_EXT6;
+    // ... and of the ray-cast sensor
+    m.attr("MRX_BUF_RAYS") = (int)MRX_BUF_RAYS;
+    m.attr("MRX_BUF_RAY_FRAME") = (int)MRX_BUF_RAY_FRAME;
+    m.attr("MRX_BUF_RAY_DISTANCE") = (int)MRX_BUF_RAY_DISTANCE;
+    m.attr("MRX_BUF_RAY_ID") = (int)MRX_BUF_RAY_ID;
+    m.attr("MRX_NUM_BUFFERS_EXT7") = (int)MRX_NUM_BUFFERS_EXT7;
     m.attr("MRX_DTYPE_F16") = (int)MRX_DTYPE_F16;
     m.attr("MRX_DTYPE_BF16") = (int)MRX_DTYPE_BF16;
     m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
@@ -435,8 +441,18 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<int> &device_ids, int max_instances_per_world,
                          Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors,
                          py::object instance_materials, bool normals, py::object instance_labels, int supersample,
-                         py::object positions, py::object boxes, py::object observations) {
+                         py::object positions, py::object boxes, py::object observations, py::object rays) {
                  const ObsArg obsArg = parseObservations(observations, render_outputs);
+                 // rays: None (no sensor) or R, an int in 1 ... 65536
+                 uint32_t raysPerWorld = 0;
+                 if (!rays.is_none()) {
+                     if (py::isinstance<py::bool_>(rays) || !py::isinstance<py::int_>(rays))
+                         throw py::value_error("rays must be None or an int in 1 ... 65536 (the number of rays per world)");
+                     const long long n = rays.cast<long long>();
+                     if (n < 1 || n > 65536)
+                         throw py::value_error("rays must be None or an int in 1 ... 65536 (the number of rays per world)");
+                     raysPerWorld = (uint32_t)n;
+                 }
                  // boxes: None / 0 / False (no output) or K, an int in 1 ... 1024
                  uint32_t boxLabels = 0;
                  if (py::isinstance<py::bool_>(boxes)) {
@@ -592,6 +608,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                  cfg.positions = positionFrame;
                  cfg.boxLabels = boxLabels;
                  cfg.observations = obsArg.field;
+                 cfg.raysPerWorld = raysPerWorld;
                  std::unique_ptr<Manager> mgr(new Manager(cfg));
                  // (mrx_config cannot carry the range: the first frame is packed raw and restarted under it here)
                  if (obsArg.hasRange)
@@ -629,7 +646,10 @@ PYBIND11_MODULE(madrona_renderer, m)
              py::arg("boxes") = py::none(),
              // observations = "rgbd" or dict(channels=, dtype=, stack=, depth_range=): the packed channel-first tensor a
              // policy takes (observation_tensor, observation_reset_tensor, observe, set_observation_depth_range)
-             py::arg("observations") = py::none())
+             py::arg("observations") = py::none(),
+             // rays = R: a ray-cast sensor of R rays per world (ray_tensor, ray_frame_tensor, ray_distance_tensor,
+             // ray_id_tensor, trace)
+             py::arg("rays") = py::none())
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -677,6 +697,23 @@ PYBIND11_MODULE(madrona_renderer, m)
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().boxTensor(shardOf(self, shard))); },
              py::arg("shard") = py::none())
         .def("boxes", &Manager::boxes)
+        // ray-cast sensor: R or 0; f32 [worlds, R, 8] rays and i32 [worlds] mount rows, both written like a pose; f32
+        // [worlds, R] t of the nearest hit and i32 [worlds, R] the id of the row that was hit (RuntimeError without
+        // rays=); the trace stage alone
+        .def_property_readonly("rays", &Manager::rays)
+        .def("ray_tensor",
+             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().rayTensor(shardOf(self, shard))); },
+             py::arg("shard") = py::none())
+        .def("ray_frame_tensor",
+             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().rayFrameTensor(shardOf(self, shard))); },
+             py::arg("shard") = py::none())
+        .def("ray_distance_tensor",
+             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().rayDistanceTensor(shardOf(self, shard))); },
+             py::arg("shard") = py::none())
+        .def("ray_id_tensor",
+             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().rayIdTensor(shardOf(self, shard))); },
+             py::arg("shard") = py::none())
+        .def("trace", &Manager::trace)
         // packed observation output: the option as a dict or None; [views, S * C, H, W] in the dtype asked for, frame 0
         // the oldest (RuntimeError without observations=); the reset column u8 [views] (RuntimeError with stack 1); the
         // observation stage alone -- on a stacked renderer one more frame; the depth range, whose setter restarts

@@ -76,6 +76,9 @@ class SceneDesc:
     # the packed observation output (observation_tensor()): None = none, a channels string ("rgb", "rgbd", "d", "y",
     # "yd": float32, no stack) or a dict(channels=, dtype=, stack=, depth_range=): the channel-first tensor a policy takes
     observations: object = None
+    # the ray-cast sensor (ray_tensor(), ray_frame_tensor(), ray_distance_tensor(), ray_id_tensor(), trace()): None =
+    # none, R = that many caller-written rays per world, traced through the world's instances behind every render
+    rays: object = None
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -319,6 +322,8 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
         extra["boxes"] = desc.boxes
     if desc.observations is not None and desc.observations is not False:
         extra["observations"] = desc.observations
+    if desc.rays is not None:
+        extra["rays"] = desc.rays
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:
