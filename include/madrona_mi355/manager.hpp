@@ -131,6 +131,12 @@ public:
         // take the rays and the row they are mounted on, and a trace stage behind every render writes
         // rayDistanceTensor() and rayIdTensor().
         uint32_t raysPerWorld = 0;
+        // Optical-flow output (mrx_flow_create): flowTensor() then holds, per native pixel, the image-space displacement
+        // since the previous step of the surface point the pixel sees, computed by a stage behind every render from a
+        // device snapshot of last step's poses, cameras and projections.  Sets the visibility-ids flag, as
+        // MADRONA_MI355_VISIBILITY=1 does: the ids tensor then holds visibility ids, so segmaskTensor() and boxLabels are
+        // unavailable.  Needs depth rendered.
+        bool flow = false;
     };
     // the label that stands for the id of the object a row is bound to (MRX_LABEL_OBJECT)
     static constexpr int32_t kLabelObject = INT32_MIN;
@@ -214,6 +220,14 @@ public:
     madrona::py::Tensor rayDistanceTensor(uint32_t shard = 0) const;
     madrona::py::Tensor rayIdTensor(uint32_t shard = 0) const;
     void trace();
+    // optical-flow output: whether there is one; f32 [views, H, W, 4] (Raytracer: [views, res, res, 4] transposed, as
+    // rgb): (dx, dy, dz, 1) -- the point pixel (x, y) sees was at (x - dx, y - dy) at the previous step, dz the change of
+    // depth -- and (0, 0, 0, 0) where there is none (fatal without Config::flow); the flow stage alone, which leaves
+    // the snapshot as it is; the snapshot stage alone, which makes the current state the previous one
+    bool flows() const;
+    madrona::py::Tensor flowTensor(uint32_t shard = 0) const;
+    void flow();
+    void flowSnapshot();
     // binds every row to the (non-negative) object id its ObjectID column now holds: a spare
     // row gets its geometry, an existing row swaps it (makeEntityRenderable at run time,
     // src/sim.inl:5-8); waits for the device

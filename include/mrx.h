@@ -382,7 +382,16 @@ enum {
     /* i32 [worlds,R]: the segmask value of the instance row that was hit -- its label, or the id
      * of the object it is bound to -- and -1 on a miss. */
     MRX_BUF_RAY_ID = 21,
-    MRX_NUM_BUFFERS_EXT7 = 22
+    MRX_NUM_BUFFERS_EXT7 = 22,
+    /* f32 [views,H,W,4] (Raytracer: [views,res,res,4], transposed like rgb), needs mrx_flow_create (DESIGN.md S17,
+     * 4.23): per native pixel (dx, dy, dz, 1) -- the surface point the pixel (x, y) sees was at image position
+     * (x - dx, y - dy) when the snapshot was taken, that is at the previous step; dx runs along image columns and dy
+     * along image rows in both modes; dz is the change of depth -- and (0, 0, 0, 0) on background, where the ids tensor
+     * holds -1 and where the point lay behind the previous camera.  Camera motion, the rigid motion and the scale of
+     * the instance the pixel's visibility id belongs to and a change of projection all count.  An allocation of its
+     * own, one per shard; it has no sample tensor. */
+    MRX_BUF_FLOW = 22,
+    MRX_NUM_BUFFERS_EXT8 = 23
 };
 
 enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2, MRX_DTYPE_F16 = 3, MRX_DTYPE_BF16 = 4 };
@@ -512,6 +521,35 @@ int mrx_trace_rays_host(const float *tri_pos, uint32_t num_tris, const int32_t *
                         const int32_t *labels_or_null, const uint32_t *world_inst_start, uint32_t num_worlds,
                         const int32_t *frame_or_null, const float *rays, uint32_t rays_per_world, int brute,
                         float *out_t, int32_t *out_id);
+
+/* -- optical-flow output.  Attached after creation, as the sensor is: mrx_flow_create(r) allocates
+ *    MRX_BUF_FLOW and a device snapshot of the instance position, rotation and scale columns, the camera position and
+ *    rotation columns and every view's projection constants, takes the snapshot and computes a first, still-scene flow.
+ *    From then on mrx_step / mrx_render / mrx_time_renders enqueue two more kernels last on the render's stream, behind
+ *    the trace stage: the flow, which reads the depth and ids tensors the caller sees, the live columns and constants
+ *    and the snapshot, and then the snapshot of the live state for the next step.  MRX_E_INVALID unless the renderer
+ *    has MRX_FLAG_VISIBILITY_IDS and renders depth, at 2^32 native pixels or more, on a second call and on a shard; on
+ *    a renderer of several shards it fans out, all or nothing.  mrx_flow_enabled returns 1 or 0; MRX_E_INVALID for a null
+ *    renderer.  mrx_flow enqueues the flow kernel alone (every shard's on its own stream): it does not advance the
+ *    snapshot, so calling it twice gives the same tensor.  mrx_flow_snapshot enqueues the snapshot alone: what a caller
+ *    that teleported bodies on an episode reset calls after writing the poses, so that the reset shows no motion.
+ *    Both MRX_E_UNSUPPORTED without the output.  MRX_FLOW_PASS_ROWS=n in the environment at mrx_flow_create stages n
+ *    rows of a world at a time (tests).
+ *    mrx_flow_host runs the stage's source on the CPU, for tests; it touches no device and sets no error text.  depth
+ *    and ids are [views][nslow][nfast] in storage order (transposed != 0: [x][y]), s the supersampling factor; consts
+ *    is sx ox sz oz -- [views][4] with consts_per_view != 0, else one set for all views --, prev_consts always
+ *    [views][4]; inst_kbase [num_instances], world_inst_start [num_worlds + 1], view_world [views]; live and prev are
+ *    each five arrays: instance position [I][3], rotation [I][4], scale [I][3], camera position [views][3], rotation
+ *    [views][4]; pass_rows as MRX_FLOW_PASS_ROWS (0: the default).  It writes out_flow [views][nslow][nfast][4]. */
+int mrx_flow_create(mrx_renderer *r);
+int mrx_flow_enabled(mrx_renderer *r);
+int mrx_flow(mrx_renderer *r);
+int mrx_flow_snapshot(mrx_renderer *r);
+int mrx_flow_host(const float *depth, const int32_t *ids, uint32_t views, uint32_t nfast, uint32_t nslow,
+                  int transposed, uint32_t s, const float *consts, int consts_per_view, const float *prev_consts,
+                  const uint32_t *inst_kbase, const uint32_t *world_inst_start, const uint32_t *view_world,
+                  uint32_t num_worlds, uint32_t num_instances, const float *const live[5], const float *const prev[5],
+                  uint32_t pass_rows, float *out_flow);
 
 /* -- debug readback: waits for the stream, then copies the first `bytes`
  *    bytes of a buffer to host memory (what /root/reference/src/dump.cpp:53-70

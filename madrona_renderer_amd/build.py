@@ -18,8 +18,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "observe.hip", "rays.hip", "rays_host.cpp", "bvh.cpp", "mrx_api.cpp", "assets.cpp", "ktx2.cpp"]
-HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "observe.hpp", "rays.hpp", "rays_core.hpp", "assets.hpp", "bc7_tables.inc",
+HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "observe.hip", "rays.hip", "rays_host.cpp", "flow.hip", "flow_host.cpp", "bvh.cpp", "mrx_api.cpp", "assets.cpp", "ktx2.cpp"]
+HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "observe.hpp", "rays.hpp", "rays_core.hpp", "flow.hpp", "flow_core.hpp", "assets.hpp", "bc7_tables.inc",
                           "../../include/mrx.h"]
 MGR_SOURCES = ["manager.cpp"]
 MGR_DEPS = MGR_SOURCES + ["../../include/madrona_mi355/manager.hpp",
@@ -180,6 +180,28 @@ def build_rays_driver(force=False, verbose=False):
     return out
 
 
+def flow_driver_path():
+    return os.path.join(ROOT, "build", "flow_host_driver")
+
+
+def build_flow_driver(force=False, verbose=False):
+    """AddressSanitizer + UBSan build of the optical-flow output's host entry (flow_host.cpp: flow_core.hpp on the
+    CPU) with its driver, csrc/flow_host_driver.cpp.  Host compiler only; run by tests/test_flow_cpu.py on the
+    CPU, as a stand-alone program -- never on the GPU box."""
+    out = flow_driver_path()
+    srcs = ["flow_host_driver.cpp", "flow_host.cpp"]
+    deps = srcs + ["flow.hpp", "flow_core.hpp", "raster.hpp", "../../include/mrx.h"]
+    if force or _stale(out, deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
+               "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+               "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
+        cmd += [os.path.join(CSRC, s) for s in srcs]
+        cmd += ["-o", out]
+        _run(cmd, verbose)
+    return out
+
+
 def build_all(force=False, verbose=False):
     build_hip(force, verbose)
     build_manager(force, verbose)
@@ -191,6 +213,8 @@ def build_all(force=False, verbose=False):
 if __name__ == "__main__":
     if "--asan" in sys.argv:
         print(build_asan(force="--force" in sys.argv, verbose=True))
+    elif "--flow-driver" in sys.argv:
+        print(build_flow_driver(force="--force" in sys.argv, verbose=True))
     elif "--rays-driver" in sys.argv:
         print(build_rays_driver(force="--force" in sys.argv, verbose=True))
     else:

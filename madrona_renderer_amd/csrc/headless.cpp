@@ -23,6 +23,9 @@
 //                     [--rays R]   (1 ... 65536: a ray-cast sensor of R rays per world, a horizontal fan of unit rays from
 //                                   the world's first camera position; --dump-last-frame also writes NAME.rays.txt, one
 //                                   line `world ray t id` per ray)
+//                     [--flow]   (the optical-flow output: per pixel the image-space motion since the previous step;
+//                                 --dump-last-frame also writes NAME.flow.npy, shape (views, H, W, 4), descr <f4; needs
+//                                 depth, excludes --boxes and --instance-labels: the ids tensor holds visibility ids)
 //                     [--observations CHANNELS[,DTYPE[,STACK]]]   (the packed observation output: rgb, rgbd, d, y or yd;
 //                                    float32 (default), float16, bfloat16 or uint8; 1 ... 8 stacked frames;
 //                                    --dump-last-frame also writes NAME.obs.npy, shape (views, STACK * C, H, W), descr
@@ -106,6 +109,8 @@ struct Args {
     // --rays R: a ray-cast sensor of R rays per world, 1 ... 65536: a horizontal fan of unit rays from the world's first
     // camera position; --dump-last-frame then also writes NAME.rays.txt
     uint32_t rays = 0;
+    // --flow: the optical-flow output; --dump-last-frame then also writes NAME.flow.npy
+    bool flow = false;
     // --observations CHANNELS[,DTYPE[,STACK]]: the packed observation output (layout 0: none); --dump-last-frame then
     // also writes NAME.obs.npy.  --obs-depth-range LO,HI: the range its depth channels are normalised to
     uint32_t obsLayout = 0, obsDtype = 0, obsStack = 1;
@@ -142,7 +147,7 @@ float parseFloat(const char *flag, const char *s)
 {
     std::fprintf(stderr,
                  "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]] [--boxes K] [--rays R] [--observations CHANNELS[,DTYPE[,STACK]]] [--obs-depth-range LO,HI]\n",
+                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]] [--boxes K] [--rays R] [--flow] [--observations CHANNELS[,DTYPE[,STACK]]] [--obs-depth-range LO,HI]\n",
                  argv0);
     std::exit(EXIT_FAILURE);
 }
@@ -262,6 +267,8 @@ Args parse(int argc, char **argv)
                 std::exit(EXIT_FAILURE);
             }
             a.rays = (uint32_t)v;
+        } else if (!std::strcmp(argv[i], "--flow")) {
+            a.flow = true;
         } else if (!std::strcmp(argv[i], "--observations") && i + 1 < argc) {
             static const char *const layouts[] = { "", "rgb", "rgbd", "d", "y", "yd" };
             static const char *const dtypes[] = { "float32", "float16", "bfloat16", "uint8" };
@@ -343,6 +350,14 @@ Args parse(int argc, char **argv)
     }
     if (a.positions && a.outputs == Manager::RenderOutputs::RGB) {
         std::fprintf(stderr, "--positions: positions are computed from depth, which is not rendered with --outputs rgb\n");
+        std::exit(EXIT_FAILURE);
+    }
+    if (a.flow && a.outputs == Manager::RenderOutputs::RGB) {
+        std::fprintf(stderr, "--flow: the flow is computed from depth, which is not rendered with --outputs rgb\n");
+        std::exit(EXIT_FAILURE);
+    }
+    if (a.flow && (a.boxes || a.hasLabels)) {
+        std::fprintf(stderr, "--flow: the ids tensor holds visibility ids, so there is no segmask for --boxes or --instance-labels\n");
         std::exit(EXIT_FAILURE);
     }
     if (a.boxes && a.mode == Mode::Rasterizer && !a.hasLabels) {
@@ -631,20 +646,21 @@ bool dumpRays(const std::string &name, mrx_renderer *shard, uint32_t firstWorld,
     return ok;
 }
 
-// NAME.obs.npy of --observations: the observation tensor of the shard as a NumPy file (format 1.0), shape
-// (views, S * C, H, W); bfloat16 has no NumPy type and goes out as <u2, the bit patterns
-bool dumpObsNpy(const std::string &name, mrx_renderer *shard)
+// A four-dimensional tensor of the shard as a NumPy file (format 1.0), NAME + suffix, in the tensor's own shape and
+// order.  NAME.obs.npy of --observations: the observation tensor, (views, S * C, H, W); bfloat16 has no NumPy type and
+// goes out as <u2, the bit patterns.  NAME.flow.npy of --flow: the flow tensor, (views, H, W, 4) <f4.
+bool dumpNpy(const std::string &name, mrx_renderer *shard, int which = MRX_BUF_OBSERVATION, const char *suffix = ".obs.npy")
 {
     int64_t dims[4] = { 0, 0, 0, 0 };
     int nd = 0, dt = 0, dev = 0;
-    if (!mrx_buffer(shard, MRX_BUF_OBSERVATION, dims, &nd, &dt, &dev) || nd != 4) {
+    if (!mrx_buffer(shard, which, dims, &nd, &dt, &dev) || nd != 4) {
         std::fprintf(stderr, "%s\n", mrx_last_error());
         return false;
     }
     const char *descr = dt == MRX_DTYPE_F32 ? "<f4" : dt == MRX_DTYPE_F16 ? "<f2" : dt == MRX_DTYPE_BF16 ? "<u2" : "|u1";
     const size_t elem = dt == MRX_DTYPE_F32 ? 4 : dt == MRX_DTYPE_U8 ? 1 : 2;
     std::vector<uint8_t> data((size_t)(dims[0] * dims[1] * dims[2] * dims[3]) * elem);
-    if (mrx_copy_to_host(shard, MRX_BUF_OBSERVATION, data.data(), data.size()) != MRX_OK) {
+    if (mrx_copy_to_host(shard, which, data.data(), data.size()) != MRX_OK) {
         std::fprintf(stderr, "%s\n", mrx_last_error());
         return false;
     }
@@ -659,13 +675,13 @@ bool dumpObsNpy(const std::string &name, mrx_renderer *shard)
     out += (char)(header.size() & 0xFF);
     out += (char)(header.size() >> 8);
     out += header;
-    FILE *f = std::fopen((name + ".obs.npy").c_str(), "wb");
+    FILE *f = std::fopen((name + suffix).c_str(), "wb");
     const bool ok = f && std::fwrite(out.data(), 1, out.size(), f) == out.size() &&
                     std::fwrite(data.data(), 1, data.size(), f) == data.size();
     if (f && std::fclose(f) != 0)
         return false;
     if (!ok)
-        std::fprintf(stderr, "cannot write %s.obs.npy\n", name.c_str());
+        std::fprintf(stderr, "cannot write %s%s\n", name.c_str(), suffix);
     return ok;
 }
 
@@ -767,6 +783,7 @@ int main(int argc, char **argv)
     cfg.positions = args.positions;
     cfg.boxLabels = args.boxes;
     cfg.raysPerWorld = args.rays;
+    cfg.flow = args.flow;
     if (args.obsLayout)
         cfg.observations = MRX_FLAG_OBSERVATIONS(args.obsLayout, args.obsDtype, args.obsStack);
 
@@ -836,7 +853,9 @@ int main(int argc, char **argv)
             if (args.rays)
                 ok = dumpRays(name, sh, lo, hi - lo, args.rays) && ok;
             if (args.obsLayout)
-                ok = dumpObsNpy(name, sh) && ok;
+                ok = dumpNpy(name, sh) && ok;
+            if (args.flow)      // NAME.flow.npy: the flow tensor as it is, (views, H, W, 4) float32 in storage order
+                ok = dumpNpy(name, sh, MRX_BUF_FLOW, ".flow.npy") && ok;
         }
     }
     if (!ok)

@@ -133,6 +133,13 @@ Manager::Manager(const Config &cfg)
     if (const char *v = std::getenv("MADRONA_MI355_VISIBILITY"))
         if (std::atoi(v) != 0)
             c.flags |= MRX_FLAG_VISIBILITY_IDS;
+    if (cfg.flow) {
+        if (cfg.renderOutputs == RenderOutputs::RGB)
+            detail::fatal("flow needs depth: renderOutputs RGB renders none");
+        if (cfg.boxLabels)
+            detail::fatal("flow and boxLabels exclude each other: under flow the ids tensor holds visibility ids");
+        c.flags |= MRX_FLAG_VISIBILITY_IDS;
+    }
     if (const char *k = std::getenv("MADRONA_MI355_KERNEL"))
         c.kernel_variant = std::atoi(k);
 
@@ -142,6 +149,8 @@ Manager::Manager(const Config &cfg)
         detail::fatal(mrx_last_error());
     // (the flag word is full: the sensor is attached to the renderer once it exists)
     if (cfg.raysPerWorld && mrx_rays_create(impl_->r, cfg.raysPerWorld) != MRX_OK)
+        detail::fatal(mrx_last_error());
+    if (cfg.flow && mrx_flow_create(impl_->r) != MRX_OK)
         detail::fatal(mrx_last_error());
     // the initial values of an int32 column, world-major as mrx_create lays the rows out (spare rows `spare`)
     const auto expand = [&](const int32_t *perInstance, int32_t spare) {
@@ -295,6 +304,22 @@ Tensor Manager::rayIdTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_R
 void Manager::trace()
 {
     if (mrx_trace(impl_->r) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+bool Manager::flows() const { return mrx_flow_enabled(impl_->r) == 1; }
+
+Tensor Manager::flowTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_FLOW, shard); }
+
+void Manager::flow()
+{
+    if (mrx_flow(impl_->r) != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+void Manager::flowSnapshot()
+{
+    if (mrx_flow_snapshot(impl_->r) != MRX_OK)
         detail::fatal(mrx_last_error());
 }
 

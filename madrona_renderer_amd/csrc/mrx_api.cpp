@@ -30,6 +30,7 @@
 #include "unproject.hpp"
 #include "boxes.hpp"
 #include "rays.hpp"
+#include "flow.hpp"
 #include "observe.hpp"
 
 namespace {
@@ -403,6 +404,12 @@ struct mrx_renderer {
     bool rayBrute = false;
     DevBuf<float> rays, rayT;
     DevBuf<int32_t> rayFrame, rayId, rayBound;
+    // optical-flow output (mrx_flow_create): the [views][H][W][4] tensor the flow stage writes and
+    // the snapshot of last step's pose, scale and camera columns and projection constants it reads -- allocations of
+    // their own, outside allocOutputs and the placement search.  No pointer: no further launch.  flowPassRows:
+    // MRX_FLOW_PASS_ROWS, the forced number of rows per staging pass (0: the default).
+    DevBuf<float> flowOut, flowSnap;
+    uint32_t flowPassRows = 0;
     DevBuf<unsigned long long> stamps;
     // XCD phase feedback (raster.hip): a host-mapped word workgroup 0 reports its XCC id to
     uint32_t *xccHost = nullptr, *xccDev = nullptr;
@@ -469,8 +476,46 @@ struct mrx_renderer {
             e = launchBoxes();
         if (e == hipSuccess && obsLayout)
             e = launchObserve();
-        return e == hipSuccess && raysPerWorld ? launchRays() : e;
+        if (e == hipSuccess && raysPerWorld)
+            e = launchRays();
+        if (e == hipSuccess && flowOut.ptr)
+            e = launchFlow();
+        return e == hipSuccess && flowOut.ptr ? launchFlowSnapshot() : e;
     }
+
+    // (depth, ids, the constants and every table pointer are read from the render's parameters at every launch: the
+    // placement search re-binds the first two, mrx_set_view_projection the constants, bindGeometry the tables; pose,
+    // table and snapshot CONTENTS are read by the kernel)
+    mrx::FlowParams flowParams()
+    {
+        mrx::FlowParams q {};
+        q.depth = ss > 1 ? outDepth.ptr : params.depth;
+        q.ids = ss > 1 ? outIds.ptr : params.ids;
+        q.flow = flowOut.ptr;
+        q.instKBase = params.instKBase;
+        q.worldInstStart = params.worldInstStart;
+        q.viewWorld = params.viewWorld;
+        q.live.instPos = params.instPos;
+        q.live.instRot = params.instRot;
+        q.live.instScale = params.instScale;
+        q.live.camPos = params.camPos;
+        q.live.camRot = params.camRot;
+        q.viewProj = params.viewProj;
+        q.sx = params.sx; q.ox = params.ox; q.sz = params.sz; q.oz = params.oz;
+        q.numViews = params.numViews;
+        q.numInstances = info.num_instances;
+        q.nfast = info.storage_fast;
+        q.nslow = info.storage_slow;
+        q.s = ss;
+        q.half = ss / 2;
+        q.transposed = params.transposed;
+        q.numCUs = params.numCUs;
+        q.passRows = flowPassRows;
+        mrx::flowBindSnapshot(flowSnap.ptr, q);
+        return q;
+    }
+    hipError_t launchFlow() { return mrx::launchFlow(flowParams(), stream); }
+    hipError_t launchFlowSnapshot() { return mrx::launchFlowSnapshot(flowParams(), stream); }
 
     // (every table pointer is read from the render's parameters at every launch: bindGeometry re-binds them; pose, scale,
     // ObjectID, label, ray and frame CONTENTS are read by the kernel)
@@ -642,6 +687,7 @@ struct mrx_renderer {
         boxes.release();
         obs.release(); obsReset.release();
         rays.release(); rayT.release(); rayFrame.release(); rayId.release(); rayBound.release();
+        flowOut.release(); flowSnap.release();
         if (xccHost) (void)hipHostFree(xccHost);
         bvhNodes.release(); bvhLeafTris.release(); worldInstStart.release();
         viewWorld.release(); instKBase.release(); objInfo.release();
@@ -664,7 +710,7 @@ struct mrx_renderer {
 // handshake.  Workers spin on their word for a while after a command (a simulation loop calls
 // step() every few tens of microseconds) and then sleep in a futex; MRX_SHARD_SPIN_US sets how
 // long (default 200), MRX_SHARD_THREADS=0 restores the serial form (startShardWorkers).
-enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdUnproject, kCmdBoxes, kCmdObserve, kCmdObserveRestart, kCmdTrace, kCmdExit };
+enum : int { kCmdNone = 0, kCmdRender, kCmdSync, kCmdTimed, kCmdResolve, kCmdUnproject, kCmdBoxes, kCmdObserve, kCmdObserveRestart, kCmdTrace, kCmdFlow, kCmdFlowSnapshot, kCmdExit };
 
 struct ShardWorker {
     std::vector<mrx_renderer *> shards;         // the shards of ONE device, launched in order
@@ -759,6 +805,14 @@ int groupRun(const std::vector<mrx_renderer *> &shards, int cmd, int steps, bool
     case kCmdTrace:
         for (mrx_renderer *sh : shards)
             MRX_HIP(sh->launchRays());
+        return MRX_OK;
+    case kCmdFlow:
+        for (mrx_renderer *sh : shards)
+            MRX_HIP(sh->launchFlow());
+        return MRX_OK;
+    case kCmdFlowSnapshot:
+        for (mrx_renderer *sh : shards)
+            MRX_HIP(sh->launchFlowSnapshot());
         return MRX_OK;
     case kCmdObserveRestart:
         for (mrx_renderer *sh : shards) {
@@ -3054,7 +3108,7 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
     }
     if (sample && which != MRX_BUF_RGB && which != MRX_BUF_DEPTH && which != MRX_BUF_SEGMASK &&
         which != MRX_BUF_VISIBILITY && which != MRX_BUF_NORMAL) {
-        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT7 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
+        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT8 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
              "not a rendered output: only rgb, depth, normals and the ids tensor have samples");
         return nullptr;
     }
@@ -3139,6 +3193,14 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
         *dtype = which == MRX_BUF_RAYS || which == MRX_BUF_RAY_DISTANCE ? MRX_DTYPE_F32 : MRX_DTYPE_I32;
         ptr = which == MRX_BUF_RAYS ? (void *)r->rays.ptr : which == MRX_BUF_RAY_FRAME ? (void *)r->rayFrame.ptr
             : which == MRX_BUF_RAY_DISTANCE ? (void *)r->rayT.ptr : (void *)r->rayId.ptr;
+        break;
+    case MRX_BUF_FLOW:      // the optical-flow output: native size whatever the factor, no samples
+        dims[0] = V; dims[1] = r->info.storage_slow; dims[2] = r->info.storage_fast; dims[3] = 4;
+        *ndim = 4; *dtype = MRX_DTYPE_F32; ptr = r->flowOut.ptr;
+        if (!ptr) {
+            fail(MRX_E_UNSUPPORTED, "no optical flow: mrx_flow_create was not called on this renderer");
+            return nullptr;
+        }
         break;
     case MRX_BUF_DEPTH:     // mgr.cpp:570-590
         dims[0] = V; dims[1] = S; dims[2] = F; dims[3] = 1;
@@ -3497,6 +3559,116 @@ int mrx_ray_plan(uint32_t worlds, uint32_t rays_per_world, uint32_t bvh_depth, u
     }
     return (int)plan.workgroups;
 }
+
+// the output of one renderer on one device: the tensor, the snapshot of the state as it is, the first flow
+static int flowCreateOne(mrx_renderer *r)
+{
+    MRX_HIP(hipSetDevice(r->device));
+    const uint64_t px = (uint64_t)r->info.num_views * r->info.storage_fast * r->info.storage_slow;
+    const uint64_t snap = mrx::flowSnapshotLayout(r->info.num_instances, r->info.num_views).total;
+    auto undo = [&](hipError_t e) {
+        r->flowOut.release(); r->flowSnap.release();
+        return fail(MRX_E_HIP, std::string("optical flow: ") + hipGetErrorString(e));
+    };
+    // (one spare 16 bytes each: a renderer without a pixel or a row still has two pointers, the sign of the output)
+    hipError_t e = r->flowOut.alloc((size_t)px * 4u + 4u);
+    if (e == hipSuccess) e = r->flowSnap.alloc((size_t)snap + 4u);
+    if (e == hipSuccess) e = hipMemsetAsync(r->flowOut.ptr, 0, ((size_t)px * 4u + 4u) * 4u, r->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r->flowSnap.ptr, 0, ((size_t)snap + 4u) * 4u, r->stream);
+    if (e != hipSuccess)
+        return undo(e);
+    if (const char *dbg = std::getenv("MRX_FLOW_PASS_ROWS"))    // tests: several staging passes at tiny sizes
+        r->flowPassRows = (uint32_t)std::max(0, std::atoi(dbg));
+    // the initial state is the previous state of the first frame: a still scene
+    e = r->launchFlowSnapshot();
+    if (e == hipSuccess) e = r->launchFlow();
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess)
+        return undo(e);
+    // per native pixel 4 bytes of depth and 4 of ids read, 16 written
+    r->info.bytes_per_step += px * 24ull;
+    return MRX_OK;
+}
+
+// takes the output off a shard again (mrx_flow_create failed on a later one)
+static void flowDestroyOne(mrx_renderer *r)
+{
+    (void)hipSetDevice(r->device);
+    (void)hipStreamSynchronize(r->stream);
+    r->info.bytes_per_step -= (uint64_t)r->info.num_views * r->info.storage_fast * r->info.storage_slow * 24ull;
+    r->flowOut.release(); r->flowSnap.release();
+}
+
+static bool flowOn(const mrx_renderer *r)
+{
+    return r->shards.empty() ? r->flowOut.ptr != nullptr : r->shards[0]->flowOut.ptr != nullptr;
+}
+
+int mrx_flow_create(mrx_renderer *r)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (r->parent)
+        return fail(MRX_E_INVALID, "mrx_flow_create on a shard: attach the output to the renderer it belongs to");
+    if (flowOn(r))
+        return fail(MRX_E_INVALID, "this renderer already has the optical-flow output");
+    const mrx_renderer *first = r->shards.empty() ? r : r->shards[0];
+    if (!first->ids.ptr || first->params.idsAreSegmask)
+        return fail(MRX_E_INVALID, "optical flow needs visibility ids: create the renderer with MRX_FLAG_VISIBILITY_IDS");
+    if (!first->depth.ptr)
+        return fail(MRX_E_INVALID, "optical flow needs depth: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)");
+    mrx_info_t whole {};
+    if (infoFull(r, &whole) != MRX_OK)
+        return MRX_E_INVALID;
+    if ((uint64_t)whole.num_views * whole.storage_fast * whole.storage_slow > mrx::kFlowMaxPixels)
+        return fail(MRX_E_INVALID, "optical flow: more than 2^32 - 1 native pixels");
+    if (r->shards.empty())
+        return flowCreateOne(r);
+    // all or nothing: a shard that fails takes the output of the shards before it along
+    for (size_t i = 0; i < r->shards.size(); ++i) {
+        const int rc = flowCreateOne(r->shards[i]);
+        if (rc != MRX_OK) {
+            const std::string why = g_err;
+            for (size_t k = 0; k < i; ++k)
+                flowDestroyOne(r->shards[k]);
+            return fail(rc, why);
+        }
+    }
+    return MRX_OK;
+}
+
+int mrx_flow_enabled(mrx_renderer *r)
+{
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    return flowOn(r) ? 1 : 0;
+}
+
+static int flowRun(mrx_renderer *r, bool snapshot)
+{
+    {
+        const int src = settle(r);
+        if (src != MRX_OK)
+            return src;
+    }
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (!flowOn(r))
+        return fail(MRX_E_UNSUPPORTED, "no optical flow: mrx_flow_create was not called on this renderer");
+    if (!r->shards.empty())
+        return shardsRun(r, snapshot ? kCmdFlowSnapshot : kCmdFlow);
+    MRX_HIP(hipSetDevice(r->device));
+    MRX_HIP(snapshot ? r->launchFlowSnapshot() : r->launchFlow());
+    return MRX_OK;
+}
+
+int mrx_flow(mrx_renderer *r) { return flowRun(r, false); }
+int mrx_flow_snapshot(mrx_renderer *r) { return flowRun(r, true); }
 
 int mrx_observations(mrx_renderer *r)
 {

@@ -319,6 +319,9 @@ PYBIND11_MODULE(madrona_renderer, m)
     m.attr("MRX_BUF_RAY_DISTANCE") = (int)MRX_BUF_RAY_DISTANCE;
     m.attr("MRX_BUF_RAY_ID") = (int)MRX_BUF_RAY_ID;
     m.attr("MRX_NUM_BUFFERS_EXT7") = (int)MRX_NUM_BUFFERS_EXT7;
+    // ... and of the optical-flow output
+    m.attr("MRX_BUF_FLOW") = (int)MRX_BUF_FLOW;
+    m.attr("MRX_NUM_BUFFERS_EXT8") = (int)MRX_NUM_BUFFERS_EXT8;
     m.attr("MRX_DTYPE_F16") = (int)MRX_DTYPE_F16;
     m.attr("MRX_DTYPE_BF16") = (int)MRX_DTYPE_BF16;
     m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
@@ -441,7 +444,8 @@ PYBIND11_MODULE(madrona_renderer, m)
                          const std::vector<int> &device_ids, int max_instances_per_world,
                          Manager::RenderOutputs render_outputs, py::object world_lights, py::object instance_colors,
                          py::object instance_materials, bool normals, py::object instance_labels, int supersample,
-                         py::object positions, py::object boxes, py::object observations, py::object rays) {
+                         py::object positions, py::object boxes, py::object observations, py::object rays,
+                         bool flow) {
                  const ObsArg obsArg = parseObservations(observations, render_outputs);
                  // rays: None (no sensor) or R, an int in 1 ... 65536
                  uint32_t raysPerWorld = 0;
@@ -467,6 +471,11 @@ PYBIND11_MODULE(madrona_renderer, m)
                      throw py::value_error("boxes must be None or an int in 1 ... 1024 (the number of labels)");
                  if (supersample < 1 || supersample > 4)
                      throw py::value_error("supersample must be 1, 2, 3 or 4");
+                 if (flow && render_outputs == Manager::RenderOutputs::RGB)
+                     throw py::value_error("flow needs depth: render_outputs RGB renders none");
+                 if (flow && boxLabels)
+                     throw py::value_error("flow and boxes exclude each other: under flow the ids tensor holds visibility "
+                                           "ids, the box stage needs a segmask");
                  // positions: False / None (no output), True or "world", or "view"
                  uint32_t positionFrame = 0;
                  if (py::isinstance<py::bool_>(positions))
@@ -609,6 +618,7 @@ PYBIND11_MODULE(madrona_renderer, m)
                  cfg.boxLabels = boxLabels;
                  cfg.observations = obsArg.field;
                  cfg.raysPerWorld = raysPerWorld;
+                 cfg.flow = flow;
                  std::unique_ptr<Manager> mgr(new Manager(cfg));
                  // (mrx_config cannot carry the range: the first frame is packed raw and restarted under it here)
                  if (obsArg.hasRange)
@@ -649,7 +659,9 @@ PYBIND11_MODULE(madrona_renderer, m)
              py::arg("observations") = py::none(),
              // rays = R: a ray-cast sensor of R rays per world (ray_tensor, ray_frame_tensor, ray_distance_tensor,
              // ray_id_tensor, trace)
-             py::arg("rays") = py::none())
+             py::arg("rays") = py::none(),
+             // flow = True: the optical-flow output (flow_tensor, flow, flow_snapshot); sets the visibility-ids flag
+             py::arg("flow") = false)
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
@@ -714,6 +726,15 @@ PYBIND11_MODULE(madrona_renderer, m)
              [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().rayIdTensor(shardOf(self, shard))); },
              py::arg("shard") = py::none())
         .def("trace", &Manager::trace)
+        // optical-flow output: whether there is one; f32 [views, H, W, 4] = (dx, dy, dz, 1) per pixel whose point was in
+        // front of the previous camera, zeros elsewhere (RuntimeError without flow=True); the flow stage alone, which
+        // does not advance the snapshot; the snapshot stage alone (after an episode reset wrote the poses)
+        .def_property_readonly("flows", &Manager::flows)
+        .def("flow_tensor",
+             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().flowTensor(shardOf(self, shard))); },
+             py::arg("shard") = py::none())
+        .def("flow", &Manager::flow)
+        .def("flow_snapshot", &Manager::flowSnapshot)
         // packed observation output: the option as a dict or None; [views, S * C, H, W] in the dtype asked for, frame 0
         // the oldest (RuntimeError without observations=); the reset column u8 [views] (RuntimeError with stack 1); the
         // observation stage alone -- on a stacked renderer one more frame; the depth range, whose setter restarts

@@ -79,6 +79,9 @@ class SceneDesc:
     # the ray-cast sensor (ray_tensor(), ray_frame_tensor(), ray_distance_tensor(), ray_id_tensor(), trace()): None =
     # none, R = that many caller-written rays per world, traced through the world's instances behind every render
     rays: object = None
+    # the optical-flow output (flow_tensor(), flow(), flow_snapshot()): per pixel the image-space motion since the
+    # previous step; sets the visibility-ids flag, so segmask_tensor() and boxes= are unavailable; needs depth
+    flow: bool = False
 
     def __post_init__(self):
         if self.mesh_vertices is None:
@@ -324,6 +327,8 @@ def make_renderer(desc, gpu_id=0, device_ids=None, render_outputs=None):
         extra["observations"] = desc.observations
     if desc.rays is not None:
         extra["rays"] = desc.rays
+    if desc.flow:
+        extra["flow"] = True
     if desc.max_instances_per_world:
         extra["max_instances_per_world"] = int(desc.max_instances_per_world)
     if render_outputs is not None:
