@@ -4,8 +4,8 @@ The flow kernel against tests/flow_oracle.flow applied to the renderer's own dep
 previous state -- read back from the tensors before the step that moves them -- on every bit: through the raster group
 kernel, the BVH tile kernel and the flat kernel, both modes, s = 1, 2, 3, a one-CU grid, a world of more rows than one
 staging pass and a world with spare rows.  The order of flow and snapshot on the stream, flow() and flow_snapshot()
-alone, every other output against a renderer without the option, two shards, the option off, the headless dump and the
-yardstick."""
+alone, every other output against a renderer without the option, two shards, the option off, boxes= and flow= refused together, the
+headless dump and the yardstick."""
 import dataclasses
 import os
 import statistics
@@ -276,6 +276,24 @@ def test_the_option_off(native):
     assert b.flows is True
     with pytest.raises(RuntimeError):
         b.segmask_tensor()                                  # the known limit: the ids tensor holds visibility ids
+
+
+def test_boxes_and_flow_together_are_refused_and_the_next_renderer_works(native):
+    """boxes= reads label or segmask ids, flow= turns the ids tensor into visibility ids: the pair is an error, raised
+    before anything is created, and leaves nothing behind that a renderer created right afterwards would trip over"""
+    scene = _scene("Rasterizer", 40, 24, worlds=3)
+    labelled = dataclasses.replace(scene, instance_labels=True, boxes=8)
+    with pytest.raises(ValueError, match="flow and boxes exclude each other"):
+        _make(dataclasses.replace(labelled, flow=True), visibility=False)
+    for desc in (labelled, dataclasses.replace(scene, flow=True)):
+        r = _make(desc, visibility=False)
+        r.step()
+        r.sync()
+        assert (_np(r.depth_tensor()) != 0).any()
+        if desc.boxes:
+            assert r.flows is False and (_np(r.box_tensor())[..., 4] > 0).any()
+        else:
+            assert r.flows is True and (_np(r.flow_tensor())[..., 3] == 1).any()
 
 
 def test_headless_dump_equals_the_tensor(native, tmp_path):
