@@ -18,8 +18,9 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "observe.hip", "rays.hip", "rays_host.cpp", "flow.hip", "flow_host.cpp", "bvh.cpp", "mrx_api.cpp", "assets.cpp", "ktx2.cpp"]
+HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "observe.hip", "rays.hip", "rays_host.cpp", "flow.hip", "flow_host.cpp", "bvh.cpp", "mrx_api.cpp", "scene.cpp", "stages.cpp", "shards.cpp", "host_tools.cpp", "assets.cpp", "ktx2.cpp"]
 HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "observe.hpp", "rays.hpp", "rays_core.hpp", "flow.hpp", "flow_core.hpp", "assets.hpp", "bc7_tables.inc",
+                          "renderer.hpp", "shards.hpp", "error.hpp",
                           "../../include/mrx.h"]
 MGR_SOURCES = ["manager.cpp"]
 MGR_DEPS = MGR_SOURCES + ["../../include/madrona_mi355/manager.hpp",
@@ -202,6 +203,26 @@ def build_flow_driver(force=False, verbose=False):
     return out
 
 
+def shards_driver_path():
+    return os.path.join(ROOT, "build", "shards_tsan_driver")
+
+
+def build_shards_driver(force=False, verbose=False):
+    """ThreadSanitizer build of the shard-worker protocol (shards.cpp: no HIP in it) with its driver,
+    csrc/shards_tsan_driver.cpp, whose stub callback stands in for the renderer.  Host compiler only; run by
+    tests/test_sanitizers.py on the CPU, as a stand-alone program -- never on the GPU box."""
+    out = shards_driver_path()
+    srcs = ["shards_tsan_driver.cpp", "shards.cpp"]
+    deps = srcs + ["shards.hpp", "error.hpp", "../../include/mrx.h"]
+    if force or _stale(out, deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=thread", "-fno-omit-frame-pointer"]
+        cmd += [os.path.join(CSRC, s) for s in srcs]
+        cmd += ["-lpthread", "-o", out]
+        _run(cmd, verbose)
+    return out
+
+
 def build_all(force=False, verbose=False):
     build_hip(force, verbose)
     build_manager(force, verbose)
@@ -215,6 +236,8 @@ if __name__ == "__main__":
         print(build_asan(force="--force" in sys.argv, verbose=True))
     elif "--flow-driver" in sys.argv:
         print(build_flow_driver(force="--force" in sys.argv, verbose=True))
+    elif "--shards-driver" in sys.argv:
+        print(build_shards_driver(force="--force" in sys.argv, verbose=True))
     elif "--rays-driver" in sys.argv:
         print(build_rays_driver(force="--force" in sys.argv, verbose=True))
     else:

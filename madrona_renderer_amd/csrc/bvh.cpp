@@ -243,7 +243,7 @@ void buildBlas(const ObjTri *tris, const std::vector<int32_t> &objFirst,
                 uint32_t depth = 0;
                 const uint32_t root = collapse(bl, rootBin, out, 1, depth, attempt == 1);
                 // a pop pushes at most eight entries: 1 + 7 per level bounds the stack.  The
-                // balanced rebuild is accepted as it comes: buildScene (mrx_api.cpp) refuses a
+                // balanced rebuild is accepted as it comes: buildScene (scene.cpp) refuses a
                 // scene whose deepest BLAS still exceeds the bound
                 if (1 + 7 * depth <= kBvhStackCap || attempt == 1) {
                     info.root = (int32_t)root;

@@ -63,7 +63,7 @@ def test_dense_scene_raytracer_overflows():
 
 @pytest.mark.parametrize("tex_cap,rounds", [(64, 40), (96, 30), (1008, 4)])
 def test_textured_dense_scene_overflows_at_every_cap(tex_cap, rounds):
-    # case b: the default cap is at most 1008 records (mrx_api.cpp chooseBvhGroups)
+    # case b: the default cap is at most 1008 records (scene.cpp chooseBvhGroups)
     w = _wit(br.dense_scene(textured=True), textured=True, tex_cap=tex_cap)
     assert br.max_rounds(w, view=0) >= rounds
 
@@ -114,7 +114,7 @@ def test_one_tile_views_overflow():
 
 
 def test_small_worlds_are_the_flat_kernels():
-    # case l: at most 64 triangles in at most 64 rows per world (mrx_api.cpp chooseBvhGroups), views of several tiles
+    # case l: at most 64 triangles in at most 64 rows per world (scene.cpp chooseBvhGroups), views of several tiles
     d = br.small_world_scene(200)
     from oracle import oracle
     fs = oracle.FlatScene(d)

@@ -41,7 +41,7 @@ def test_configs3_every_shard_against_the_oracle_and_the_whole_against_one_rende
     import torch
     desc, ref = job
     # a host thread per shard, as on a node of eight devices (by default shards that share a
-    # device share a thread: mrx_api.cpp startShardWorkers)
+    # device share a thread: shards.cpp startShardWorkers)
     monkeypatch.setenv("MRX_SHARD_THREADS", "2")
     monkeypatch.setenv("MADRONA_MI355_VISIBILITY", "1" if ids else "0")
     many = scenes.make_renderer(desc, device_ids=[0] * SHARDS)

@@ -2,7 +2,8 @@
 VERDICT r2 item 9): the oracle (`make -C oracle asan`) and the host code that reads untrusted
 input -- OBJ / MTL / PNG / KTX2 / BC7 readers and the BLAS builder (`python -m
 madrona_renderer_amd.build --asan`).  CPU only: GPU AddressSanitizer is not available on the
-pool.  A sanitizer report aborts the driver, so a zero exit status is the assertion."""
+pool.  A sanitizer report aborts the driver, so a zero exit status is the assertion.
+The shard-worker protocol runs under ThreadSanitizer the same way (`--shards-driver`): a stand-alone program."""
 import glob
 import os
 import subprocess
@@ -58,3 +59,16 @@ def test_blas_builder_under_sanitizers(host_driver, tris, kind):
     # recursion cap and the balanced rebuild), coincident centroids (median split by index)
     out = _run([host_driver, "blas", str(tris), "5", str(kind)])
     assert "stack bound holds" in out
+
+
+def test_shard_protocol_under_thread_sanitizer():
+    # the shard-worker protocol (csrc/shards.cpp) against a stub renderer: sync and async mode, spin 0 and 50 us,
+    # 2 / 3 / 8 groups and shards sharing one, bursts, futex sleeps, failures, stops, and 10000 rounds per spin
+    # setting of "two renders, at once a timed command, a sync" with exact per-round counts -- the round a worker
+    # ran a command under another post's sequence number would count the timed command twice
+    driver = build.build_shards_driver()
+    p = subprocess.run([driver, "10000"], capture_output=True, text=True, timeout=300, cwd=ROOT,
+                       env=dict(os.environ, TSAN_OPTIONS="halt_on_error=0:exitcode=66"))
+    assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
+    assert "ThreadSanitizer" not in p.stderr and "WARNING" not in p.stderr, p.stderr[-3000:]
+    assert "10000 pairing rounds per spin setting, all passed" in p.stdout

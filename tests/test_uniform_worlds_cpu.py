@@ -1,6 +1,6 @@
 """CPU checks of the uniform-world generator (tests/uniform_worlds.py) that the FAST raster group kernel's
 GPU tests use: it is deterministic, every scene it names meets the host's uniformity predicate (restated
-here from mrx_api.cpp bindGeometry and raster.hip launchRaster), the batches reach the cases the kernel's
+here from scene.cpp bindGeometry and raster.hip launchRaster), the batches reach the cases the kernel's
 per-strip near-free bit and tie rule decide, and the oracle agrees with the independent float64 caster
 and shading model on them."""
 import numpy as np
@@ -12,7 +12,7 @@ from tests.util import digest
 
 
 def fast_eligible(desc, fs):
-    """The host's conditions for the FAST entry, from the scene alone (mrx_api.cpp bindGeometry: uniInstances,
+    """The host's conditions for the FAST entry, from the scene alone (scene.cpp bindGeometry: uniInstances,
     uniCamsPerWorld, uniPrefix, uniFirstTri; raster.hip launchRaster: 16 slots, one tile per view)."""
     w0 = desc.worlds[0]
     n0, c0 = w0[0], w0[2]

@@ -1,7 +1,7 @@
 """Deterministic uniform worlds for the FAST raster group kernel (raster.hip, rasterGroupKernelFast).
 
 The host gives a batch to that kernel only when its worlds are uniform and its views fit one tile
-(mrx_api.cpp bindGeometry, raster.hip launchRaster): every world binds the same 1..4 drawn objects in the
+(scene.cpp bindGeometry, raster.hip launchRaster): every world binds the same 1..4 drawn objects in the
 same order and has the same number of cameras (below 256), a world draws at most 16 triangles, a view is at
 most 64x64 and every used object's first triangle is below 65536.  The scenes here keep to all of that and
 put the hard cases inside it: cube.obj next to raw meshes holding exact duplicate triangles (ties), a
