@@ -105,7 +105,7 @@ def build_manager(force=False, verbose=False):
 def build_module(force=False, verbose=False):
     import pybind11
     out = module_path()
-    if force or _stale(out, PY_SOURCES + MGR_DEPS) or \
+    if force or _stale(out, PY_SOURCES + MGR_DEPS + ["obs_names.hpp"]) or \
             os.path.getmtime(out) < os.path.getmtime(lib_path()):
         cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wall",
                "-fvisibility=hidden",
@@ -124,7 +124,7 @@ def headless_path():
 def build_headless(force=False, verbose=False):
     """The reference's headless CLI (src/headless.cpp) over the MI355X Manager."""
     out = headless_path()
-    deps = ["headless.cpp", "assets.cpp", "assets.hpp"] + MGR_DEPS
+    deps = ["headless.cpp", "assets.cpp", "assets.hpp", "obs_names.hpp"] + MGR_DEPS
     if force or _stale(out, deps) or os.path.getmtime(out) < os.path.getmtime(lib_path()):
         cmd = ["g++", "-O2", "-std=c++17", "-Wall",
                "-DMRX_DATA_DIR=\"%s\"" % os.path.join(ROOT, "data"),

@@ -53,6 +53,7 @@
 #include <cerrno>
 #include <chrono>
 #include <cmath>
+#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -62,6 +63,7 @@
 #include "../../include/madrona_mi355/manager.hpp"
 #include "../../include/mrx.h"
 #include "assets.hpp"
+#include "obs_names.hpp"
 
 #ifndef MRX_DATA_DIR
 #define MRX_DATA_DIR "data"
@@ -131,25 +133,58 @@ std::vector<std::string> splitCommas(const char *s)
     return fields;
 }
 
+// a refusal: the text on stderr, EXIT_FAILURE
+[[noreturn]] __attribute__((format(printf, 1, 2))) void die(const char *fmt, ...)
+{
+    va_list ap;
+    va_start(ap, fmt);
+    std::vfprintf(stderr, fmt, ap);
+    va_end(ap);
+    std::exit(EXIT_FAILURE);
+}
+
 // a number of the whole argument, finite
 float parseFloat(const char *flag, const char *s)
 {
     char *end = nullptr;
     const float v = std::strtof(s, &end);
-    if (!*s || *end || !std::isfinite(v)) {
-        std::fprintf(stderr, "%s: not a number: %s\n", flag, s);
-        std::exit(EXIT_FAILURE);
-    }
+    if (!*s || *end || !std::isfinite(v))
+        die("%s: not a number: %s\n", flag, s);
     return v;
+}
+
+// an unsigned integer of the whole argument in `base` (0: strtoull's prefixes), without a sign
+bool parseUnsigned(const char *s, int base, unsigned long long &v)
+{
+    char *end = nullptr;
+    errno = 0;
+    v = std::strtoull(s, &end, base);
+    return *s && *s != '-' && *s != '+' && !*end && errno == 0;
+}
+
+// the SEED of --instance-colors, --instance-materials and --instance-labels
+uint64_t parseSeed(const char *flag, const char *s)
+{
+    unsigned long long v = 0;
+    if (!parseUnsigned(s, 0, v))
+        die("%s: not an unsigned integer seed: %s\n", flag, s);
+    return v;
+}
+
+// a decimal count in 1 ... hi; `what` is the noun of the refusal ("a factor", "a number of labels")
+uint32_t parseCount(const char *flag, const char *what, unsigned long long hi, const char *s)
+{
+    unsigned long long v = 0;
+    if (!parseUnsigned(s, 10, v) || v < 1 || v > hi)
+        die("%s: not %s from 1 to %llu: %s\n", flag, what, hi, s);
+    return (uint32_t)v;
 }
 
 [[noreturn]] void usage(const char *argv0)
 {
-    std::fprintf(stderr,
-                 "%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
-                 "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]] [--boxes K] [--rays R] [--flow] [--observations CHANNELS[,DTYPE[,STACK]]] [--obs-depth-range LO,HI]\n",
-                 argv0);
-    std::exit(EXIT_FAILURE);
+    die("%s [NUM_WORLDS] [NUM_STEPS] [rt|rast] [BATCH_WIDTH] [BATCH_HEIGHT] "
+        "[--dump-last-frame file_name_without_extension] [--scene synthetic|demo] [--depth] [--gpus N] [--outputs rgbd|depth|rgb] [--vfov DEG] [--znear Z] [--light X,Y,Z[,AMBIENT,DIFFUSE]] [--instance-colors SEED] [--instance-materials SEED] [--normals] [--instance-labels SEED] [--supersample N] [--positions [world|view]] [--boxes K] [--rays R] [--flow] [--observations CHANNELS[,DTYPE[,STACK]]] [--obs-depth-range LO,HI]\n",
+        argv0);
 }
 
 Args parse(int argc, char **argv)
@@ -165,221 +200,124 @@ Args parse(int argc, char **argv)
     a.width = (uint32_t)std::atoi(argv[4]);
     a.height = (uint32_t)std::atoi(argv[5]);
     for (int i = 6; i < argc; ++i) {
-        if (!std::strcmp(argv[i], "--dump-last-frame") && i + 1 < argc) {
+        // option `name` without a value; and the value of option `name`, null unless argv[i] is it and a value follows
+        const auto is = [&](const char *name) { return !std::strcmp(argv[i], name); };
+        const auto value = [&](const char *name) -> const char * { return is(name) && i + 1 < argc ? argv[++i] : nullptr; };
+        const char *v = nullptr;
+        if ((v = value("--dump-last-frame"))) {
             a.dump = true;
-            a.outName = argv[++i];
-        } else if (!std::strcmp(argv[i], "--scene") && i + 1 < argc) {
-            a.demo = !std::strcmp(argv[++i], "demo");
-        } else if (!std::strcmp(argv[i], "--depth")) {
+            a.outName = v;
+        } else if ((v = value("--scene"))) {
+            a.demo = !std::strcmp(v, "demo");
+        } else if (is("--depth")) {
             a.dumpDepth = true;
-        } else if (!std::strcmp(argv[i], "--normals")) {
+        } else if (is("--normals")) {
             a.normals = true;
-        } else if (!std::strcmp(argv[i], "--gpus") && i + 1 < argc) {
-            a.gpus = (uint32_t)std::atoi(argv[++i]);
-        } else if (!std::strcmp(argv[i], "--vfov") && i + 1 < argc) {
-            a.vfov = parseFloat("--vfov", argv[++i]);
-            if (!(a.vfov > 0.0f && a.vfov < 180.0f)) {
-                std::fprintf(stderr, "--vfov: %s is not in (0, 180) degrees\n", argv[i]);
-                std::exit(EXIT_FAILURE);
-            }
-        } else if (!std::strcmp(argv[i], "--light") && i + 1 < argc) {
+        } else if ((v = value("--gpus"))) {
+            a.gpus = (uint32_t)std::atoi(v);
+        } else if ((v = value("--vfov"))) {
+            a.vfov = parseFloat("--vfov", v);
+            if (!(a.vfov > 0.0f && a.vfov < 180.0f))
+                die("--vfov: %s is not in (0, 180) degrees\n", v);
+        } else if ((v = value("--light"))) {
             // three or five numbers; the library's own check decides (mrx_light_constants needs no device)
-            std::vector<std::string> fields(1);
-            for (const char *ch = argv[++i]; *ch; ++ch) {
-                if (*ch == ',')
-                    fields.emplace_back();
-                else
-                    fields.back() += *ch;
-            }
-            const int n = (int)fields.size();
-            float v[5] = { 0.0f, 0.0f, 0.0f, a.light.ambient, a.light.diffuse };
-            for (int k = 0; k < n && k < 5; ++k)
-                v[k] = parseFloat("--light", fields[(size_t)k].c_str());
-            float c[5];
-            const mrx_light l = { { v[0], v[1], v[2] }, v[3], v[4] };
-            if (n != 3 && n != 5) {
-                std::fprintf(stderr, "--light: wants X,Y,Z or X,Y,Z,AMBIENT,DIFFUSE, got %s\n", argv[i]);
-                std::exit(EXIT_FAILURE);
-            }
-            if (mrx_light_constants(l, c) != MRX_OK) {
-                std::fprintf(stderr, "--light: %s\n", mrx_last_error());
-                std::exit(EXIT_FAILURE);
-            }
-            a.light = { { v[0], v[1], v[2] }, v[3], v[4] };
+            const std::vector<std::string> fields = splitCommas(v);
+            const size_t n = fields.size();
+            float l[5] = { 0.0f, 0.0f, 0.0f, a.light.ambient, a.light.diffuse }, c[5];
+            for (size_t k = 0; k < n && k < 5; ++k)
+                l[k] = parseFloat("--light", fields[k].c_str());
+            if (n != 3 && n != 5)
+                die("--light: wants X,Y,Z or X,Y,Z,AMBIENT,DIFFUSE, got %s\n", v);
+            if (mrx_light_constants(mrx_light { { l[0], l[1], l[2] }, l[3], l[4] }, c) != MRX_OK)
+                die("--light: %s\n", mrx_last_error());
+            a.light = { { l[0], l[1], l[2] }, l[3], l[4] };
             a.hasLight = true;
-        } else if (!std::strcmp(argv[i], "--instance-colors") && i + 1 < argc) {
-            const char *s = argv[++i];
-            char *end = nullptr;
-            errno = 0;
-            a.colorSeed = std::strtoull(s, &end, 0);
-            if (!*s || *s == '-' || *s == '+' || *end || errno != 0) {
-                std::fprintf(stderr, "--instance-colors: not an unsigned integer seed: %s\n", s);
-                std::exit(EXIT_FAILURE);
-            }
+        } else if ((v = value("--instance-colors"))) {
+            a.colorSeed = parseSeed("--instance-colors", v);
             a.hasColors = true;
-        } else if (!std::strcmp(argv[i], "--instance-materials") && i + 1 < argc) {
-            const char *s = argv[++i];
-            char *end = nullptr;
-            errno = 0;
-            a.materialSeed = std::strtoull(s, &end, 0);
-            if (!*s || *s == '-' || *s == '+' || *end || errno != 0) {
-                std::fprintf(stderr, "--instance-materials: not an unsigned integer seed: %s\n", s);
-                std::exit(EXIT_FAILURE);
-            }
+        } else if ((v = value("--instance-materials"))) {
+            a.materialSeed = parseSeed("--instance-materials", v);
             a.hasMaterials = true;
-        } else if (!std::strcmp(argv[i], "--instance-labels") && i + 1 < argc) {
-            const char *s = argv[++i];
-            char *end = nullptr;
-            errno = 0;
-            a.labelSeed = std::strtoull(s, &end, 0);
-            if (!*s || *s == '-' || *s == '+' || *end || errno != 0) {
-                std::fprintf(stderr, "--instance-labels: not an unsigned integer seed: %s\n", s);
-                std::exit(EXIT_FAILURE);
-            }
+        } else if ((v = value("--instance-labels"))) {
+            a.labelSeed = parseSeed("--instance-labels", v);
             a.hasLabels = true;
-        } else if (!std::strcmp(argv[i], "--supersample") && i + 1 < argc) {
-            const char *s = argv[++i];
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long v = std::strtoull(s, &end, 10);
-            if (!*s || *s == '-' || *s == '+' || *end || errno != 0 || v < 1 || v > 4) {
-                std::fprintf(stderr, "--supersample: not a factor from 1 to 4: %s\n", s);
-                std::exit(EXIT_FAILURE);
-            }
-            a.supersample = (uint32_t)v;
-        } else if (!std::strcmp(argv[i], "--boxes") && i + 1 < argc) {
-            const char *s = argv[++i];
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long v = std::strtoull(s, &end, 10);
-            if (!*s || *s == '-' || *s == '+' || *end || errno != 0 || v < 1 || v > 1024) {
-                std::fprintf(stderr, "--boxes: not a number of labels from 1 to 1024: %s\n", s);
-                std::exit(EXIT_FAILURE);
-            }
-            a.boxes = (uint32_t)v;
-        } else if (!std::strcmp(argv[i], "--rays") && i + 1 < argc) {
-            const char *s = argv[++i];
-            char *end = nullptr;
-            errno = 0;
-            const unsigned long long v = std::strtoull(s, &end, 10);
-            if (!*s || *s == '-' || *s == '+' || *end || errno != 0 || v < 1 || v > 65536) {
-                std::fprintf(stderr, "--rays: not a number of rays per world from 1 to 65536: %s\n", s);
-                std::exit(EXIT_FAILURE);
-            }
-            a.rays = (uint32_t)v;
-        } else if (!std::strcmp(argv[i], "--flow")) {
+        } else if ((v = value("--supersample"))) {
+            a.supersample = parseCount("--supersample", "a factor", 4, v);
+        } else if ((v = value("--boxes"))) {
+            a.boxes = parseCount("--boxes", "a number of labels", 1024, v);
+        } else if ((v = value("--rays"))) {
+            a.rays = parseCount("--rays", "a number of rays per world", 65536, v);
+        } else if (is("--flow")) {
             a.flow = true;
-        } else if (!std::strcmp(argv[i], "--observations") && i + 1 < argc) {
-            static const char *const layouts[] = { "", "rgb", "rgbd", "d", "y", "yd" };
-            static const char *const dtypes[] = { "float32", "float16", "bfloat16", "uint8" };
-            const char *v = argv[++i];
+        } else if ((v = value("--observations"))) {
             const std::vector<std::string> f = splitCommas(v);
-            uint32_t layout = 0, dtype = f.size() > 1 ? 4u : 0u, stack = 1;
-            for (uint32_t k = 1; k <= 5; ++k)
-                if (f[0] == layouts[k])
-                    layout = k;
-            for (uint32_t k = 0; f.size() > 1 && k < 4; ++k)
-                if (f[1] == dtypes[k])
-                    dtype = k;
+            const uint32_t layout = obsLayoutOf(f[0]), dtype = f.size() > 1 ? obsDtypeOf(f[1]) : 0u;
+            uint32_t stack = 1;
             if (f.size() > 2) {
                 const char *t = f[2].c_str();
                 stack = t[0] >= '1' && t[0] <= '8' && !t[1] ? (uint32_t)(t[0] - '0') : 0u;
             }
-            if (!layout || dtype == 4 || !stack || f.size() > 3) {
-                std::fprintf(stderr, "--observations: wants CHANNELS[,DTYPE[,STACK]] -- rgb|rgbd|d|y|yd, "
-                                     "float32|float16|bfloat16|uint8, 1 ... 8 -- got: %s\n", v);
-                std::exit(EXIT_FAILURE);
-            }
+            if (!layout || dtype == kNumObsDtypes || !stack || f.size() > 3)
+                die("--observations: wants CHANNELS[,DTYPE[,STACK]] -- rgb|rgbd|d|y|yd, "
+                    "float32|float16|bfloat16|uint8, 1 ... 8 -- got: %s\n", v);
             a.obsLayout = layout; a.obsDtype = dtype; a.obsStack = stack;
-        } else if (!std::strcmp(argv[i], "--obs-depth-range") && i + 1 < argc) {
-            const char *v = argv[++i];
+        } else if ((v = value("--obs-depth-range"))) {
             const std::vector<std::string> f = splitCommas(v);
-            if (f.size() != 2) {
-                std::fprintf(stderr, "--obs-depth-range: wants LO,HI, got: %s\n", v);
-                std::exit(EXIT_FAILURE);
-            }
+            if (f.size() != 2)
+                die("--obs-depth-range: wants LO,HI, got: %s\n", v);
             a.obsLo = parseFloat("--obs-depth-range", f[0].c_str());
             a.obsHi = parseFloat("--obs-depth-range", f[1].c_str());
-            if (!(a.obsLo >= 0.0f && a.obsLo < a.obsHi)) {
-                std::fprintf(stderr, "--obs-depth-range: wants 0 <= LO < HI, got: %s\n", v);
-                std::exit(EXIT_FAILURE);
-            }
+            if (!(a.obsLo >= 0.0f && a.obsLo < a.obsHi))
+                die("--obs-depth-range: wants 0 <= LO < HI, got: %s\n", v);
             a.hasObsRange = true;
-        } else if (!std::strcmp(argv[i], "--positions")) {
+        } else if (is("--positions")) {
             // the frame is optional: the next argument is taken for it unless it is another option
             a.positions = 1;
             if (i + 1 < argc && std::strncmp(argv[i + 1], "--", 2) != 0) {
                 const char *f = argv[++i];
                 if (!std::strcmp(f, "view"))
                     a.positions = 2;
-                else if (std::strcmp(f, "world") != 0) {
-                    std::fprintf(stderr, "--positions: the frame is world or view, not: %s\n", f);
-                    std::exit(EXIT_FAILURE);
-                }
+                else if (std::strcmp(f, "world") != 0)
+                    die("--positions: the frame is world or view, not: %s\n", f);
             }
-        } else if (!std::strcmp(argv[i], "--znear") && i + 1 < argc) {
-            a.znear = parseFloat("--znear", argv[++i]);
-            if (!(a.znear > 0.0f)) {
-                std::fprintf(stderr, "--znear: %s is not > 0\n", argv[i]);
-                std::exit(EXIT_FAILURE);
-            }
-        } else if (!std::strcmp(argv[i], "--outputs") && i + 1 < argc) {
-            const char *o = argv[++i];
-            if (!std::strcmp(o, "rgbd")) a.outputs = Manager::RenderOutputs::RGBD;
-            else if (!std::strcmp(o, "depth")) a.outputs = Manager::RenderOutputs::Depth;
-            else if (!std::strcmp(o, "rgb")) a.outputs = Manager::RenderOutputs::RGB;
+        } else if ((v = value("--znear"))) {
+            a.znear = parseFloat("--znear", v);
+            if (!(a.znear > 0.0f))
+                die("--znear: %s is not > 0\n", v);
+        } else if ((v = value("--outputs"))) {
+            if (!std::strcmp(v, "rgbd")) a.outputs = Manager::RenderOutputs::RGBD;
+            else if (!std::strcmp(v, "depth")) a.outputs = Manager::RenderOutputs::Depth;
+            else if (!std::strcmp(v, "rgb")) a.outputs = Manager::RenderOutputs::RGB;
             else usage(argv[0]);
         } else {
             usage(argv[0]);
         }
     }
+    const bool noRgb = a.outputs == Manager::RenderOutputs::Depth, noDepth = a.outputs == Manager::RenderOutputs::RGB;
     if (a.numWorlds == 0 || a.width == 0 || a.height == 0 || a.gpus == 0 || a.gpus > a.numWorlds)
         usage(argv[0]);
-    if ((uint64_t)a.supersample * a.width > 16384 || (uint64_t)a.supersample * a.height > 16384) {
-        std::fprintf(stderr, "--supersample: %u times %u x %u is more than 16384 pixels a side\n", a.supersample, a.width,
-                     a.height);
-        std::exit(EXIT_FAILURE);
-    }
-    if (a.mode == Mode::Raycaster && !(a.znear < 1000.0f)) {
-        std::fprintf(stderr, "--znear: must be below the Raytracer far plane (1000)\n");
-        std::exit(EXIT_FAILURE);
-    }
-    if (a.dumpDepth && a.outputs == Manager::RenderOutputs::RGB) {
-        std::fprintf(stderr, "--depth: depth is not rendered with --outputs rgb\n");
-        std::exit(EXIT_FAILURE);
-    }
-    if (a.positions && a.outputs == Manager::RenderOutputs::RGB) {
-        std::fprintf(stderr, "--positions: positions are computed from depth, which is not rendered with --outputs rgb\n");
-        std::exit(EXIT_FAILURE);
-    }
-    if (a.flow && a.outputs == Manager::RenderOutputs::RGB) {
-        std::fprintf(stderr, "--flow: the flow is computed from depth, which is not rendered with --outputs rgb\n");
-        std::exit(EXIT_FAILURE);
-    }
-    if (a.flow && (a.boxes || a.hasLabels)) {
-        std::fprintf(stderr, "--flow: the ids tensor holds visibility ids, so there is no segmask for --boxes or --instance-labels\n");
-        std::exit(EXIT_FAILURE);
-    }
-    if (a.boxes && a.mode == Mode::Rasterizer && !a.hasLabels) {
-        std::fprintf(stderr, "--boxes: boxes are computed from the segmask, which rast has only with --instance-labels\n");
-        std::exit(EXIT_FAILURE);
-    }
-    {
-        const bool colour = a.obsLayout && a.obsLayout != MRX_OBS_D;
-        const bool depth = a.obsLayout == MRX_OBS_RGBD || a.obsLayout == MRX_OBS_D || a.obsLayout == MRX_OBS_YD;
-        if (colour && a.outputs == Manager::RenderOutputs::Depth) {
-            std::fprintf(stderr, "--observations: these channels need rgb, which is not rendered with --outputs depth\n");
-            std::exit(EXIT_FAILURE);
-        }
-        if (depth && a.outputs == Manager::RenderOutputs::RGB) {
-            std::fprintf(stderr, "--observations: these channels need depth, which is not rendered with --outputs rgb\n");
-            std::exit(EXIT_FAILURE);
-        }
-        if (a.hasObsRange && !depth) {
-            std::fprintf(stderr, "--obs-depth-range: needs --observations with a depth channel (rgbd, d or yd)\n");
-            std::exit(EXIT_FAILURE);
-        }
-    }
+    if ((uint64_t)a.supersample * a.width > 16384 || (uint64_t)a.supersample * a.height > 16384)
+        die("--supersample: %u times %u x %u is more than 16384 pixels a side\n", a.supersample, a.width, a.height);
+    if (a.mode == Mode::Raycaster && !(a.znear < 1000.0f))
+        die("--znear: must be below the Raytracer far plane (1000)\n");
+    if (a.dumpDepth && noDepth)
+        die("--depth: depth is not rendered with --outputs rgb\n");
+    if (a.positions && noDepth)
+        die("--positions: positions are computed from depth, which is not rendered with --outputs rgb\n");
+    if (a.flow && noDepth)
+        die("--flow: the flow is computed from depth, which is not rendered with --outputs rgb\n");
+    if (a.flow && (a.boxes || a.hasLabels))
+        die("--flow: the ids tensor holds visibility ids, so there is no segmask for --boxes or --instance-labels\n");
+    if (a.boxes && a.mode == Mode::Rasterizer && !a.hasLabels)
+        die("--boxes: boxes are computed from the segmask, which rast has only with --instance-labels\n");
+    const bool colour = a.obsLayout && a.obsLayout != MRX_OBS_D;
+    const bool depth = a.obsLayout == MRX_OBS_RGBD || a.obsLayout == MRX_OBS_D || a.obsLayout == MRX_OBS_YD;
+    if (colour && noRgb)
+        die("--observations: these channels need rgb, which is not rendered with --outputs depth\n");
+    if (depth && noDepth)
+        die("--observations: these channels need depth, which is not rendered with --outputs rgb\n");
+    if (a.hasObsRange && !depth)
+        die("--obs-depth-range: needs --observations with a depth channel (rgbd, d or yd)\n");
     return a;
 }
 
@@ -507,6 +445,28 @@ void buildDemo(Scene &s, uint32_t n, const std::string &dataDir)
 // DumpWhat::Labels: the segmask of a renderer with the label column: the low 24 bits of each pixel's label as
 // (r, g, b), r lowest, alpha 255; background pixels (-1) are (0, 0, 0, 0).
 enum class DumpWhat { Rgb, Depth, InvDepth, Normal, Labels };
+
+// how a dump ends when the library refused a copy: its text on stderr, false
+bool libraryError()
+{
+    std::fprintf(stderr, "%s\n", mrx_last_error());
+    return false;
+}
+
+// the tail of the dumps below: `head`, then `bodyBytes` of `body`, as the file `path`; false, and a line on stderr,
+// unless every byte was written and the file closed
+bool writeFile(const std::string &path, const std::string &head, const void *body = nullptr, size_t bodyBytes = 0)
+{
+    FILE *f = std::fopen(path.c_str(), "wb");
+    bool ok = f && std::fwrite(head.data(), 1, head.size(), f) == head.size() &&
+              (!bodyBytes || std::fwrite(body, 1, bodyBytes, f) == bodyBytes);
+    if (f && std::fclose(f) != 0)
+        ok = false;
+    if (!ok)
+        std::fprintf(stderr, "cannot write %s\n", path.c_str());
+    return ok;
+}
+
 bool dumpTiled(const std::string &name, mrx_renderer *shard, uint32_t numImages, uint32_t resX,
                uint32_t resY, DumpWhat what, bool transpose)
 {
@@ -515,10 +475,8 @@ bool dumpTiled(const std::string &name, mrx_renderer *shard, uint32_t numImages,
     std::vector<uint8_t> host(bytesPerImage * numImages);
     if (mrx_copy_to_host(shard, depth ? MRX_BUF_DEPTH : what == DumpWhat::Normal ? MRX_BUF_NORMAL
                                 : what == DumpWhat::Labels ? MRX_BUF_SEGMASK : MRX_BUF_RGB,
-                         host.data(), host.size()) != MRX_OK) {
-        std::fprintf(stderr, "%s\n", mrx_last_error());
-        return false;
-    }
+                         host.data(), host.size()) != MRX_OK)
+        return libraryError();
     float dmin = 0.0f;
     if (what == DumpWhat::InvDepth)
         for (size_t i = 0; i < host.size() / 4; ++i) {
@@ -572,10 +530,8 @@ bool dumpPly(const std::string &name, mrx_renderer *shard, uint32_t numImages, u
     std::vector<float> pos(px * 4);
     std::vector<uint8_t> rgb(withRgb ? px * 4 : 0);
     if (mrx_copy_to_host(shard, MRX_BUF_POSITION, pos.data(), pos.size() * sizeof(float)) != MRX_OK ||
-        (withRgb && mrx_copy_to_host(shard, MRX_BUF_RGB, rgb.data(), rgb.size()) != MRX_OK)) {
-        std::fprintf(stderr, "%s\n", mrx_last_error());
-        return false;
-    }
+        (withRgb && mrx_copy_to_host(shard, MRX_BUF_RGB, rgb.data(), rgb.size()) != MRX_OK))
+        return libraryError();
     size_t hits = 0;
     for (size_t i = 0; i < px; ++i)
         hits += pos[4 * i + 3] != 0.0f ? 1 : 0;
@@ -592,13 +548,7 @@ bool dumpPly(const std::string &name, mrx_renderer *shard, uint32_t numImages, u
         if (withRgb)
             out.append(reinterpret_cast<const char *>(&rgb[4 * i]), 3);
     }
-    FILE *f = std::fopen((name + ".ply").c_str(), "wb");
-    const bool ok = f && std::fwrite(out.data(), 1, out.size(), f) == out.size();
-    if (f && std::fclose(f) != 0)
-        return false;
-    if (!ok)
-        std::fprintf(stderr, "cannot write %s.ply\n", name.c_str());
-    return ok;
+    return writeFile(name + ".ply", out);
 }
 
 // NAME.boxes.txt of --boxes: one line `view label xmin ymin xmax ymax count` per non-empty row of the box tensor of
@@ -606,22 +556,18 @@ bool dumpPly(const std::string &name, mrx_renderer *shard, uint32_t numImages, u
 bool dumpBoxes(const std::string &name, mrx_renderer *shard, uint32_t numImages, uint32_t K)
 {
     std::vector<int32_t> rows((size_t)numImages * K * 5);
-    if (mrx_copy_to_host(shard, MRX_BUF_BOXES, rows.data(), rows.size() * sizeof(int32_t)) != MRX_OK) {
-        std::fprintf(stderr, "%s\n", mrx_last_error());
-        return false;
-    }
-    FILE *f = std::fopen((name + ".boxes.txt").c_str(), "w");
-    bool ok = f != nullptr;
-    for (size_t i = 0; ok && i < (size_t)numImages * K; ++i) {
+    if (mrx_copy_to_host(shard, MRX_BUF_BOXES, rows.data(), rows.size() * sizeof(int32_t)) != MRX_OK)
+        return libraryError();
+    std::string out;
+    char line[160];
+    for (size_t i = 0; i < (size_t)numImages * K; ++i) {
         const int32_t *b = &rows[5 * i];
-        if (b[4] > 0)
-            ok = std::fprintf(f, "%zu %zu %d %d %d %d %d\n", i / K, i % K, b[0], b[1], b[2], b[3], b[4]) > 0;
+        if (b[4] > 0) {
+            std::snprintf(line, sizeof line, "%zu %zu %d %d %d %d %d\n", i / K, i % K, b[0], b[1], b[2], b[3], b[4]);
+            out += line;
+        }
     }
-    if (f && std::fclose(f) != 0)
-        ok = false;
-    if (!ok)
-        std::fprintf(stderr, "cannot write %s.boxes.txt\n", name.c_str());
-    return ok;
+    return writeFile(name + ".boxes.txt", out);
 }
 
 // NAME.rays.txt of --rays: one line `world ray t id` per ray of the shard's worlds (world numbers are the job's), t with
@@ -631,19 +577,15 @@ bool dumpRays(const std::string &name, mrx_renderer *shard, uint32_t firstWorld,
     std::vector<float> t((size_t)numWorlds * R);
     std::vector<int32_t> id((size_t)numWorlds * R);
     if (mrx_copy_to_host(shard, MRX_BUF_RAY_DISTANCE, t.data(), t.size() * sizeof(float)) != MRX_OK ||
-        mrx_copy_to_host(shard, MRX_BUF_RAY_ID, id.data(), id.size() * sizeof(int32_t)) != MRX_OK) {
-        std::fprintf(stderr, "%s\n", mrx_last_error());
-        return false;
+        mrx_copy_to_host(shard, MRX_BUF_RAY_ID, id.data(), id.size() * sizeof(int32_t)) != MRX_OK)
+        return libraryError();
+    std::string out;
+    char line[96];
+    for (size_t i = 0; i < t.size(); ++i) {
+        std::snprintf(line, sizeof line, "%zu %zu %.9g %d\n", firstWorld + i / R, i % R, (double)t[i], id[i]);
+        out += line;
     }
-    FILE *f = std::fopen((name + ".rays.txt").c_str(), "w");
-    bool ok = f != nullptr;
-    for (size_t i = 0; ok && i < t.size(); ++i)
-        ok = std::fprintf(f, "%zu %zu %.9g %d\n", firstWorld + i / R, i % R, (double)t[i], id[i]) > 0;
-    if (f && std::fclose(f) != 0)
-        ok = false;
-    if (!ok)
-        std::fprintf(stderr, "cannot write %s.rays.txt\n", name.c_str());
-    return ok;
+    return writeFile(name + ".rays.txt", out);
 }
 
 // A four-dimensional tensor of the shard as a NumPy file (format 1.0), NAME + suffix, in the tensor's own shape and
@@ -653,17 +595,13 @@ bool dumpNpy(const std::string &name, mrx_renderer *shard, int which = MRX_BUF_O
 {
     int64_t dims[4] = { 0, 0, 0, 0 };
     int nd = 0, dt = 0, dev = 0;
-    if (!mrx_buffer(shard, which, dims, &nd, &dt, &dev) || nd != 4) {
-        std::fprintf(stderr, "%s\n", mrx_last_error());
-        return false;
-    }
+    if (!mrx_buffer(shard, which, dims, &nd, &dt, &dev) || nd != 4)
+        return libraryError();
     const char *descr = dt == MRX_DTYPE_F32 ? "<f4" : dt == MRX_DTYPE_F16 ? "<f2" : dt == MRX_DTYPE_BF16 ? "<u2" : "|u1";
     const size_t elem = dt == MRX_DTYPE_F32 ? 4 : dt == MRX_DTYPE_U8 ? 1 : 2;
     std::vector<uint8_t> data((size_t)(dims[0] * dims[1] * dims[2] * dims[3]) * elem);
-    if (mrx_copy_to_host(shard, which, data.data(), data.size()) != MRX_OK) {
-        std::fprintf(stderr, "%s\n", mrx_last_error());
-        return false;
-    }
+    if (mrx_copy_to_host(shard, which, data.data(), data.size()) != MRX_OK)
+        return libraryError();
     char dict[160];
     std::snprintf(dict, sizeof dict, "{'descr': '%s', 'fortran_order': False, 'shape': (%lld, %lld, %lld, %lld), }", descr,
                   (long long)dims[0], (long long)dims[1], (long long)dims[2], (long long)dims[3]);
@@ -675,14 +613,7 @@ bool dumpNpy(const std::string &name, mrx_renderer *shard, int which = MRX_BUF_O
     out += (char)(header.size() & 0xFF);
     out += (char)(header.size() >> 8);
     out += header;
-    FILE *f = std::fopen((name + suffix).c_str(), "wb");
-    const bool ok = f && std::fwrite(out.data(), 1, out.size(), f) == out.size() &&
-                    std::fwrite(data.data(), 1, data.size(), f) == data.size();
-    if (f && std::fclose(f) != 0)
-        return false;
-    if (!ok)
-        std::fprintf(stderr, "cannot write %s%s\n", name.c_str(), suffix);
-    return ok;
+    return writeFile(name + suffix, out, data.data(), data.size());
 }
 
 }  // namespace

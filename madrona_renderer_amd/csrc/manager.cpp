@@ -21,18 +21,44 @@ static bool g_throwOnError = false;
 // conditions surface as exceptions instead of killing the interpreter.
 void setThrowOnError(bool v) { g_throwOnError = v; }
 
-[[noreturn]] static void fatal(const std::string &msg)
+[[noreturn]] static void fatal(const char *msg)
 {
     if (g_throwOnError)
         throw std::runtime_error(msg);
-    std::fprintf(stderr, "FATAL: %s\n", msg.c_str());
+    std::fprintf(stderr, "FATAL: %s\n", msg);
     std::fflush(stderr);
     std::abort();
 }
+[[noreturn]] static void fatal(const std::string &msg) { fatal(msg.c_str()); }
 }  // namespace detail
 
 using madrona::py::Tensor;
 using madrona::py::TensorElementType;
+
+namespace {
+// the status of a C-ABI call: anything but MRX_OK is fatal, with the library's text
+void check(int rc)
+{
+    if (rc != MRX_OK)
+        detail::fatal(mrx_last_error());
+}
+
+// ... of a setter whose values the caller may get wrong: MRX_E_INVALID is theirs (false, the text in mrx_last_error)
+bool accepted(int rc)
+{
+    if (rc == MRX_E_INVALID)
+        return false;
+    check(rc);
+    return true;
+}
+
+mrx_info_t info(mrx_renderer *r)
+{
+    mrx_info_t i {};
+    check(mrx_info_sized(r, &i, sizeof i));
+    return i;
+}
+}  // namespace
 
 struct Manager::Impl {
     mrx_renderer *r = nullptr;
@@ -145,13 +171,12 @@ Manager::Manager(const Config &cfg)
 
     if (cfg.raysPerWorld > 65536)
         detail::fatal("raysPerWorld " + std::to_string(cfg.raysPerWorld) + " is not in 0 ... 65536");
-    if (mrx_create(&c, &impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
+    check(mrx_create(&c, &impl_->r));
     // (the flag word is full: the sensor is attached to the renderer once it exists)
-    if (cfg.raysPerWorld && mrx_rays_create(impl_->r, cfg.raysPerWorld) != MRX_OK)
-        detail::fatal(mrx_last_error());
-    if (cfg.flow && mrx_flow_create(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
+    if (cfg.raysPerWorld)
+        check(mrx_rays_create(impl_->r, cfg.raysPerWorld));
+    if (cfg.flow)
+        check(mrx_flow_create(impl_->r));
     // the initial values of an int32 column, world-major as mrx_create lays the rows out (spare rows `spare`)
     const auto expand = [&](const int32_t *perInstance, int32_t spare) {
         std::vector<int32_t> rows;
@@ -165,20 +190,17 @@ Manager::Manager(const Config &cfg)
     };
     if (cfg.instanceMaterials) {
         const std::vector<int32_t> ids = expand(cfg.instanceMaterials, -1);
-        if (!ids.empty() &&
-            mrx_set_instance_materials(impl_->r, 0, (uint32_t)ids.size(), ids.data()) != MRX_OK)
-            detail::fatal(mrx_last_error());
+        if (!ids.empty())
+            check(mrx_set_instance_materials(impl_->r, 0, (uint32_t)ids.size(), ids.data()));
     }
     if (cfg.instanceLabels) {
         const std::vector<int32_t> labels = expand(cfg.instanceLabels, MRX_LABEL_OBJECT);
-        if (!labels.empty() &&
-            mrx_set_instance_labels(impl_->r, 0, (uint32_t)labels.size(), labels.data()) != MRX_OK)
-            detail::fatal(mrx_last_error());
+        if (!labels.empty())
+            check(mrx_set_instance_labels(impl_->r, 0, (uint32_t)labels.size(), labels.data()));
     }
     // ... then the first frame again: what a caller reads before its first step() already shows them
     if (cfg.instanceMaterials || cfg.instanceLabels)
-        if (mrx_render(impl_->r) != MRX_OK)
-            detail::fatal(mrx_last_error());
+        check(mrx_render(impl_->r));
 
     // vestigial in the reference too (mgr.cpp:516-522)
     const char *num_agents_str = std::getenv("HIDESEEK_NUM_AGENTS");
@@ -188,146 +210,63 @@ Manager::Manager(const Config &cfg)
 
 Manager::~Manager() {}
 
-void Manager::step()
-{
-    if (mrx_step(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
-
-void Manager::render()
-{
-    if (mrx_render(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
-
-void Manager::sync()
-{
-    if (mrx_sync(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
+void Manager::step() { check(mrx_step(impl_->r)); }
+void Manager::render() { check(mrx_render(impl_->r)); }
+void Manager::sync() { check(mrx_sync(impl_->r)); }
 
 Tensor Manager::rgbTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_RGB, shard); }
 Tensor Manager::depthTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_DEPTH, shard); }
 Tensor Manager::segmaskTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_SEGMASK, shard); }
 Tensor Manager::visibilityTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_VISIBILITY, shard); }
+Tensor Manager::normalTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_NORMAL, shard); }
 
 Tensor Manager::instanceObjectTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_OBJECT, shard); }
 Tensor Manager::instanceScaleTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_SCALE, shard); }
 Tensor Manager::instanceColorTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_COLOR, shard); }
 Tensor Manager::instanceMaterialTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_MATERIAL, shard); }
 Tensor Manager::instanceLabelTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_LABEL, shard); }
-
-Tensor Manager::normalTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_NORMAL, shard); }
-
-Tensor Manager::instancePositionTensor(uint32_t shard) const
-{
-    return impl_->wrap(MRX_BUF_INSTANCE_POSITION, shard);
-}
-Tensor Manager::instanceRotationTensor(uint32_t shard) const
-{
-    return impl_->wrap(MRX_BUF_INSTANCE_ROTATION, shard);
-}
-Tensor Manager::cameraPositionTensor(uint32_t shard) const
-{
-    return impl_->wrap(MRX_BUF_CAMERA_POSITION, shard);
-}
-Tensor Manager::cameraRotationTensor(uint32_t shard) const
-{
-    return impl_->wrap(MRX_BUF_CAMERA_ROTATION, shard);
-}
+Tensor Manager::instancePositionTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_POSITION, shard); }
+Tensor Manager::instanceRotationTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_INSTANCE_ROTATION, shard); }
+Tensor Manager::cameraPositionTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_CAMERA_POSITION, shard); }
+Tensor Manager::cameraRotationTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_CAMERA_ROTATION, shard); }
 
 uint64_t Manager::rgbCudaPtr(uint32_t shard) const { return (uint64_t)rgbTensor(shard).devicePtr(); }
 uint64_t Manager::depthCudaPtr(uint32_t shard) const { return (uint64_t)depthTensor(shard).devicePtr(); }
 uint64_t Manager::segmaskCudaPtr(uint32_t shard) const { return (uint64_t)segmaskTensor(shard).devicePtr(); }
 
+// the post-render stages: the option the renderer was created with, the stage's tensors, the stage alone
 uint32_t Manager::supersample() const { return (uint32_t)mrx_supersample(impl_->r); }
-
 Tensor Manager::sampleTensor(int which, uint32_t shard) const { return impl_->wrap(which, shard, true); }
-
-void Manager::resolve()
-{
-    if (mrx_resolve(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
+void Manager::resolve() { check(mrx_resolve(impl_->r)); }
 
 uint32_t Manager::positions() const { return (uint32_t)mrx_positions(impl_->r); }
-
 Tensor Manager::positionTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_POSITION, shard); }
-
-void Manager::unproject()
-{
-    if (mrx_unproject(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
+void Manager::unproject() { check(mrx_unproject(impl_->r)); }
 
 uint32_t Manager::boxLabels() const { return (uint32_t)mrx_box_labels(impl_->r); }
-
 Tensor Manager::boxTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_BOXES, shard); }
-
-void Manager::boxes()
-{
-    if (mrx_boxes(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
+void Manager::boxes() { check(mrx_boxes(impl_->r)); }
 
 uint32_t Manager::observations() const { return (uint32_t)mrx_observations(impl_->r); }
-
 Tensor Manager::observationTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_OBSERVATION, shard); }
-
 Tensor Manager::observationResetTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_OBSERVATION_RESET, shard); }
-
-void Manager::observe()
-{
-    if (mrx_observe(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
-
-void Manager::setObservationDepthRange(float lo, float hi)
-{
-    if (mrx_set_observation_depth_range(impl_->r, lo, hi) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
-
-void Manager::observationDepthRange(float *lo, float *hi) const
-{
-    if (mrx_observation_depth_range(impl_->r, lo, hi) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
+void Manager::observe() { check(mrx_observe(impl_->r)); }
+void Manager::setObservationDepthRange(float lo, float hi) { check(mrx_set_observation_depth_range(impl_->r, lo, hi)); }
+void Manager::observationDepthRange(float *lo, float *hi) const { check(mrx_observation_depth_range(impl_->r, lo, hi)); }
 
 uint32_t Manager::rays() const { return (uint32_t)mrx_rays(impl_->r); }
-
 Tensor Manager::rayTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_RAYS, shard); }
 Tensor Manager::rayFrameTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_RAY_FRAME, shard); }
 Tensor Manager::rayDistanceTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_RAY_DISTANCE, shard); }
 Tensor Manager::rayIdTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_RAY_ID, shard); }
-
-void Manager::trace()
-{
-    if (mrx_trace(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
+void Manager::trace() { check(mrx_trace(impl_->r)); }
 
 bool Manager::flows() const { return mrx_flow_enabled(impl_->r) == 1; }
-
 Tensor Manager::flowTensor(uint32_t shard) const { return impl_->wrap(MRX_BUF_FLOW, shard); }
+void Manager::flow() { check(mrx_flow(impl_->r)); }
+void Manager::flowSnapshot() { check(mrx_flow_snapshot(impl_->r)); }
 
-void Manager::flow()
-{
-    if (mrx_flow(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
-
-void Manager::flowSnapshot()
-{
-    if (mrx_flow_snapshot(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
-
-void Manager::refreshObjects()
-{
-    if (mrx_refresh_objects(impl_->r) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
+void Manager::refreshObjects() { check(mrx_refresh_objects(impl_->r)); }
 
 uint32_t Manager::numShards() const { return (uint32_t)mrx_num_shards(impl_->r); }
 
@@ -342,142 +281,77 @@ uint32_t Manager::shardFirstWorld(uint32_t shard) const
 float Manager::timeRenders(int steps)
 {
     float ms = 0.f;
-    if (mrx_time_renders(impl_->r, steps, &ms) != MRX_OK)
-        detail::fatal(mrx_last_error());
+    check(mrx_time_renders(impl_->r, steps, &ms));
     return ms;
 }
 
 double Manager::timeStepsHost(int steps)
 {
     double us = 0.0;
-    if (mrx_time_steps_host(impl_->r, steps, &us) != MRX_OK)
-        detail::fatal(mrx_last_error());
+    check(mrx_time_steps_host(impl_->r, steps, &us));
     return us;
 }
 
-void Manager::mark(int which)
-{
-    if (mrx_mark(impl_->r, which) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
+void Manager::mark(int which) { check(mrx_mark(impl_->r, which)); }
 
 float Manager::elapsedMs()
 {
     float ms = 0.f;
-    if (mrx_elapsed_ms(impl_->r, &ms) != MRX_OK)
-        detail::fatal(mrx_last_error());
+    check(mrx_elapsed_ms(impl_->r, &ms));
     return ms;
 }
 
-uint64_t Manager::bytesPerStep() const
-{
-    mrx_info_t info {};
-    if (mrx_info_sized(impl_->r, &info, sizeof info) != MRX_OK)
-        detail::fatal(mrx_last_error());
-    return info.bytes_per_step;
-}
+uint32_t Manager::numViews() const { return info(impl_->r).num_views; }
+uint32_t Manager::numWorlds() const { return info(impl_->r).num_worlds; }
+uint32_t Manager::numInstanceRows() const { return info(impl_->r).num_instances; }
+uint64_t Manager::bytesPerStep() const { return info(impl_->r).bytes_per_step; }
+const char *Manager::renderPath() const { return info(impl_->r).render_path == 1 ? "bvh" : "raster"; }
 
 void *Manager::nativeHandle() const { return impl_->r; }
 
 bool Manager::setViewProjection(uint32_t first, uint32_t count, const CameraProjection *proj)
 {
-    const int rc = mrx_set_view_projection(impl_->r, first, count, reinterpret_cast<const mrx_projection *>(proj));
-    if (rc == MRX_E_INVALID)
-        return false;
-    if (rc != MRX_OK)
-        detail::fatal(mrx_last_error());
-    return true;
+    return accepted(mrx_set_view_projection(impl_->r, first, count, reinterpret_cast<const mrx_projection *>(proj)));
 }
 
 void Manager::viewProjection(uint32_t first, uint32_t count, CameraProjection *out) const
 {
-    if (mrx_view_projection(impl_->r, first, count, reinterpret_cast<mrx_projection *>(out)) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
-
-uint32_t Manager::numViews() const
-{
-    mrx_info_t inf {};
-    if (mrx_info(impl_->r, &inf) != MRX_OK)
-        detail::fatal(mrx_last_error());
-    return inf.num_views;
+    check(mrx_view_projection(impl_->r, first, count, reinterpret_cast<mrx_projection *>(out)));
 }
 
 bool Manager::setWorldLights(uint32_t first, uint32_t count, const Light *lights)
 {
-    const int rc = mrx_set_world_light(impl_->r, first, count, reinterpret_cast<const mrx_light *>(lights));
-    if (rc == MRX_E_INVALID)
-        return false;
-    if (rc != MRX_OK)
-        detail::fatal(mrx_last_error());
-    return true;
+    return accepted(mrx_set_world_light(impl_->r, first, count, reinterpret_cast<const mrx_light *>(lights)));
 }
 
 void Manager::worldLights(uint32_t first, uint32_t count, Light *out) const
 {
-    if (mrx_world_light(impl_->r, first, count, reinterpret_cast<mrx_light *>(out)) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
-
-uint32_t Manager::numWorlds() const
-{
-    mrx_info_t inf {};
-    if (mrx_info(impl_->r, &inf) != MRX_OK)
-        detail::fatal(mrx_last_error());
-    return inf.num_worlds;
+    check(mrx_world_light(impl_->r, first, count, reinterpret_cast<mrx_light *>(out)));
 }
 
 bool Manager::setInstanceMaterials(uint32_t first, uint32_t count, const int32_t *materials)
 {
-    const int rc = mrx_set_instance_materials(impl_->r, first, count, materials);
-    if (rc == MRX_E_INVALID)
-        return false;
-    if (rc != MRX_OK)
-        detail::fatal(mrx_last_error());
-    return true;
+    return accepted(mrx_set_instance_materials(impl_->r, first, count, materials));
 }
 
 void Manager::instanceMaterials(uint32_t first, uint32_t count, int32_t *out) const
 {
-    if (mrx_instance_materials(impl_->r, first, count, out) != MRX_OK)
-        detail::fatal(mrx_last_error());
+    check(mrx_instance_materials(impl_->r, first, count, out));
 }
 
 bool Manager::setInstanceLabels(uint32_t first, uint32_t count, const int32_t *labels)
 {
-    const int rc = mrx_set_instance_labels(impl_->r, first, count, labels);
-    if (rc == MRX_E_INVALID)
-        return false;
-    if (rc != MRX_OK)
-        detail::fatal(mrx_last_error());
-    return true;
+    return accepted(mrx_set_instance_labels(impl_->r, first, count, labels));
 }
 
 void Manager::instanceLabels(uint32_t first, uint32_t count, int32_t *out) const
 {
-    if (mrx_instance_labels(impl_->r, first, count, out) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
-
-uint32_t Manager::numInstanceRows() const
-{
-    mrx_info_t inf {};
-    if (mrx_info(impl_->r, &inf) != MRX_OK)
-        detail::fatal(mrx_last_error());
-    return inf.num_instances;
+    check(mrx_instance_labels(impl_->r, first, count, out));
 }
 
 int Manager::placement(float *candUs, int capacity, float *keptUs) const
 {
     return mrx_placement(impl_->r, candUs, capacity, keptUs);
-}
-
-const char *Manager::renderPath() const
-{
-    mrx_info_t info {};
-    if (mrx_info_sized(impl_->r, &info, sizeof info) != MRX_OK)
-        detail::fatal(mrx_last_error());
-    return info.render_path == 1 ? "bvh" : "raster";
 }
 
 const char *Manager::rasterEntry() const
@@ -493,24 +367,20 @@ Manager::KernelFormInfo Manager::kernelForm() const
 {
     static const char *const names[] = {"Uniform", "PV", "PVL", "C", "PVLC", "M", "PVLM", "N", "NPV", "L", "LN", "PVM"};
     mrx_kernel_form_t f {};
-    if (mrx_kernel_form(impl_->r, &f) != MRX_OK)
-        detail::fatal(mrx_last_error());
+    check(mrx_kernel_form(impl_->r, &f));
     if (f.form < 0 || f.form >= (int)(sizeof names / sizeof names[0]))
         detail::fatal("mrx_kernel_form: unknown form");
     return KernelFormInfo { names[f.form], f.slots };
 }
 
-void Manager::setStream(void *hipStream)
-{
-    if (mrx_set_stream(impl_->r, hipStream) != MRX_OK)
-        detail::fatal(mrx_last_error());
-}
+void Manager::setStream(void *hipStream) { check(mrx_set_stream(impl_->r, hipStream)); }
 
 void Manager::setShardStream(uint32_t shard, void *hipStream)
 {
     mrx_renderer *sh = mrx_shard(impl_->r, (int)shard);
-    if (!sh || mrx_set_stream(sh, hipStream) != MRX_OK)
+    if (!sh)
         detail::fatal(mrx_last_error());
+    check(mrx_set_stream(sh, hipStream));
 }
 
 }  // namespace madRender

@@ -16,6 +16,7 @@
 
 #include "../../include/madrona_mi355/manager.hpp"
 #include "../../include/mrx.h"
+#include "obs_names.hpp"
 
 namespace py = pybind11;
 
@@ -42,7 +43,6 @@ void checkProjection(const Manager::CameraProjection &q)
     if (!(std::isfinite(q.znear) && q.znear >= 0.0f))
         throw py::value_error("znear must be finite and > 0 (None: the mode's default)");
 }
-// a znear the caller gave (not None): finite and > 0
 // the light check of the library (mrx_light_constants): ValueError
 void checkLight(const Manager::Light &l)
 {
@@ -51,6 +51,7 @@ void checkLight(const Manager::Light &l)
     if (mrx_light_constants(in, c) != MRX_OK)
         throw py::value_error(mrx_last_error());
 }
+// a znear the caller gave (not None): finite and > 0
 float znearOf(float z)
 {
     if (!(std::isfinite(z) && z > 0.0f))
@@ -145,8 +146,9 @@ py::object makeCapsule(const PyTensor &self)
     return py::reinterpret_steal<py::object>(cap);
 }
 
-template <typename T, int N>
-using FArr = py::array_t<T, py::array::c_style | py::array::forcecast>;
+// a NumPy argument as a dense array of T, converted where it is not one
+template <typename T>
+using CArray = py::array_t<T, py::array::c_style | py::array::forcecast>;
 
 PyTensor wrapTensor(py::object self, Tensor t) { return PyTensor { t, std::move(self) }; }
 
@@ -174,9 +176,6 @@ struct ObsArg {
     bool hasRange = false;
     float lo = 0.0f, hi = 0.0f;
 };
-
-const char *const kObsChannels[] = { nullptr, "rgb", "rgbd", "d", "y", "yd" };
-const char *const kObsDtypes[] = { "float32", "float16", "bfloat16", "uint8" };
 
 // (lo, hi) with 0 <= lo < hi, both finite, as float32
 void parseObsRange(const py::object &range, float &lo, float &hi)
@@ -237,16 +236,10 @@ ObsArg parseObservations(const py::object &arg, Manager::RenderOutputs outputs)
     } else {
         throw py::value_error("observations must be None, a channels string or a dict (channels, dtype, stack, depth_range)");
     }
-    uint32_t layout = 0, dt = 4;
-    for (uint32_t i = 1; i <= 5; ++i)
-        if (channels == kObsChannels[i])
-            layout = i;
-    for (uint32_t i = 0; i < 4; ++i)
-        if (dtype == kObsDtypes[i])
-            dt = i;
+    const uint32_t layout = obsLayoutOf(channels), dt = obsDtypeOf(dtype);
     if (!layout)
         throw py::value_error("observations: unknown channels " + channels + " (rgb, rgbd, d, y, yd)");
-    if (dt == 4)
+    if (dt == kNumObsDtypes)
         throw py::value_error("observations: unknown dtype " + dtype + " (float32, float16, bfloat16, uint8)");
     if (stack < 1 || stack > 8)
         throw py::value_error("observations: stack must be an int in 1 ... 8");
@@ -265,6 +258,160 @@ ObsArg parseObservations(const py::object &arg, Manager::RenderOutputs outputs)
     return out;
 }
 
+// a count the constructor takes as None (0) or an int in 1 ... hi; with `orZero`, 0 and False stand for None too.
+// Anything else, True included, is refused with `msg`.
+uint32_t countOrNone(const py::object &arg, long long hi, bool orZero, const char *msg)
+{
+    if (arg.is_none() || (orZero && py::isinstance<py::bool_>(arg) && !arg.cast<bool>()))
+        return 0;
+    if (py::isinstance<py::bool_>(arg) || !py::isinstance<py::int_>(arg))
+        throw py::value_error(msg);
+    const long long n = arg.cast<long long>();   // (an int beyond long long: pybind's cast error)
+    if (n < (orZero ? 0 : 1) || n > hi)
+        throw py::value_error(msg);
+    return (uint32_t)n;
+}
+
+// a per-instance column the constructor takes as None (no column), a bool (True: a column of the default value) or an
+// array of `rows` rows -- of `cols` entries each, one-dimensional where cols is 0; anything else is refused with `msg`.
+// Sets the Config's switch and pointer; the array returned backs the pointer.
+template <typename T>
+CArray<T> parseColumn(const py::object &arg, size_t rows, py::ssize_t cols, const char *msg, bool &column, const T *&data)
+{
+    CArray<T> a;
+    if (py::isinstance<py::bool_>(arg)) {
+        column = arg.cast<bool>();
+    } else if (!arg.is_none()) {
+        a = CArray<T>::ensure(arg);
+        if (!a || a.ndim() != (cols ? 2 : 1) || (size_t)a.shape(0) != rows || (cols && a.shape(1) != cols))
+            throw py::value_error(msg);
+        data = a.data();
+        column = true;
+    }
+    return a;
+}
+
+// a scalar or a sequence of floats, for set_camera_projection and set_world_light, which broadcast a scalar
+std::vector<float> asVec(const py::object &o, bool &scalar)
+{
+    scalar = !py::isinstance<py::sequence>(o) && !py::hasattr(o, "__len__");
+    if (scalar)
+        return { o.cast<float>() };
+    return CArray<float>(o).cast<std::vector<float>>();
+}
+
+// set_instance_labels / set_instance_materials and instance_labels / instance_materials: an int32 column from and to
+// host memory through its Manager accessor.  `none` is the column's "no value" (what a call of no rows points at);
+// `array` and `values` are the nouns of the two refusals.
+void setRows(Manager &self, bool (Manager::*set)(uint32_t, uint32_t, const int32_t *), int32_t none, const std::string &array,
+             const std::string &values, const CArray<int32_t> &ids, int64_t first_row)
+{
+    if (ids.ndim() != 1)
+        throw py::value_error(array + " must be a one-dimensional int32 array");
+    if (first_row < 0 || first_row + (int64_t)ids.shape(0) > (int64_t)self.numInstanceRows())
+        throw py::value_error("more " + values + " than instance rows from first_row on");
+    if (!(self.*set)((uint32_t)first_row, (uint32_t)ids.shape(0), ids.shape(0) ? ids.data() : &none))
+        throw py::value_error(mrx_last_error());
+}
+
+py::array_t<int32_t> getRows(Manager &self, void (Manager::*get)(uint32_t, uint32_t, int32_t *) const, int32_t none)
+{
+    const uint32_t n = self.numInstanceRows();
+    py::array_t<int32_t> out(n);
+    (self.*get)(0, n, n ? out.mutable_data() : &none);
+    return out;
+}
+
+// ---- the constructor, in steps: parse the options, check the scene, fill the Config, construct ----------------------
+struct Options {
+    ObsArg obs;
+    uint32_t raysPerWorld = 0, boxLabels = 0, positionFrame = 0;
+};
+
+// step 1: the keyword options that are no plain value, and the combinations that exclude each other
+Options parseOptions(Manager::RenderOutputs outputs, int supersample, const py::object &positions, const py::object &boxes,
+                     const py::object &observations, const py::object &rays, bool flow)
+{
+    Options o;
+    o.obs = parseObservations(observations, outputs);
+    // rays: None (no sensor) or R, an int in 1 ... 65536
+    o.raysPerWorld = countOrNone(rays, 65536, false, "rays must be None or an int in 1 ... 65536 (the number of rays per world)");
+    // boxes: None / 0 / False (no output) or K, an int in 1 ... 1024
+    o.boxLabels = countOrNone(boxes, 1024, true, "boxes must be None or an int in 1 ... 1024 (the number of labels)");
+    if (supersample < 1 || supersample > 4)
+        throw py::value_error("supersample must be 1, 2, 3 or 4");
+    if (flow && outputs == Manager::RenderOutputs::RGB)
+        throw py::value_error("flow needs depth: render_outputs RGB renders none");
+    if (flow && o.boxLabels)
+        throw py::value_error("flow and boxes exclude each other: under flow the ids tensor holds visibility "
+                              "ids, the box stage needs a segmask");
+    // positions: False / None (no output), True or "world", or "view"
+    if (py::isinstance<py::bool_>(positions))
+        o.positionFrame = positions.cast<bool>() ? 1u : 0u;
+    else if (py::isinstance<py::str>(positions) && positions.cast<std::string>() == "world")
+        o.positionFrame = 1;
+    else if (py::isinstance<py::str>(positions) && positions.cast<std::string>() == "view")
+        o.positionFrame = 2;
+    else if (!positions.is_none())
+        throw py::value_error("positions must be False, True, \"world\" or \"view\"");
+    if (o.positionFrame && outputs == Manager::RenderOutputs::RGB)
+        throw py::value_error("positions need depth: render_outputs RGB renders none");
+    return o;
+}
+
+// step 2: the shapes of the scene's arrays -- the C ABI carries no lengths for the per-mesh arrays and reads uvs
+// row-for-row with vertices -- and the cameras against the mode
+void checkScene(size_t num_worlds, size_t worlds, Manager::RenderMode mode, const std::vector<PyCamera> &cameras,
+                const CArray<float> &vertices, const CArray<float> &uvs, const CArray<uint32_t> &vertexOffsets,
+                const CArray<uint32_t> &indexOffsets, const CArray<int32_t> &materials)
+{
+    if (vertices.size() && (vertices.ndim() != 2 || vertices.shape(1) != 3))
+        throw py::value_error("mesh_vertices must have shape [N, 3]");
+    if (uvs.size() && (uvs.ndim() != 2 || uvs.shape(1) != 2))
+        throw py::value_error("mesh_uvs must have shape [N, 2]");
+    if (num_worlds != worlds)
+        throw py::value_error("num_worlds does not match len(worlds)");
+    if (indexOffsets.size() != vertexOffsets.size() || materials.size() != vertexOffsets.size())
+        throw py::value_error("mesh_vertex_offsets, mesh_indices_offsets and "
+                              "mesh_materials must have one entry per mesh");
+    if ((uvs.size() ? uvs.shape(0) : 0) != (vertices.size() ? vertices.shape(0) : 0))
+        throw py::value_error("mesh_uvs must have one row per row of mesh_vertices");
+    if (mode == Manager::RenderMode::Raytracer)
+        for (const PyCamera &c : cameras)
+            if (!(c.proj.znear < 1000.0f))
+                throw py::value_error("znear must be below the Raytracer far plane (1000)");
+}
+
+// world_lights: [(direction, ambient, diffuse)] per world
+std::vector<Manager::Light> parseLights(const py::object &world_lights, int num_worlds)
+{
+    std::vector<Manager::Light> lights;
+    const py::sequence seq = world_lights.cast<py::sequence>();
+    if ((int64_t)py::len(seq) != num_worlds)
+        throw py::value_error("world_lights needs one (direction, ambient, diffuse) per world");
+    for (const py::handle &h : seq) {
+        const py::tuple t = py::tuple(py::reinterpret_borrow<py::object>(h));
+        if (t.size() != 3)
+            throw py::value_error("world_lights entries are (direction, ambient, diffuse)");
+        const std::array<float, 3> d = t[0].cast<std::array<float, 3>>();
+        const Manager::Light l = { { d[0], d[1], d[2] }, t[1].cast<float>(), t[2].cast<float>() };
+        checkLight(l);
+        lights.push_back(l);
+    }
+    return lights;
+}
+
+// what a Config points at beside the caller's own arrays: alive until the Manager is constructed
+struct ConfigStore {
+    std::vector<ImportedCamera> cameras;
+    std::vector<Manager::CameraProjection> projections;
+    std::vector<const char *> assetPaths, texturePaths;
+    std::vector<int32_t> matAssignments;
+    std::vector<Manager::Light> lights;
+    CArray<uint8_t> colors;
+    CArray<int32_t> materials, labels;
+};
+
 }  // namespace
 
 PYBIND11_MODULE(madrona_renderer, m)
@@ -272,59 +419,35 @@ PYBIND11_MODULE(madrona_renderer, m)
     m.doc() = "MI355X-native batch renderer with the madrona_renderer API";
     madRender::detail::setThrowOnError(true);
     // the C ABI's names of the colour override column (include/mrx.h), as the library was built with them
-    m.attr("MRX_FLAG_INSTANCE_COLORS") = (uint32_t)MRX_FLAG_INSTANCE_COLORS;
-    m.attr("MRX_BUF_INSTANCE_COLOR") = (int)MRX_BUF_INSTANCE_COLOR;
-    m.attr("MRX_NUM_BUFFERS") = (int)MRX_NUM_BUFFERS;
+#define MRX_ATTR(name) m.attr(#name) = py::int_((long long)(name))
+    MRX_ATTR(MRX_FLAG_INSTANCE_COLORS); MRX_ATTR(MRX_BUF_INSTANCE_COLOR); MRX_ATTR(MRX_NUM_BUFFERS);
     // ... and of the material override column
-    m.attr("MRX_FLAG_INSTANCE_MATERIALS") = (uint32_t)MRX_FLAG_INSTANCE_MATERIALS;
-    m.attr("MRX_BUF_INSTANCE_MATERIAL") = (int)MRX_BUF_INSTANCE_MATERIAL;
-    m.attr("MRX_NUM_BUFFERS_EXT") = (int)MRX_NUM_BUFFERS_EXT;
+    MRX_ATTR(MRX_FLAG_INSTANCE_MATERIALS); MRX_ATTR(MRX_BUF_INSTANCE_MATERIAL); MRX_ATTR(MRX_NUM_BUFFERS_EXT);
     // ... and of the surface-normal output
-    m.attr("MRX_FLAG_NORMALS") = (uint32_t)MRX_FLAG_NORMALS;
-    m.attr("MRX_BUF_NORMAL") = (int)MRX_BUF_NORMAL;
-    m.attr("MRX_NUM_BUFFERS_EXT2") = (int)MRX_NUM_BUFFERS_EXT2;
+    MRX_ATTR(MRX_FLAG_NORMALS); MRX_ATTR(MRX_BUF_NORMAL); MRX_ATTR(MRX_NUM_BUFFERS_EXT2);
     // ... and of the label column
-    m.attr("MRX_FLAG_INSTANCE_LABELS") = (uint32_t)MRX_FLAG_INSTANCE_LABELS;
-    m.attr("MRX_BUF_INSTANCE_LABEL") = (int)MRX_BUF_INSTANCE_LABEL;
-    m.attr("MRX_NUM_BUFFERS_EXT3") = (int)MRX_NUM_BUFFERS_EXT3;
-    m.attr("MRX_LABEL_OBJECT") = (int32_t)MRX_LABEL_OBJECT;
+    MRX_ATTR(MRX_FLAG_INSTANCE_LABELS); MRX_ATTR(MRX_BUF_INSTANCE_LABEL); MRX_ATTR(MRX_NUM_BUFFERS_EXT3);
+    MRX_ATTR(MRX_LABEL_OBJECT);
     // ... and of the supersampling factor
-    m.attr("MRX_FLAG_SUPERSAMPLE_SHIFT") = (uint32_t)MRX_FLAG_SUPERSAMPLE_SHIFT;
-    m.attr("MRX_FLAG_SUPERSAMPLE_MASK") = (uint32_t)MRX_FLAG_SUPERSAMPLE_MASK;
+    MRX_ATTR(MRX_FLAG_SUPERSAMPLE_SHIFT); MRX_ATTR(MRX_FLAG_SUPERSAMPLE_MASK);
     // ... and of the position output
-    m.attr("MRX_FLAG_POSITIONS") = (uint32_t)MRX_FLAG_POSITIONS;
-    m.attr("MRX_FLAG_POSITIONS_VIEW") = (uint32_t)MRX_FLAG_POSITIONS_VIEW;
-    m.attr("MRX_BUF_POSITION") = (int)MRX_BUF_POSITION;
-    m.attr("MRX_NUM_BUFFERS_EXT4") = (int)MRX_NUM_BUFFERS_EXT4;
+    MRX_ATTR(MRX_FLAG_POSITIONS); MRX_ATTR(MRX_FLAG_POSITIONS_VIEW); MRX_ATTR(MRX_BUF_POSITION); MRX_ATTR(MRX_NUM_BUFFERS_EXT4);
     // ... and of the box labels
-    m.attr("MRX_FLAG_BOX_LABELS_SHIFT") = (uint32_t)MRX_FLAG_BOX_LABELS_SHIFT;
-    m.attr("MRX_FLAG_BOX_LABELS_MASK") = (uint32_t)MRX_FLAG_BOX_LABELS_MASK;
-    m.attr("MRX_BUF_BOXES") = (int)MRX_BUF_BOXES;
-    m.attr("MRX_NUM_BUFFERS_EXT5") = (int)MRX_NUM_BUFFERS_EXT5;
+    MRX_ATTR(MRX_FLAG_BOX_LABELS_SHIFT); MRX_ATTR(MRX_FLAG_BOX_LABELS_MASK); MRX_ATTR(MRX_BUF_BOXES); MRX_ATTR(MRX_NUM_BUFFERS_EXT5);
     // ... and of the packed observation output
-    m.attr("MRX_FLAG_OBS_SHIFT") = (uint32_t)MRX_FLAG_OBS_SHIFT;
-    m.attr("MRX_FLAG_OBS_MASK") = (uint32_t)MRX_FLAG_OBS_MASK;
-    m.attr("MRX_FLAG_OBS_LAYOUT_MASK") = (uint32_t)MRX_FLAG_OBS_LAYOUT_MASK;
-    m.attr("MRX_FLAG_OBS_DTYPE_MASK") = (uint32_t)MRX_FLAG_OBS_DTYPE_MASK;
-    m.attr("MRX_FLAG_OBS_STACK_MASK") = (uint32_t)MRX_FLAG_OBS_STACK_MASK;
+    MRX_ATTR(MRX_FLAG_OBS_SHIFT); MRX_ATTR(MRX_FLAG_OBS_MASK); MRX_ATTR(MRX_FLAG_OBS_LAYOUT_MASK);
+    MRX_ATTR(MRX_FLAG_OBS_DTYPE_MASK); MRX_ATTR(MRX_FLAG_OBS_STACK_MASK);
     m.def("MRX_FLAG_OBSERVATIONS", [](uint32_t layout, uint32_t dtype, uint32_t stack) {
         return (uint32_t)MRX_FLAG_OBSERVATIONS(layout, dtype, stack);
     });
-    m.attr("MRX_BUF_OBSERVATION") = (int)MRX_BUF_OBSERVATION;
-    m.attr("MRX_BUF_OBSERVATION_RESET") = (int)MRX_BUF_OBSERVATION_RESET;
-    m.attr("MRX_NUM_BUFFERS_EXT6") = (int)MRX_NUM_BUFFERS_EXT6;
+    MRX_ATTR(MRX_BUF_OBSERVATION); MRX_ATTR(MRX_BUF_OBSERVATION_RESET); MRX_ATTR(MRX_NUM_BUFFERS_EXT6);
     // ... and of the ray-cast sensor
-    m.attr("MRX_BUF_RAYS") = (int)MRX_BUF_RAYS;
-    m.attr("MRX_BUF_RAY_FRAME") = (int)MRX_BUF_RAY_FRAME;
-    m.attr("MRX_BUF_RAY_DISTANCE") = (int)MRX_BUF_RAY_DISTANCE;
-    m.attr("MRX_BUF_RAY_ID") = (int)MRX_BUF_RAY_ID;
-    m.attr("MRX_NUM_BUFFERS_EXT7") = (int)MRX_NUM_BUFFERS_EXT7;
+    MRX_ATTR(MRX_BUF_RAYS); MRX_ATTR(MRX_BUF_RAY_FRAME); MRX_ATTR(MRX_BUF_RAY_DISTANCE); MRX_ATTR(MRX_BUF_RAY_ID);
+    MRX_ATTR(MRX_NUM_BUFFERS_EXT7);
     // ... and of the optical-flow output
-    m.attr("MRX_BUF_FLOW") = (int)MRX_BUF_FLOW;
-    m.attr("MRX_NUM_BUFFERS_EXT8") = (int)MRX_NUM_BUFFERS_EXT8;
-    m.attr("MRX_DTYPE_F16") = (int)MRX_DTYPE_F16;
-    m.attr("MRX_DTYPE_BF16") = (int)MRX_DTYPE_BF16;
-    m.attr("MRX_CONFIG_V4_LIGHT_SIZE") = MRX_CONFIG_V4_LIGHT_SIZE;
+    MRX_ATTR(MRX_BUF_FLOW); MRX_ATTR(MRX_NUM_BUFFERS_EXT8);
+    MRX_ATTR(MRX_DTYPE_F16); MRX_ATTR(MRX_DTYPE_BF16); MRX_ATTR(MRX_CONFIG_V4_LIGHT_SIZE);
+#undef MRX_ATTR
     m.attr("MRX_CONFIG_SIZE") = (uint32_t)sizeof(mrx_config);
 
     py::enum_<Manager::RenderMode>(m, "RenderMode")
@@ -426,16 +549,13 @@ PYBIND11_MODULE(madrona_renderer, m)
                                })
         .def_property_readonly("gpu_id", [](const PyTensor &self) { return self.t.gpuID(); });
 
-    py::class_<Manager>(m, "MadronaRenderer")
+    py::class_<Manager> renderer(m, "MadronaRenderer");
+    renderer
         .def(py::init([](int gpu_id, int num_worlds, Manager::RenderMode render_mode,
                          int batch_render_view_width, int batch_render_view_height,
-                         const std::vector<ImportedAsset> &asset_paths,
-                         py::array_t<float, py::array::c_style | py::array::forcecast> mesh_vertices,
-                         py::array_t<float, py::array::c_style | py::array::forcecast> mesh_uvs,
-                         py::array_t<uint32_t, py::array::c_style | py::array::forcecast> mesh_indices,
-                         py::array_t<uint32_t, py::array::c_style | py::array::forcecast> mesh_vertex_offsets,
-                         py::array_t<uint32_t, py::array::c_style | py::array::forcecast> mesh_indices_offsets,
-                         py::array_t<int32_t, py::array::c_style | py::array::forcecast> mesh_materials,
+                         const std::vector<ImportedAsset> &asset_paths, CArray<float> mesh_vertices,
+                         CArray<float> mesh_uvs, CArray<uint32_t> mesh_indices, CArray<uint32_t> mesh_vertex_offsets,
+                         CArray<uint32_t> mesh_indices_offsets, CArray<int32_t> mesh_materials,
                          const std::vector<AdditionalMaterial> &mats,
                          const std::vector<std::string> &texture_paths,
                          const std::vector<ImportedInstance> &instances,
@@ -446,85 +566,24 @@ PYBIND11_MODULE(madrona_renderer, m)
                          py::object instance_materials, bool normals, py::object instance_labels, int supersample,
                          py::object positions, py::object boxes, py::object observations, py::object rays,
                          bool flow) {
-                 const ObsArg obsArg = parseObservations(observations, render_outputs);
-                 // rays: None (no sensor) or R, an int in 1 ... 65536
-                 uint32_t raysPerWorld = 0;
-                 if (!rays.is_none()) {
-                     if (py::isinstance<py::bool_>(rays) || !py::isinstance<py::int_>(rays))
-                         throw py::value_error("rays must be None or an int in 1 ... 65536 (the number of rays per world)");
-                     const long long n = rays.cast<long long>();
-                     if (n < 1 || n > 65536)
-                         throw py::value_error("rays must be None or an int in 1 ... 65536 (the number of rays per world)");
-                     raysPerWorld = (uint32_t)n;
-                 }
-                 // boxes: None / 0 / False (no output) or K, an int in 1 ... 1024
-                 uint32_t boxLabels = 0;
-                 if (py::isinstance<py::bool_>(boxes)) {
-                     if (boxes.cast<bool>())
-                         throw py::value_error("boxes must be None or an int in 1 ... 1024 (the number of labels)");
-                 } else if (py::isinstance<py::int_>(boxes)) {
-                     const long long k = boxes.cast<long long>();   // (an int beyond long long: pybind's cast error)
-                     if (k < 0 || k > 1024)
-                         throw py::value_error("boxes must be None or an int in 1 ... 1024 (the number of labels)");
-                     boxLabels = (uint32_t)k;
-                 } else if (!boxes.is_none())
-                     throw py::value_error("boxes must be None or an int in 1 ... 1024 (the number of labels)");
-                 if (supersample < 1 || supersample > 4)
-                     throw py::value_error("supersample must be 1, 2, 3 or 4");
-                 if (flow && render_outputs == Manager::RenderOutputs::RGB)
-                     throw py::value_error("flow needs depth: render_outputs RGB renders none");
-                 if (flow && boxLabels)
-                     throw py::value_error("flow and boxes exclude each other: under flow the ids tensor holds visibility "
-                                           "ids, the box stage needs a segmask");
-                 // positions: False / None (no output), True or "world", or "view"
-                 uint32_t positionFrame = 0;
-                 if (py::isinstance<py::bool_>(positions))
-                     positionFrame = positions.cast<bool>() ? 1u : 0u;
-                 else if (py::isinstance<py::str>(positions) && positions.cast<std::string>() == "world")
-                     positionFrame = 1;
-                 else if (py::isinstance<py::str>(positions) && positions.cast<std::string>() == "view")
-                     positionFrame = 2;
-                 else if (!positions.is_none())
-                     throw py::value_error("positions must be False, True, \"world\" or \"view\"");
-                 if (positionFrame && render_outputs == Manager::RenderOutputs::RGB)
-                     throw py::value_error("positions need depth: render_outputs RGB renders none");
-                 if (mesh_vertices.size() && (mesh_vertices.ndim() != 2 || mesh_vertices.shape(1) != 3))
-                     throw py::value_error("mesh_vertices must have shape [N, 3]");
-                 if (mesh_uvs.size() && (mesh_uvs.ndim() != 2 || mesh_uvs.shape(1) != 2))
-                     throw py::value_error("mesh_uvs must have shape [N, 2]");
-                 if ((size_t)num_worlds != worlds.size())
-                     throw py::value_error("num_worlds does not match len(worlds)");
-                 // the C ABI carries no lengths for the per-mesh arrays and reads
-                 // uvs row-for-row with vertices: check them here
-                 if (mesh_indices_offsets.size() != mesh_vertex_offsets.size() ||
-                     mesh_materials.size() != mesh_vertex_offsets.size())
-                     throw py::value_error("mesh_vertex_offsets, mesh_indices_offsets and "
-                                           "mesh_materials must have one entry per mesh");
-                 if ((mesh_uvs.size() ? mesh_uvs.shape(0) : 0) !=
-                     (mesh_vertices.size() ? mesh_vertices.shape(0) : 0))
-                     throw py::value_error("mesh_uvs must have one row per row of mesh_vertices");
-                 std::vector<ImportedCamera> cameras(pycameras.size());
-                 std::vector<Manager::CameraProjection> projections(pycameras.size());
-                 bool anyProjection = false;
-                 for (size_t i = 0; i < pycameras.size(); ++i) {
-                     cameras[i] = pycameras[i].cam;
-                     projections[i] = pycameras[i].proj;
-                     anyProjection = anyProjection || projections[i].vfovDeg != 90.0f || projections[i].znear != 0.0f;
-                 }
-                 if (render_mode == Manager::RenderMode::Raytracer)
-                     for (const Manager::CameraProjection &q : projections)
-                         if (!(q.znear < 1000.0f))
-                             throw py::value_error("znear must be below the Raytracer far plane (1000)");
-                 std::vector<const char *> cstrs(asset_paths.size());
-                 std::vector<int32_t> mat_assignments(asset_paths.size());
-                 for (size_t i = 0; i < asset_paths.size(); ++i) {
-                     cstrs[i] = asset_paths[i].path.c_str();
-                     mat_assignments[i] = asset_paths[i].matID;
-                 }
-                 std::vector<const char *> texture_cstrs(texture_paths.size());
-                 for (size_t i = 0; i < texture_paths.size(); ++i)
-                     texture_cstrs[i] = texture_paths[i].c_str();
+                 const Options opt = parseOptions(render_outputs, supersample, positions, boxes, observations, rays, flow);
+                 checkScene((size_t)num_worlds, worlds.size(), render_mode, pycameras, mesh_vertices, mesh_uvs,
+                            mesh_vertex_offsets, mesh_indices_offsets, mesh_materials);
 
+                 // fill the Config: the reference's fields first
+                 ConfigStore s;
+                 bool anyProjection = false;
+                 for (const PyCamera &c : pycameras) {
+                     s.cameras.push_back(c.cam);
+                     s.projections.push_back(c.proj);
+                     anyProjection = anyProjection || c.proj.vfovDeg != 90.0f || c.proj.znear != 0.0f;
+                 }
+                 for (const ImportedAsset &a : asset_paths) {
+                     s.assetPaths.push_back(a.path.c_str());
+                     s.matAssignments.push_back(a.matID);
+                 }
+                 for (const std::string &p : texture_paths)
+                     s.texturePaths.push_back(p.c_str());
                  Manager::Config cfg {};
                  cfg.gpuID = gpu_id;
                  cfg.numWorlds = (uint32_t)num_worlds;
@@ -541,88 +600,55 @@ PYBIND11_MODULE(madrona_renderer, m)
                  g.numVertices = mesh_vertices.size() ? (uint32_t)mesh_vertices.shape(0) : 0;
                  g.numIndices = (uint32_t)mesh_indices.size();
                  g.numMeshes = (uint32_t)mesh_vertex_offsets.size();
-                 cfg.rcfg.assetPaths = cstrs.data();
-                 cfg.rcfg.numAssetPaths = (uint32_t)cstrs.size();
-                 cfg.rcfg.matAssignments = mat_assignments.data();
-                 cfg.rcfg.numMatAssignments = (uint32_t)mat_assignments.size();
+                 cfg.rcfg.assetPaths = s.assetPaths.data();
+                 cfg.rcfg.numAssetPaths = (uint32_t)s.assetPaths.size();
+                 cfg.rcfg.matAssignments = s.matAssignments.data();
+                 cfg.rcfg.numMatAssignments = (uint32_t)s.matAssignments.size();
                  cfg.rcfg.additionalMats = mats.data();
                  cfg.rcfg.numAdditionalMats = (uint32_t)mats.size();
-                 cfg.rcfg.additionalTextures = texture_cstrs.data();
-                 cfg.rcfg.numAdditionalTextures = (uint32_t)texture_cstrs.size();
+                 cfg.rcfg.additionalTextures = s.texturePaths.data();
+                 cfg.rcfg.numAdditionalTextures = (uint32_t)s.texturePaths.size();
                  cfg.rcfg.importedInstances = const_cast<ImportedInstance *>(instances.data());
                  cfg.rcfg.numInstances = (uint32_t)instances.size();
-                 cfg.rcfg.cameras = const_cast<ImportedCamera *>(cameras.data());
-                 cfg.rcfg.numCameras = (uint32_t)cameras.size();
+                 cfg.rcfg.cameras = s.cameras.data();
+                 cfg.rcfg.numCameras = (uint32_t)s.cameras.size();
                  cfg.rcfg.worlds = const_cast<Sim::WorldInit *>(worlds.data());
-                 // additions: one renderer over several devices; spare instance rows
+                 // ... then the additions: one renderer over several devices; spare instance rows
                  cfg.deviceIDs = device_ids.empty() ? nullptr : device_ids.data();
                  cfg.numDevices = (uint32_t)device_ids.size();
                  if (max_instances_per_world < 0)
                      throw py::value_error("max_instances_per_world must not be negative");
                  cfg.maxInstancesPerWorld = (uint32_t)max_instances_per_world;
                  cfg.renderOutputs = render_outputs;
-                 cfg.cameraProjections = anyProjection ? projections.data() : nullptr;
-                 // world_lights: [(direction, ambient, diffuse)] per world, or None
-                 std::vector<Manager::Light> lights;
+                 cfg.cameraProjections = anyProjection ? s.projections.data() : nullptr;
                  if (!world_lights.is_none()) {
-                     const py::sequence seq = world_lights.cast<py::sequence>();
-                     if ((int64_t)py::len(seq) != num_worlds)
-                         throw py::value_error("world_lights needs one (direction, ambient, diffuse) per world");
-                     for (const py::handle &h : seq) {
-                         const py::tuple t = py::tuple(py::reinterpret_borrow<py::object>(h));
-                         if (t.size() != 3)
-                             throw py::value_error("world_lights entries are (direction, ambient, diffuse)");
-                         const std::array<float, 3> d = t[0].cast<std::array<float, 3>>();
-                         const Manager::Light l = { { d[0], d[1], d[2] }, t[1].cast<float>(), t[2].cast<float>() };
-                         checkLight(l);
-                         lights.push_back(l);
-                     }
-                     cfg.worldLights = lights.data();
+                     s.lights = parseLights(world_lights, num_worlds);
+                     cfg.worldLights = s.lights.data();
                  }
                  // instance_colors: None (no column), True (a zero-filled one) or [num_instances, 4] uint8
-                 py::array_t<uint8_t, py::array::c_style | py::array::forcecast> colors;
-                 if (py::isinstance<py::bool_>(instance_colors)) {
-                     cfg.instanceColorColumn = instance_colors.cast<bool>();
-                 } else if (!instance_colors.is_none()) {
-                     colors = py::array_t<uint8_t, py::array::c_style | py::array::forcecast>::ensure(instance_colors);
-                     if (!colors || colors.ndim() != 2 || (size_t)colors.shape(0) != instances.size() || colors.shape(1) != 4)
-                         throw py::value_error("instance_colors must be None, True or a uint8 array of shape [num_instances, 4]");
-                     cfg.instanceColors = colors.data();
-                     cfg.instanceColorColumn = true;
-                 }
+                 s.colors = parseColumn<uint8_t>(instance_colors, instances.size(), 4,
+                                                 "instance_colors must be None, True or a uint8 array of shape [num_instances, 4]",
+                                                 cfg.instanceColorColumn, cfg.instanceColors);
                  // instance_materials: None (no column), True (a column of -1) or [num_instances] int32
-                 py::array_t<int32_t, py::array::c_style | py::array::forcecast> matIds;
-                 if (py::isinstance<py::bool_>(instance_materials)) {
-                     cfg.instanceMaterialColumn = instance_materials.cast<bool>();
-                 } else if (!instance_materials.is_none()) {
-                     matIds = py::array_t<int32_t, py::array::c_style | py::array::forcecast>::ensure(instance_materials);
-                     if (!matIds || matIds.ndim() != 1 || (size_t)matIds.shape(0) != instances.size())
-                         throw py::value_error("instance_materials must be None, True or an int32 array of shape [num_instances]");
-                     cfg.instanceMaterials = matIds.data();
-                     cfg.instanceMaterialColumn = true;
-                 }
+                 s.materials = parseColumn<int32_t>(instance_materials, instances.size(), 0,
+                                                    "instance_materials must be None, True or an int32 array of shape [num_instances]",
+                                                    cfg.instanceMaterialColumn, cfg.instanceMaterials);
                  cfg.normals = normals;
                  // instance_labels: None (no column), True (a column of MRX_LABEL_OBJECT) or [num_instances] int32
-                 py::array_t<int32_t, py::array::c_style | py::array::forcecast> labels;
-                 if (py::isinstance<py::bool_>(instance_labels)) {
-                     cfg.instanceLabelColumn = instance_labels.cast<bool>();
-                 } else if (!instance_labels.is_none()) {
-                     labels = py::array_t<int32_t, py::array::c_style | py::array::forcecast>::ensure(instance_labels);
-                     if (!labels || labels.ndim() != 1 || (size_t)labels.shape(0) != instances.size())
-                         throw py::value_error("instance_labels must be None, True or an int32 array of shape [num_instances]");
-                     cfg.instanceLabels = labels.data();
-                     cfg.instanceLabelColumn = true;
-                 }
+                 s.labels = parseColumn<int32_t>(instance_labels, instances.size(), 0,
+                                                 "instance_labels must be None, True or an int32 array of shape [num_instances]",
+                                                 cfg.instanceLabelColumn, cfg.instanceLabels);
                  cfg.supersample = (uint32_t)supersample;
-                 cfg.positions = positionFrame;
-                 cfg.boxLabels = boxLabels;
-                 cfg.observations = obsArg.field;
-                 cfg.raysPerWorld = raysPerWorld;
+                 cfg.positions = opt.positionFrame;
+                 cfg.boxLabels = opt.boxLabels;
+                 cfg.observations = opt.obs.field;
+                 cfg.raysPerWorld = opt.raysPerWorld;
                  cfg.flow = flow;
+
                  std::unique_ptr<Manager> mgr(new Manager(cfg));
                  // (mrx_config cannot carry the range: the first frame is packed raw and restarted under it here)
-                 if (obsArg.hasRange)
-                     mgr->setObservationDepthRange(obsArg.lo, obsArg.hi);
+                 if (opt.obs.hasRange)
+                     mgr->setObservationDepthRange(opt.obs.lo, opt.obs.hi);
                  return mgr.release();
              }),
              py::arg("gpu_id"), py::arg("num_worlds"), py::arg("render_mode"),
@@ -665,16 +691,6 @@ PYBIND11_MODULE(madrona_renderer, m)
         .def("step", &Manager::step)
         .def("render", &Manager::render)
         .def("sync", &Manager::sync)
-        .def("rgb_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().rgbTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
-        .def("depth_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().depthTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
-        // u8 [views, H, W, 4], storage as rgb's: the view-space normal of every pixel's winning triangle (needs normals=True)
-        .def("normal_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().normalTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
         // supersampling: the factor; the s * W x s * H tensor the render writes for "rgb", "depth", "segmask",
         // "visibility" or "normal" (RuntimeError at factor 1 or on an output that is not rendered); the resolve stage alone
         .def_property_readonly("supersample", &Manager::supersample)
@@ -691,54 +707,26 @@ PYBIND11_MODULE(madrona_renderer, m)
              },
              py::arg("name"), py::arg("shard") = py::none())
         .def("resolve", &Manager::resolve)
-        // position output: None, "world" or "view"; f32 [views, H, W, 4], (x, y, z, 1) per hit pixel and zeros on
-        // background (RuntimeError without positions=); the unprojection stage alone
+        // position output: None, "world" or "view"; the unprojection stage alone
         .def_property_readonly("positions",
                                [](const Manager &self) -> py::object {
                                    const uint32_t f = self.positions();
                                    return f == 0 ? py::object(py::none()) : py::object(py::str(f == 2 ? "view" : "world"));
                                })
-        .def("position_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().positionTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
         .def("unproject", &Manager::unproject)
-        // box labels: K or 0; i32 [views, K, 5] = (xmin, ymin, xmax, ymax, count) (RuntimeError without boxes=); the
-        // box stage alone
+        // box labels: K or 0; the box stage alone
         .def_property_readonly("box_labels", &Manager::boxLabels)
-        .def("box_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().boxTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
         .def("boxes", &Manager::boxes)
-        // ray-cast sensor: R or 0; f32 [worlds, R, 8] rays and i32 [worlds] mount rows, both written like a pose; f32
-        // [worlds, R] t of the nearest hit and i32 [worlds, R] the id of the row that was hit (RuntimeError without
-        // rays=); the trace stage alone
+        // ray-cast sensor: R or 0; the trace stage alone
         .def_property_readonly("rays", &Manager::rays)
-        .def("ray_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().rayTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
-        .def("ray_frame_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().rayFrameTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
-        .def("ray_distance_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().rayDistanceTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
-        .def("ray_id_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().rayIdTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
         .def("trace", &Manager::trace)
-        // optical-flow output: whether there is one; f32 [views, H, W, 4] = (dx, dy, dz, 1) per pixel whose point was in
-        // front of the previous camera, zeros elsewhere (RuntimeError without flow=True); the flow stage alone, which
-        // does not advance the snapshot; the snapshot stage alone (after an episode reset wrote the poses)
+        // optical-flow output: whether there is one; the flow stage alone, which does not advance the snapshot; the
+        // snapshot stage alone (after an episode reset wrote the poses)
         .def_property_readonly("flows", &Manager::flows)
-        .def("flow_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().flowTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
         .def("flow", &Manager::flow)
         .def("flow_snapshot", &Manager::flowSnapshot)
-        // packed observation output: the option as a dict or None; [views, S * C, H, W] in the dtype asked for, frame 0
-        // the oldest (RuntimeError without observations=); the reset column u8 [views] (RuntimeError with stack 1); the
-        // observation stage alone -- on a stacked renderer one more frame; the depth range, whose setter restarts
-        // every stack
+        // packed observation output: the option as a dict or None; the observation stage alone -- on a stacked renderer
+        // one more frame; the depth range, whose setter restarts every stack
         .def_property_readonly("observations",
                                [](const Manager &self) -> py::object {
                                    const uint32_t f = self.observations();
@@ -753,12 +741,6 @@ PYBIND11_MODULE(madrona_renderer, m)
                                    d["depth_range"] = hi > 0.0f ? py::object(py::make_tuple(lo, hi)) : py::object(py::none());
                                    return d;
                                })
-        .def("observation_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().observationTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
-        .def("observation_reset_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().observationResetTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
         .def("observe", &Manager::observe)
         .def("set_observation_depth_range",
              [](Manager &self, py::object lo, py::object hi) {
@@ -771,70 +753,16 @@ PYBIND11_MODULE(madrona_renderer, m)
                  self.setObservationDepthRange(l, h);
              },
              py::arg("lo"), py::arg("hi") = py::none())
-        .def("segmask_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().segmaskTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
-        .def("visibility_tensor",
-             [](py::object self, py::object shard) { return wrapTensor(self, self.cast<Manager &>().visibilityTensor(shardOf(self, shard))); },
-             py::arg("shard") = py::none())
         .def("rgb_cuda_ptr", [](py::object self, py::object shard) { return self.cast<Manager &>().rgbCudaPtr(shardOf(self, shard)); },
              py::arg("shard") = py::none())
         .def("depth_cuda_ptr", [](py::object self, py::object shard) { return self.cast<Manager &>().depthCudaPtr(shardOf(self, shard)); },
              py::arg("shard") = py::none())
         .def("segmask_cuda_ptr", [](py::object self, py::object shard) { return self.cast<Manager &>().segmaskCudaPtr(shardOf(self, shard)); },
              py::arg("shard") = py::none())
-        .def("instance_scale_tensor",
-             [](py::object self, py::object shard) {
-                 return wrapTensor(self, self.cast<Manager &>().instanceScaleTensor(shardOf(self, shard)));
-             },
-             py::arg("shard") = py::none())
         // binds rows to the object ids their ObjectID column holds (spare rows: max_instances_per_world)
         .def("refresh_objects", &Manager::refreshObjects)
         .def_property_readonly("num_shards", &Manager::numShards)
         .def("shard_first_world", &Manager::shardFirstWorld, py::arg("shard"))
-        .def("instance_position_tensor",
-             [](py::object self, py::object shard) {
-                 return wrapTensor(self, self.cast<Manager &>().instancePositionTensor(shardOf(self, shard)));
-             },
-             py::arg("shard") = py::none())
-        .def("instance_object_tensor",
-             [](py::object self, py::object shard) {
-                 return wrapTensor(self, self.cast<Manager &>().instanceObjectTensor(shardOf(self, shard)));
-             },
-             py::arg("shard") = py::none())
-        // u8 [instances, 4]: the colour override of every row, a == 0 = none (needs instance_colors=)
-        .def("instance_color_tensor",
-             [](py::object self, py::object shard) {
-                 return wrapTensor(self, self.cast<Manager &>().instanceColorTensor(shardOf(self, shard)));
-             },
-             py::arg("shard") = py::none())
-        // i32 [instances]: the label of every row, MRX_LABEL_OBJECT = the bound object's id (needs instance_labels=)
-        .def("instance_label_tensor",
-             [](py::object self, py::object shard) {
-                 return wrapTensor(self, self.cast<Manager &>().instanceLabelTensor(shardOf(self, shard)));
-             },
-             py::arg("shard") = py::none())
-        // i32 [instances]: the material override of every row, outside the table = none (needs instance_materials=)
-        .def("instance_material_tensor",
-             [](py::object self, py::object shard) {
-                 return wrapTensor(self, self.cast<Manager &>().instanceMaterialTensor(shardOf(self, shard)));
-             },
-             py::arg("shard") = py::none())
-        .def("instance_rotation_tensor",
-             [](py::object self, py::object shard) {
-                 return wrapTensor(self, self.cast<Manager &>().instanceRotationTensor(shardOf(self, shard)));
-             },
-             py::arg("shard") = py::none())
-        .def("camera_position_tensor",
-             [](py::object self, py::object shard) {
-                 return wrapTensor(self, self.cast<Manager &>().cameraPositionTensor(shardOf(self, shard)));
-             },
-             py::arg("shard") = py::none())
-        .def("camera_rotation_tensor",
-             [](py::object self, py::object shard) {
-                 return wrapTensor(self, self.cast<Manager &>().cameraRotationTensor(shardOf(self, shard)));
-             },
-             py::arg("shard") = py::none())
         .def("time_renders", &Manager::timeRenders, py::arg("steps"))
         .def("time_steps_host", &Manager::timeStepsHost, py::arg("steps"))
         .def("mark", &Manager::mark, py::arg("which"))
@@ -898,15 +826,6 @@ PYBIND11_MODULE(madrona_renderer, m)
                  const int64_t total = (int64_t)self.numViews();
                  if (first_view < 0 || first_view > total)
                      throw py::value_error("first_view out of range");
-                 auto asVec = [](py::object o, bool &scalar) {
-                     std::vector<float> v;
-                     scalar = !py::isinstance<py::sequence>(o) && !py::hasattr(o, "__len__");
-                     if (scalar)
-                         v.push_back(o.cast<float>());
-                     else
-                         v = py::array_t<float, py::array::c_style | py::array::forcecast>(o).cast<std::vector<float>>();
-                     return v;
-                 };
                  bool fs = true, zs = true;
                  std::vector<float> fv = asVec(vfov, fs), zv;
                  if (znear.is_none())
@@ -939,19 +858,10 @@ PYBIND11_MODULE(madrona_renderer, m)
                  const int64_t total = (int64_t)self.numWorlds();
                  if (first_world < 0 || first_world > total)
                      throw py::value_error("first_world out of range");
-                 const py::array_t<float, py::array::c_style | py::array::forcecast> dir(direction);
+                 const CArray<float> dir(direction);
                  const bool one = dir.ndim() == 1;
                  if (!((one && dir.shape(0) == 3) || (dir.ndim() == 2 && dir.shape(1) == 3)))
                      throw py::value_error("direction must be one (x, y, z) or an array of shape [n, 3]");
-                 auto asVec = [](py::object o, bool &scalar) {
-                     std::vector<float> v;
-                     scalar = !py::isinstance<py::sequence>(o) && !py::hasattr(o, "__len__");
-                     if (scalar)
-                         v.push_back(o.cast<float>());
-                     else
-                         v = py::array_t<float, py::array::c_style | py::array::forcecast>(o).cast<std::vector<float>>();
-                     return v;
-                 };
                  bool as = true, ds = true;
                  std::vector<float> av, dv;
                  if (!ambient.is_none())
@@ -1006,43 +916,17 @@ PYBIND11_MODULE(madrona_renderer, m)
         // several shards splits them).  Stream-ordered: renders enqueued before keep the old ids.
         // per-instance labels from host memory, as set_instance_materials / instance_materials below
         .def("set_instance_labels",
-             [](Manager &self, py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids, int64_t first_row) {
-                 if (ids.ndim() != 1)
-                     throw py::value_error("labels must be a one-dimensional int32 array");
-                 if (first_row < 0 || first_row + (int64_t)ids.shape(0) > (int64_t)self.numInstanceRows())
-                     throw py::value_error("more labels than instance rows from first_row on");
-                 const int32_t none = MRX_LABEL_OBJECT;
-                 if (!self.setInstanceLabels((uint32_t)first_row, (uint32_t)ids.shape(0), ids.shape(0) ? ids.data() : &none))
-                     throw py::value_error(mrx_last_error());
+             [](Manager &self, CArray<int32_t> ids, int64_t first_row) {
+                 setRows(self, &Manager::setInstanceLabels, MRX_LABEL_OBJECT, "labels", "labels", ids, first_row);
              },
              py::arg("labels"), py::arg("first_row") = 0)
-        .def("instance_labels",
-             [](Manager &self) {
-                 const uint32_t n = self.numInstanceRows();
-                 py::array_t<int32_t> out(n);
-                 int32_t none = MRX_LABEL_OBJECT;
-                 self.instanceLabels(0, n, n ? out.mutable_data() : &none);
-                 return out;
-             })
+        .def("instance_labels", [](Manager &self) { return getRows(self, &Manager::instanceLabels, MRX_LABEL_OBJECT); })
         .def("set_instance_materials",
-             [](Manager &self, py::array_t<int32_t, py::array::c_style | py::array::forcecast> ids, int64_t first_row) {
-                 if (ids.ndim() != 1)
-                     throw py::value_error("materials must be a one-dimensional int32 array");
-                 if (first_row < 0 || first_row + (int64_t)ids.shape(0) > (int64_t)self.numInstanceRows())
-                     throw py::value_error("more material ids than instance rows from first_row on");
-                 const int32_t none = -1;
-                 if (!self.setInstanceMaterials((uint32_t)first_row, (uint32_t)ids.shape(0), ids.shape(0) ? ids.data() : &none))
-                     throw py::value_error(mrx_last_error());
+             [](Manager &self, CArray<int32_t> ids, int64_t first_row) {
+                 setRows(self, &Manager::setInstanceMaterials, -1, "materials", "material ids", ids, first_row);
              },
              py::arg("materials"), py::arg("first_row") = 0)
-        .def("instance_materials",
-             [](Manager &self) {
-                 const uint32_t n = self.numInstanceRows();
-                 py::array_t<int32_t> out(n);
-                 int32_t none = -1;
-                 self.instanceMaterials(0, n, n ? out.mutable_data() : &none);
-                 return out;
-             })
+        .def("instance_materials", [](Manager &self) { return getRows(self, &Manager::instanceMaterials, -1); })
         .def("camera_projection",
              [](Manager &self) {
                  const uint32_t n = self.numViews();
@@ -1066,4 +950,48 @@ PYBIND11_MODULE(madrona_renderer, m)
              },
              py::arg("stream"), py::arg("shard") = py::none())
         .def_readonly("num_agents", &Manager::numAgents);
+
+    // the tensor getters, NAME(shard=None); one the renderer was created without raises RuntimeError
+    const auto tensor = [&renderer](const char *name, Tensor (Manager::*get)(uint32_t) const) {
+        renderer.def(name,
+                     [get](py::object self, py::object shard) {
+                         return wrapTensor(self, (self.cast<Manager &>().*get)(shardOf(self, shard)));
+                     },
+                     py::arg("shard") = py::none());
+    };
+    tensor("rgb_tensor", &Manager::rgbTensor);
+    tensor("depth_tensor", &Manager::depthTensor);
+    tensor("segmask_tensor", &Manager::segmaskTensor);
+    tensor("visibility_tensor", &Manager::visibilityTensor);
+    // u8 [views, H, W, 4], storage as rgb's: the view-space normal of every pixel's winning triangle (needs normals=True)
+    tensor("normal_tensor", &Manager::normalTensor);
+    // f32 [views, H, W, 4], (x, y, z, 1) per hit pixel and zeros on background (needs positions=)
+    tensor("position_tensor", &Manager::positionTensor);
+    // i32 [views, K, 5] = (xmin, ymin, xmax, ymax, count) (needs boxes=)
+    tensor("box_tensor", &Manager::boxTensor);
+    // f32 [worlds, R, 8] rays and i32 [worlds] mount rows, both written like a pose; f32 [worlds, R] t of the nearest hit
+    // and i32 [worlds, R] the id of the row that was hit (need rays=)
+    tensor("ray_tensor", &Manager::rayTensor);
+    tensor("ray_frame_tensor", &Manager::rayFrameTensor);
+    tensor("ray_distance_tensor", &Manager::rayDistanceTensor);
+    tensor("ray_id_tensor", &Manager::rayIdTensor);
+    // f32 [views, H, W, 4] = (dx, dy, dz, 1) per pixel whose point was in front of the previous camera, zeros elsewhere
+    // (needs flow=True)
+    tensor("flow_tensor", &Manager::flowTensor);
+    // [views, S * C, H, W] in the dtype asked for, frame 0 the oldest (needs observations=); the reset column u8 [views]
+    // (RuntimeError with stack 1)
+    tensor("observation_tensor", &Manager::observationTensor);
+    tensor("observation_reset_tensor", &Manager::observationResetTensor);
+    tensor("instance_position_tensor", &Manager::instancePositionTensor);
+    tensor("instance_rotation_tensor", &Manager::instanceRotationTensor);
+    tensor("instance_scale_tensor", &Manager::instanceScaleTensor);
+    tensor("instance_object_tensor", &Manager::instanceObjectTensor);
+    // u8 [instances, 4]: the colour override of every row, a == 0 = none (needs instance_colors=)
+    tensor("instance_color_tensor", &Manager::instanceColorTensor);
+    // i32 [instances]: the label of every row, MRX_LABEL_OBJECT = the bound object's id (needs instance_labels=)
+    tensor("instance_label_tensor", &Manager::instanceLabelTensor);
+    // i32 [instances]: the material override of every row, outside the table = none (needs instance_materials=)
+    tensor("instance_material_tensor", &Manager::instanceMaterialTensor);
+    tensor("camera_position_tensor", &Manager::cameraPositionTensor);
+    tensor("camera_rotation_tensor", &Manager::cameraRotationTensor);
 }
