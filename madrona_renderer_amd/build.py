@@ -64,30 +64,35 @@ def hipcc():
     return exe
 
 
+def hip_command(out, extra_flags=()):
+    """The hipcc line of libmrx_hip.so, written to `out` (scripts/ab_build.sh builds its variants with it)."""
+    cmd = [hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC",
+           "-shared", "-ffp-contract=off", "-fno-fast-math",
+           # per-pixel state lives in small unrolled arrays; LLVM's AMDGPU
+           # promote-alloca pass turns them into 16-wide vector registers
+           # whose every conditional update copies the whole tuple
+           "-mllvm", "-disable-promote-alloca-to-vector",
+           # the SLP vectorizer packs scalar f32 math into v_pk_* pairs and
+           # pays for it in v_mov shuffles and ~40 extra VGPRs (no rate gain
+           # on gfx950: packed f32 issues at the scalar-f32 rate)
+           "-fno-slp-vectorize",
+           # the command processor writes the first 12 dwords of a kernel's arguments into SGPRs at wave
+           # launch: the group kernel's argument header (raster.hpp GroupHeader)
+           "-mllvm", "-amdgpu-kernarg-preload-count=12",
+           "-Wall", "-Wno-unused-function"]
+    cmd += list(extra_flags)
+    # e.g. MRX_EXTRA_HIPCC_FLAGS=-DMRX_BVH_DIAG=1 python -m madrona_renderer_amd.build --force
+    # (the BVH kernel's in-kernel stamps and phase switches: scripts/bvh_stamps.py, bvh_ablate.py)
+    cmd += os.environ.get("MRX_EXTRA_HIPCC_FLAGS", "").split()
+    cmd += [os.path.join(CSRC, s) for s in HIP_SOURCES]
+    cmd += ["-lz", "-ldl", "-Wl,-rpath,/opt/rocm/lib", "-o", out]
+    return cmd
+
+
 def build_hip(force=False, verbose=False, extra_flags=()):
     out = lib_path()
     if force or _stale(out, HIP_DEPS):
-        cmd = [hipcc(), "--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC",
-               "-shared", "-ffp-contract=off", "-fno-fast-math",
-               # per-pixel state lives in small unrolled arrays; LLVM's AMDGPU
-               # promote-alloca pass turns them into 16-wide vector registers
-               # whose every conditional update copies the whole tuple
-               "-mllvm", "-disable-promote-alloca-to-vector",
-               # the SLP vectorizer packs scalar f32 math into v_pk_* pairs and
-               # pays for it in v_mov shuffles and ~40 extra VGPRs (no rate gain
-               # on gfx950: packed f32 issues at the scalar-f32 rate)
-               "-fno-slp-vectorize",
-               # the command processor writes the first 12 dwords of a kernel's arguments into SGPRs at wave
-               # launch: the group kernel's argument header (raster.hpp GroupHeader)
-               "-mllvm", "-amdgpu-kernarg-preload-count=12",
-               "-Wall", "-Wno-unused-function"]
-        cmd += list(extra_flags)
-        # e.g. MRX_EXTRA_HIPCC_FLAGS=-DMRX_BVH_DIAG=1 python -m madrona_renderer_amd.build --force
-        # (the BVH kernel's in-kernel stamps and phase switches: scripts/bvh_stamps.py, bvh_ablate.py)
-        cmd += os.environ.get("MRX_EXTRA_HIPCC_FLAGS", "").split()
-        cmd += [os.path.join(CSRC, s) for s in HIP_SOURCES]
-        cmd += ["-lz", "-ldl", "-Wl,-rpath,/opt/rocm/lib", "-o", out]
-        _run(cmd, verbose)
+        _run(hip_command(out, extra_flags), verbose)
     return out
 
 

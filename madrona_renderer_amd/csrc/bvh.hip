@@ -247,6 +247,123 @@ __device__ __forceinline__ unsigned long long packHit(float it, uint32_t low)
     return ((unsigned long long)__float_as_uint(it) << 32) | low;
 }
 
+// Diagnostics (in-kernel stamps, MRX_DEBUG_STAMPS=1; phases switched off, MRX_DEBUG_SKIP) exist only in a build with
+// -DMRX_BVH_DIAG=1 (scripts/ab_build.sh diag -DMRX_BVH_DIAG=1): the flags and the stamp pointer cost scalar registers
+// in loops that have none to spare.  `stamps` and `lane` are the caller's.
+#define MRX_STAMP(i)                                                           \
+    do {                                                                       \
+        if (MRX_BVH_DIAG && stamps && lane == 0)                               \
+            stamps[i] = __builtin_amdgcn_s_memrealtime();                      \
+    } while (0)
+
+// ---- What the tile kernel and the flat kernel share, each piece once.  (The exact corner test of the four planes,
+//      the large pass over a strip, the textured record and the unpacking of a TLAS record are still written out in
+//      both: as functions they compile to other instructions -- scripts/bvh_asm_diff.py -- in kernels at their
+//      register limit.)
+// Pixel range of a triangle inside a tile: the conservative box of setup, less all but 1/32 of its one-pixel margin.
+// First and last pixel each way, as whole numbers: nothing is left if x0 > x1 or y0 > y1.
+struct TrimmedBox { float x0, x1, y0, y1; };
+__device__ __forceinline__ TrimmedBox trimBox(const TriPlanes &c, float TX0, float TX1, float TY0, float TY1)
+{
+    const float kTrim = 0.96875f;
+    TrimmedBox b;
+    b.x0 = ceilf(fmaxf(c.bbX0 + kTrim, TX0)); b.x1 = floorf(fminf(c.bbX1 - kTrim, TX1));
+    b.y0 = ceilf(fmaxf(c.bbY0 + kTrim, TY0)); b.y1 = floorf(fminf(c.bbY1 - kTrim, TY1));
+    return b;
+}
+
+// Small triangles, by (triangle, row of its box): the rows of all the wave's small triangles (lane = triangle:
+// rowsMine rows from iy0 on, bw pixels from ix0 on, planes c, low key lowKey) are numbered through (prefix sum over
+// the lanes) and dealt 64 at a time -- items itemFirst, + itemStep, ... are this wave's -- a lane fetches the planes
+// of its row's triangle from the lane that set it up (ds_bpermute) and walks the row four pixels per step: every lane
+// has a row, however uneven the boxes.  ZSTR: row stride of the depth buffer (ZS of the tile kernel, kFlatZS).
+template <int ZSTR>
+__device__ __forceinline__ void walkSmallRows(const TriPlanes &c, int rowsMine, int ix0, int bw, int iy0, uint32_t lowKey,
+                                              int itemFirst, int itemStep, unsigned long long *zbuf, uint32_t tileX0,
+                                              uint32_t tileY0, float invFar, float invNear, int lane)
+{
+    const int incl = waveInclusiveSum(rowsMine);
+    const int total = __builtin_amdgcn_readlane(incl, kWave - 1);
+    const int packedBox = ix0 | (bw << 16);        // (both < 2^15)
+    for (int item0 = itemFirst; item0 < total; item0 += itemStep) {
+        const int j = item0 + lane;
+        const bool act = j < total;
+        // the lane t whose rows hold item j: smallest t with incl[t] > j
+        int t = 0;
+#pragma unroll
+        for (int step = kWave / 2; step >= 1; step >>= 1) {
+            const int probe = __builtin_amdgcn_ds_bpermute((t + step - 1) << 2, incl);
+            t += probe <= j ? step : 0;
+        }
+        t = act ? t : 0;
+        const int src = t << 2;
+        const int inclT = __builtin_amdgcn_ds_bpermute(src, incl);
+        const int rowsT = __builtin_amdgcn_ds_bpermute(src, rowsMine);
+        const int boxT = __builtin_amdgcn_ds_bpermute(src, packedBox);
+        const int y0T = __builtin_amdgcn_ds_bpermute(src, iy0);
+        const uint32_t lowT = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)lowKey);
+#define MRX_GATHER(v) __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v)))
+        const f32x2 A01 = { MRX_GATHER(c.A0), MRX_GATHER(c.A1) }, A2D = { MRX_GATHER(c.A2), MRX_GATHER(c.Dx) };
+        const f32x2 B01 = { MRX_GATHER(c.B0), MRX_GATHER(c.B1) }, B2D = { MRX_GATHER(c.B2), MRX_GATHER(c.Dy) };
+        const f32x2 C01 = { MRX_GATHER(c.C0), MRX_GATHER(c.C1) }, C2D = { MRX_GATHER(c.C2), MRX_GATHER(c.Dc) };
+#undef MRX_GATHER
+        const int xBeg = boxT & 0xFFFF, xEnd = xBeg + (boxT >> 16);
+        const int sy = y0T + (j - (inclT - rowsT));
+        const float py = (float)sy;
+        const f32x2 yy = { py, py };
+        const f32x2 r01 = fma2(B01, yy, C01);
+        const f32x2 r2d = fma2(B2D, yy, C2D);
+        unsigned long long *zline = zbuf + (sy - (int)tileY0) * ZSTR - (int)tileX0;
+        for (int sx = xBeg; __ballot(act && sx < xEnd) != 0; sx += 4) {
+            if (act && sx < xEnd) {
+#pragma unroll
+                for (int q4 = 0; q4 < 4; ++q4) {
+                    const float px = (float)(sx + q4);
+                    const f32x2 pp = { px, px };
+                    const f32x2 e01 = fma2(A01, pp, r01);
+                    const f32x2 e2d = fma2(A2D, pp, r2d);
+                    if (sx + q4 < xEnd && fminf(fminf(e01.x, e01.y), e2d.x) >= 0.0f &&
+                        e2d.y > invFar && e2d.y <= invNear)
+                        atomicMax(zline + sx + q4, packHit(e2d.y, lowT));
+                }
+            }
+        }
+    }
+}
+
+// The planes of a triangle as a row of bigList / triRec holds them (loadPlanes reads them back in pairs)
+__device__ __forceinline__ void packPlanes(float4 *dst, const TriPlanes &c)
+{
+    dst[0] = make_float4(c.A0, c.A1, c.A2, c.Dx);
+    dst[1] = make_float4(c.B0, c.B1, c.B2, c.Dy);
+    dst[2] = make_float4(c.C0, c.C1, c.C2, c.Dc);
+}
+
+// An instance's transform -> the first five float4 of its TLAS record (kInstRecDw; the sixth holds kBase and the
+// bound object's first triangle, count and root).  (The leaf set-ups read them back field by field.)
+__device__ __forceinline__ void packInstRecord(float4 *dst, const InstXform &x, int32_t obj)
+{
+    dst[0] = make_float4(x.MV[0][0], x.MV[0][1], x.MV[0][2], x.MV[1][0]);
+    dst[1] = make_float4(x.MV[1][1], x.MV[1][2], x.MV[2][0], x.MV[2][1]);
+    dst[2] = make_float4(x.MV[2][2], x.tv[0], x.tv[1], x.tv[2]);
+    dst[3] = make_float4(x.qo[0], x.qo[1], x.qo[2], x.det);
+    dst[4] = make_float4(x.sc[0], x.sc[1], x.sc[2], __int_as_float(obj));
+}
+
+// A triangle's shading record, as resolveStrip reads it, from setupTriangleCore's shade[].  Untextured scenes: packed
+// colour, texture (NRM: the packed normal rides there), object id, `last` (the world-local triangle index).
+template <bool NRM>
+__device__ __forceinline__ void writeRecord(float4 *shadeTab, uint32_t slot, const float (&shade)[4], uint32_t nrmv, float last)
+{
+    shadeTab[slot] = make_float4(shade[0], NRM ? __uint_as_float(nrmv) : shade[1], shade[2], last);   // [2]: the object id
+}
+// Textured scenes, the unified 48-byte record.  An untextured triangle: packed colour, "no texture", object id.
+__device__ __forceinline__ void writeUntexturedRecord(float (*coldTab)[kCold], uint32_t slot, const float (&shade)[4])
+{
+    float *dst = coldTab[slot];
+    dst[0] = shade[0];
+    *reinterpret_cast<float2 *>(dst + 10) = make_float2(__uint_as_float(0u), shade[2]);
+}
 
 // ---------------------------------------------------------------------------
 // Resolve of a wave's strip: every lane looks up the winners of its pixels (four consecutive
@@ -286,6 +403,31 @@ struct SetupArgs {
     float sx, ox, sz, oz, s6bPad, ambient, diffuse;
     int32_t transposed;
 };
+
+// ResolveArgs from the argument segment (the kernel's only argument sits at offset 0 of it)
+template <bool NRM>
+__device__ __forceinline__ ResolveArgs resolveArgsOfLaunch()
+{
+    KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(pk));
+    return ResolveArgs { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough,
+                         NRM ? pk->normal : nullptr };
+}
+// The first instance row of the world the tile kernel is rendering, which a queue entry's instance counts from: the
+// first row of the pass or, MULTI, of the world of `view` (viewInstances of it, from the argument segment).
+template <bool MULTI>
+__device__ __forceinline__ uint32_t rowBaseOfView(KernargParams pk, uint32_t passBase, uint32_t view)
+{
+    uint32_t rowBase = passBase;
+    if (MULTI) {
+        const uint32_t uni = pk->bvhUniInst, cams = pk->bvhUniCams;
+        if (uni)
+            rowBase = (cams != 1u ? view / cams : view) * uni;
+        else
+            rowBase = pk->worldInstStart[pk->viewWorld[view]];
+    }
+    return rowBase;
+}
 
 // OUT: output selection (raster.hpp OutSel) -- fixed in the flat kernel, kOutByPointer (a null output is skipped
 // at run time) in the tile kernel.  Depth only: no colour is looked up or stashed, no texel is loaded.
@@ -593,11 +735,7 @@ __device__ __forceinline__ void tlasChunks(const PARAMS &p, const PROJ &pj, cons
         }
         if (has) {
             float4 *dst = reinterpret_cast<float4 *>(rec + (size_t)li * kInstRecDw);
-            dst[0] = make_float4(x.MV[0][0], x.MV[0][1], x.MV[0][2], x.MV[1][0]);
-            dst[1] = make_float4(x.MV[1][1], x.MV[1][2], x.MV[2][0], x.MV[2][1]);
-            dst[2] = make_float4(x.MV[2][2], x.tv[0], x.tv[1], x.tv[2]);
-            dst[3] = make_float4(x.qo[0], x.qo[1], x.qo[2], x.det);
-            dst[4] = make_float4(x.sc[0], x.sc[1], x.sc[2], __int_as_float(obj));
+            packInstRecord(dst, x, obj);
             dst[5] = make_float4(__uint_as_float(kBase), o0.x, o0.y, o0.z);
             rects[li] = make_float4(r.x0, r.x1, r.y0, r.y1);
         }
@@ -639,9 +777,52 @@ __device__ __forceinline__ uint32_t *tileNormalTab(unsigned char *smem)
     return reinterpret_cast<uint32_t *>(smem + off);
 }
 
+// First clear of the depth buffer: the waves that have instances to transform in the first pass go straight to
+// their pose loads, the others clear the depth buffer for them
+// (groups of views: the waves that may have instances to transform, by the largest world)
+template <int TW, int TH, bool MULTI>
+__device__ __forceinline__ void clearDepthFirst(const RasterParams &p, unsigned long long *zbuf, uint32_t i0, uint32_t i1,
+                                                uint32_t passInst, uint32_t vShift, float invFar, int wave, int lane)
+{
+    constexpr int ZS = TW + kZPad, kBvhWaves = TH / 8;
+    const uint32_t n0 = MULTI ? (p.bvhUniInst ? min(passInst, p.bvhUniInst) : passInst)
+                              : (i1 > i0 ? min(passInst, i1 - i0) : 0u);
+    const uint32_t busy = min(((n0 + kWave - 1u) / kWave) << vShift, (uint32_t)kBvhWaves);
+    if (busy >= (uint32_t)kBvhWaves) {
+        for (int i = threadIdx.x; i < ZS * TH; i += kWave * kBvhWaves)
+            zbuf[i] = packHit(invFar, 0u);
+    } else if ((uint32_t)wave >= busy) {
+        for (uint32_t i = ((uint32_t)wave - busy) * kWave + (uint32_t)lane; i < (uint32_t)(ZS * TH);
+             i += ((uint32_t)kBvhWaves - busy) * kWave)
+            zbuf[i] = packHit(invFar, 0u);
+    }
+}
+
+// A view's TLAS block in LDS: the light direction in the view's frame and the number of instances (four dwords: the
+// header), [passInst][24] records, [passInst] rectangles
+__device__ __forceinline__ uint32_t tlasDwords(uint32_t passInst) { return passInst * (kInstRecDw + 4u) + 4u; }
+__device__ __forceinline__ float4 *tlasRects(float *rec, uint32_t passInst)
+{
+    return reinterpret_cast<float4 *>(rec + (size_t)passInst * kInstRecDw);
+}
+__device__ __forceinline__ float *tlasHeader(float *rec) { return rec - 4; }
+
+// The priority of a younger workgroup with one view ends behind the barrier that closes its first produce phase -- of
+// one with two, where it turns to its second (read from the argument block: no register held for it)
+__device__ __forceinline__ void endYoungPriority()
+{
+    KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(pk));
+    if (((pk->bvhGroupViews >> 17) & 7u) >= 2u)
+        __builtin_amdgcn_s_setprio(0);
+}
+
 template <int IDS, bool TEX, int TW, int TH, bool CLS, bool MULTI, bool PV, bool MAT = false, bool NRM = false>
 __device__ __forceinline__ void tileKernelBody(const RasterParams p)
 {
+    // The algorithm of DESIGN.md section 4.2, phase by phase: each "==== phase ====" line opens one.  The phases that are
+    // functions (clearDepthFirst, walkSmallRows, resolveStrip) compile to the same instructions either way; the others
+    // stay blocks of this body: as functions they come back with other registers, and the kernel has none to spare.
     extern __shared__ __align__(16) unsigned char smem[];
     // (touchKernelArguments(), which buys the raster kernels 0.1 - 0.4 us per launch, measured nothing here --
     // 482-triangle worlds 25.4 -> 26.0 us, textured 35.6 -> 35.4: this kernel's first phase waits for its pose
@@ -659,6 +840,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
     static_assert((TW == 64 || TW == 32) && (TH == 64 || TH == 32), "tile shapes of the sweep");
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x / kWave);
     const int lane = threadIdx.x % kWave;
+    // ==== prologue: work assignment and the XCD item order ====
     const uint32_t tilesFast = (p.nfast + TW - 1) / TW, tilesSlow = (p.nslow + TH - 1) / TH;
     const uint32_t tilesPerView = tilesFast * tilesSlow;
     // XCD-aware item order for views of several tiles: consecutive workgroups run on consecutive
@@ -691,6 +873,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
         left = blockIdx.x < pairs ? 2u : 1u;
     }
     uint32_t tileX0 = (tile % tilesFast) * TW, tileY0 = (tile / tilesFast) * TH;
+    // ==== priority set-up ====
     //   Wave priority against the age order (MULTI, launches whose groups all run at once).  A CU holds two of
     // these workgroups, and its instruction arbiters serve the older wave first: the workgroup dispatched second to a
     // CU -- index >= the number of CUs: the dispatcher gives every CU one workgroup before any gets its second --
@@ -713,18 +896,12 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
     const uint32_t dskip = MRX_BVH_DIAG ? p.debugSkip : 0u;
     if (dskip & 16u)
         return;                                       // timing aid: bare launch
-    // Diagnostics (in-kernel stamps, MRX_DEBUG_STAMPS=1; phases switched off, MRX_DEBUG_SKIP)
-    // exist only in a build with -DMRX_BVH_DIAG=1 (scripts/ab_build.sh diag -DMRX_BVH_DIAG=1):
-    // the flags and the stamp pointer cost scalar registers in loops that have none to spare.
+    // (diagnostics: MRX_STAMP above)
     unsigned long long *stamps = (MRX_BVH_DIAG && p.debugStamps && wave < 4)
         ? p.debugStamps + ((size_t)blockIdx.x * 4 + wave) * 8 : nullptr;
-#define MRX_STAMP(i)                                                           \
-    do {                                                                       \
-        if (MRX_BVH_DIAG && stamps && lane == 0)                               \
-            stamps[i] = __builtin_amdgcn_s_memrealtime();                      \
-    } while (0)
     MRX_STAMP(0);
 
+    // ==== LDS carve-up ====
     // ---- LDS: depth buffer of the tile, shading records of the pass, control
     //      words, the TLAS of the pass, per-wave scratch
     unsigned long long *zbuf = reinterpret_cast<unsigned long long *>(smem);           // [TH][TW]
@@ -739,9 +916,6 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
     // dwords), [passInst][24] records, [passInst] rectangles; p.bvhGroupViews of them
     // (every address below is the current view's block + a multiple of passInst: one loop-carried scalar)
     float *instRec = reinterpret_cast<float *>(ws - wave + kBvhWaves) + 4;
-#define MRX_TLAS_DW (passInst * (kInstRecDw + 4u) + 4u)
-#define MRX_INST_RECT(rec) reinterpret_cast<float4 *>((rec) + (size_t)passInst * kInstRecDw)
-#define MRX_TLAS_HDR(rec) ((rec) - 4)
 
     // ---- view constants (wave-uniform).  Two placements, picked by what measured faster:
     //      the plain untextured instantiations work them out in every wave, here; the others
@@ -771,22 +945,8 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
     float TY0 = (float)tileY0, TY1 = (float)(tileY0 + TH - 1);
     const int smallArea = p.bvhSmallArea;
 
-    {
-        // the waves that have instances to transform in the first pass go straight to their
-        // pose loads: the others clear the depth buffer for them
-        // (groups of views: the waves that may have instances to transform, by the largest world)
-        const uint32_t n0 = MULTI ? (p.bvhUniInst ? min(passInst, p.bvhUniInst) : passInst)
-                                  : (i1 > i0 ? min(passInst, i1 - i0) : 0u);
-        const uint32_t busy = min(((n0 + kWave - 1u) / kWave) << vShift, (uint32_t)kBvhWaves);
-        if (busy >= (uint32_t)kBvhWaves) {
-            for (int i = threadIdx.x; i < ZS * TH; i += kWave * kBvhWaves)
-                zbuf[i] = packHit(invFar, 0u);
-        } else if ((uint32_t)wave >= busy) {
-            for (uint32_t i = ((uint32_t)wave - busy) * kWave + (uint32_t)lane; i < (uint32_t)(ZS * TH);
-                 i += ((uint32_t)kBvhWaves - busy) * kWave)
-                zbuf[i] = packHit(invFar, 0u);
-        }
-    }
+    // ==== first clear of the depth buffer (clearDepthFirst), and of the counters ====
+    clearDepthFirst<TW, TH, MULTI>(p, zbuf, i0, i1, passInst, vShift, invFar, wave, lane);
     if (threadIdx.x == 0)
         ctrl[0] = ctrl[1] = ctrl[2] = ctrl[3] = ctrl[4] = ctrl[6] = 0u;   // records / done waves / large triangles;
                                                       // [4], [6]: records / large triangles of odd rounds;
@@ -814,6 +974,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                 ctrl[doneIdx] = 0u;  // done waves (every wave has read the last pass's count by now); the record and
                                   // large-triangle counters of the coming round were set at the end of the last one
         }
+        // ==== TLAS pass ====
         // ---- phase I: the TLAS of this pass, in LDS.  Lane = instance: its transform
         //      (S2/S3), the S6b quantities, and the padded screen rectangle of the bounding
         //      SPHERE of its object's box -- one wave's worth of work for 64 instances.
@@ -827,7 +988,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
         //      (only the waves that have instances to transform work out the view constants; the wave
         //      with the view's first chunk always does, and leaves the light direction in LDS)
         ViewConst vc = vcAll;
-        float *const myRec = instRec + (size_t)tI * MRX_TLAS_DW;
+        float *const myRec = instRec + (size_t)tI * tlasDwords(passInst);
         if (kLvInLds && ch0 * kWave < nI)
             loadViewConst<PV>(p, myView, vc);
         if (PV && MULTI) {
@@ -846,17 +1007,17 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
         // instance loads are even issued)
         if (kLvInLds && ch0 == 0 && lane == 0) {
             if (nI != 0)
-                *reinterpret_cast<float4 *>(MRX_TLAS_HDR(myRec)) =
+                *reinterpret_cast<float4 *>(tlasHeader(myRec)) =
                     make_float4(vc.lv[0], vc.lv[1], vc.lv[2], __uint_as_float(nI));
             else
-                MRX_TLAS_HDR(myRec)[3] = __uint_as_float(0u);   // (no instances: only the count is read)
+                tlasHeader(myRec)[3] = __uint_as_float(0u);   // (no instances: only the count is read)
         }
         __syncthreads();
         MRX_STAMP(1);
 
         for (;;) {                                    // the tiles of the group (one, unless the world fits one pass)
         if (MULTI)
-            n = rflu(__float_as_uint(MRX_TLAS_HDR(instRec)[3]));   // (the instances of this tile's view)
+            n = rflu(__float_as_uint(tlasHeader(instRec)[3]));   // (the instances of this tile's view)
         // ---- phase II: geometry.  The waves split the work by instance: flat
         //      objects round-robin, the eight children of a BLAS root one per
         //      wave.  All control flow of a wave is wave-uniform.
@@ -871,6 +1032,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
             // -- produce until this wave's share is exhausted or the record table is full
             bool tableFull = false;
             while (!tableFull) {
+                // ==== traversal step: stack pop / next instance / next TLAS chunk, until a batch is queued ====
                 while (qCount < (uint32_t)kWave && !done) {
                     if (sp > 0) {
                         --sp;
@@ -948,7 +1110,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     } else if (chunk < numChunks) {
                         // next 64 instances of the TLAS: lane = instance
                         const uint32_t li = chunk * kWave + lane;
-                        const float4 ir = MRX_INST_RECT(instRec)[li < n ? li : 0u];
+                        const float4 ir = tlasRects(instRec, passInst)[li < n ? li : 0u];
                         const float4 oi = *reinterpret_cast<const float4 *>(
                             instRec + (size_t)(li < n ? li : 0u) * kInstRecDw + 20);
                         Rect r;
@@ -972,6 +1134,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                 }
                 waveLdsSync();                        // the queue entries written above are read below
 
+                // ==== leaf set-up of a batch ====
                 // -- a batch of up to 64 candidates.  Leaf test setup, lane = triangle:
                 //    S3-S7 with the instance's transform from the TLAS record.
                 const uint32_t nb = qCount < (uint32_t)kWave ? qCount : (uint32_t)kWave;
@@ -1003,7 +1166,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     // costs scalar spills in every loop below)
                     float4 lv4 = make_float4(vcAll.lv[0], vcAll.lv[1], vcAll.lv[2], 0.0f);
                     if (kLvInLds)
-                        lv4 = *reinterpret_cast<const float4 *>(MRX_TLAS_HDR(instRec));
+                        lv4 = *reinterpret_cast<const float4 *>(tlasHeader(instRec));
                     const float lv[3] = { lv4.x, lv4.y, lv4.z };
                     // (what the set-up reads of the kernel's parameters, fetched per batch from the
                     // kernel-argument segment instead of living in scalar registers: see ResolveArgs)
@@ -1021,16 +1184,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     if (PV && !(NRM && MAT)) {
                         const uint32_t *colors = pk->instColor;
                         if (colors) {
-                            uint32_t rowBase = passBase;
-                            if (MULTI) {
-                                // (viewInstances of `view`, from the argument segment)
-                                const uint32_t uni = pk->bvhUniInst, cams = pk->bvhUniCams;
-                                if (uni)
-                                    rowBase = (cams != 1u ? view / cams : view) * uni;
-                                else
-                                    rowBase = pk->worldInstStart[pk->viewWorld[view]];
-                            }
-                            icol = colors[rowBase + e.x];
+                            icol = colors[rowBaseOfView<MULTI>(pk, passBase, view) + e.x];
                         }
                     }
                     bool valid;
@@ -1041,14 +1195,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                         const auto matOf = [&]() -> MatOverride {
                             KernargParams pm = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
                             asm volatile("" : "+s"(pm));
-                            uint32_t rowBase = passBase;
-                            if (MULTI) {
-                                const uint32_t uni = pm->bvhUniInst, cams = pm->bvhUniCams;
-                                if (uni)
-                                    rowBase = (cams != 1u ? view / cams : view) * uni;
-                                else
-                                    rowBase = pm->worldInstStart[pm->viewWorld[view]];
-                            }
+                            const uint32_t rowBase = rowBaseOfView<MULTI>(pm, passBase, view);
                             const int32_t *ids = pm->instMat;
                             uint32_t numMats = pm->numMaterials;
                             if (NRM) {
@@ -1084,14 +1231,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     if (PV && IDS == 2) {
                         KernargParams pl = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
                         asm volatile("" : "+s"(pl));
-                        uint32_t rowBase = passBase;
-                        if (MULTI) {
-                            const uint32_t uni = pl->bvhUniInst, cams = pl->bvhUniCams;
-                            if (uni)
-                                rowBase = (cams != 1u ? view / cams : view) * uni;
-                            else
-                                rowBase = pl->worldInstStart[pl->viewWorld[view]];
-                        }
+                        const uint32_t rowBase = rowBaseOfView<MULTI>(pl, passBase, view);
                         const int32_t *labels = pl->instLabel;
                         const int32_t lab = (labels ? labels : pl->instObj)[rowBase + ws->queue[lane].x];
                         shade[2] = (labels && lab != kLabelObject) ? __int_as_float(lab) : shade[2];
@@ -1110,6 +1250,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     const float itMin = __builtin_fmaf(c.Dx, c.Dx >= 0.0f ? TX0 : TX1, __builtin_fmaf(c.Dy, c.Dy >= 0.0f ? TY0 : TY1, c.Dc));
                     live = live && fminf(fminf(eMax0, eMax1), eMax2) >= 0.0f && itMax > invFar && itMin <= invNear;
                 }
+                // ==== slot reservation, with the partial-batch rule ====
                 // -- shading records only for triangles that can own a pixel of the tile
                 //    (about half the candidates are back faces): slots by rank among them
                 const uint64_t liveMask = __ballot(live);
@@ -1141,21 +1282,14 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     if (TEX && NRM)
                         tileNormalTab<TEX, TW, TH, CLS, MULTI>(smem)[slot] = nrmv;
                     if (!TEX)
-                        shadeTab[slot] = make_float4(shade[0],
-                                                     NRM ? __uint_as_float(nrmv)
-                                                         : shade[1],
-                                                     shade[2], __uint_as_float(kTri));   // [2]: the triangle's object id
-                    else if (__float_as_int(shade[1]) < 0) {
-                        // an untextured triangle of a textured scene: packed colour, "no texture", object id
-                        float *dst = coldTab[slot];
-                        dst[0] = shade[0];
-                        *reinterpret_cast<float2 *>(dst + 10) = make_float2(__uint_as_float(0u), shade[2]);
-                    }
+                        writeRecord<NRM>(shadeTab, slot, shade, nrmv, __uint_as_float(kTri));
+                    else if (__float_as_int(shade[1]) < 0)
+                        writeUntexturedRecord(coldTab, slot, shade);
                     if (TEX && __float_as_int(shade[1]) >= 0) {
-                        // the u/v planes from the edge planes, the texture coordinates (read again:
-                        // L1 / L2 hits) and |1/d|; the texture's descriptor rides with the material
                         KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
                         asm volatile("" : "+s"(pk));
+                        // the u/v planes from the edge planes, the texture coordinates (read again:
+                        // L1 / L2 hits) and |1/d|; the texture's descriptor rides with the material
                         const float4 *tsrc = reinterpret_cast<const float4 *>(pk->tris + triL);
                         const float4 t2 = tsrc[2], t3 = tsrc[3];
                         // (a renderer with the material column: the record's texture may be an overriding material's,
@@ -1172,75 +1306,21 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     }
                 }
                 if (dskip & 128u) MRX_STAMP(3);
-                // pixel range of the triangle inside the tile: the conservative box
-                // of setup, less all but 1/32 of its one-pixel margin
-                const float kTrim = 0.96875f;
-                const float fx0 = ceilf(fmaxf(c.bbX0 + kTrim, TX0)), fx1 = floorf(fminf(c.bbX1 - kTrim, TX1));
-                const float fy0 = ceilf(fmaxf(c.bbY0 + kTrim, TY0)), fy1 = floorf(fminf(c.bbY1 - kTrim, TY1));
-                live = live && fx0 <= fx1 && fy0 <= fy1;
-                const int ix0 = live ? (int)fx0 : 0, iy0 = live ? (int)fy0 : 0;
-                const int bw = live ? (int)fx1 - ix0 + 1 : 0, bh = live ? (int)fy1 - iy0 + 1 : 0;
+                // pixel range of the triangle inside the tile (trimBox above)
+                const TrimmedBox tb = trimBox(c, TX0, TX1, TY0, TY1);
+                live = live && tb.x0 <= tb.x1 && tb.y0 <= tb.y1;
+                const int ix0 = live ? (int)tb.x0 : 0, iy0 = live ? (int)tb.y0 : 0;
+                const int bw = live ? (int)tb.x1 - ix0 + 1 : 0, bh = live ? (int)tb.y1 - iy0 + 1 : 0;
                 const int area = bw * bh;
                 const bool small = live && area <= smallArea;
                 const bool big = live && !small;
                 bool listFull = false;
                 if (!(dskip & 2u)) {
-                    // -- small triangles, by (triangle, row of its box): the rows of all the
-                    //    batch's small triangles are numbered through (prefix sum over the
-                    //    lanes) and dealt 64 at a time, a lane fetches the planes of its row's
-                    //    triangle from the lane that set it up (ds_bpermute) and walks the row
-                    //    four pixels per step -- every lane has a row, however uneven the boxes
-                    {
-                        const int rowsMine = (small && !(dskip & 32u)) ? bh : 0;
-                        const int incl = waveInclusiveSum(rowsMine);
-                        const int total = __builtin_amdgcn_readlane(incl, kWave - 1);
-                        const int packedBox = ix0 | (bw << 16);        // (both < 2^15)
-                        for (int item0 = 0; item0 < total; item0 += kWave) {
-                            const int j = item0 + lane;
-                            const bool act = j < total;
-                            // the lane t whose rows hold item j: smallest t with incl[t] > j
-                            int t = 0;
-#pragma unroll
-                            for (int step = kWave / 2; step >= 1; step >>= 1) {
-                                const int probe = __builtin_amdgcn_ds_bpermute((t + step - 1) << 2, incl);
-                                t += probe <= j ? step : 0;
-                            }
-                            t = act ? t : 0;
-                            const int src = t << 2;
-                            const int inclT = __builtin_amdgcn_ds_bpermute(src, incl);
-                            const int rowsT = __builtin_amdgcn_ds_bpermute(src, rowsMine);
-                            const int boxT = __builtin_amdgcn_ds_bpermute(src, packedBox);
-                            const int y0T = __builtin_amdgcn_ds_bpermute(src, iy0);
-                            const uint32_t lowT = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)lowKey);
-#define MRX_GATHER(v) __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v)))
-                            const f32x2 A01 = { MRX_GATHER(c.A0), MRX_GATHER(c.A1) }, A2D = { MRX_GATHER(c.A2), MRX_GATHER(c.Dx) };
-                            const f32x2 B01 = { MRX_GATHER(c.B0), MRX_GATHER(c.B1) }, B2D = { MRX_GATHER(c.B2), MRX_GATHER(c.Dy) };
-                            const f32x2 C01 = { MRX_GATHER(c.C0), MRX_GATHER(c.C1) }, C2D = { MRX_GATHER(c.C2), MRX_GATHER(c.Dc) };
-#undef MRX_GATHER
-                            const int xBeg = boxT & 0xFFFF, xEnd = xBeg + (boxT >> 16);
-                            const int sy = y0T + (j - (inclT - rowsT));
-                            const float py = (float)sy;
-                            const f32x2 yy = { py, py };
-                            const f32x2 r01 = fma2(B01, yy, C01);
-                            const f32x2 r2d = fma2(B2D, yy, C2D);
-                            unsigned long long *zline = zbuf + (sy - (int)tileY0) * ZS - (int)tileX0;
-                            for (int sx = xBeg; __ballot(act && sx < xEnd) != 0; sx += 4) {
-                                if (act && sx < xEnd) {
-#pragma unroll
-                                    for (int q4 = 0; q4 < 4; ++q4) {
-                                        const float px = (float)(sx + q4);
-                                        const f32x2 pp = { px, px };
-                                        const f32x2 e01 = fma2(A01, pp, r01);
-                                        const f32x2 e2d = fma2(A2D, pp, r2d);
-                                        if (sx + q4 < xEnd && fminf(fminf(e01.x, e01.y), e2d.x) >= 0.0f &&
-                                            e2d.y > invFar && e2d.y <= invNear)
-                                            atomicMax(zline + sx + q4, packHit(e2d.y, lowT));
-                                    }
-                                }
-                            }
-                        }
-                    }
+                    // ==== small walk: by (triangle, row of its box), in the wave that set them up (walkSmallRows) ====
+                    walkSmallRows<ZS>(c, (small && !(dskip & 32u)) ? bh : 0, ix0, bw, iy0, lowKey, 0, kWave, zbuf, tileX0,
+                                      tileY0, invFar, invNear, lane);
                     if (dskip & 128u) MRX_STAMP(4);
+                    // ==== large-list append, with the list-full rule ====
                     // -- large triangles go on the tile's shared list: after the barrier all
                     //    eight waves rasterise them, each its own strip
                     const uint64_t bigMask = __ballot(big && !(dskip & 64u));
@@ -1256,9 +1336,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                         if (bigBase + (uint32_t)numBig <= (uint32_t)kBigCap) {
                             if ((bigMask >> lane) & 1ull) {
                                 float4 *dst = reinterpret_cast<float4 *>(bigList[bigBase + rank]);
-                                dst[0] = make_float4(c.A0, c.A1, c.A2, c.Dx);
-                                dst[1] = make_float4(c.B0, c.B1, c.B2, c.Dy);
-                                dst[2] = make_float4(c.C0, c.C1, c.C2, c.Dc);
+                                packPlanes(dst, c);
                                 dst[3] = make_float4(__uint_as_float(lowKey), __uint_as_float(boxXY), 0.f, 0.f);
                             }
                         } else {
@@ -1281,7 +1359,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                     tableFull = true;
                     break;
                 }
-                // -- what did not fit the batch (or the record table) moves to the front of the queue
+                // ==== queue compaction: what did not fit the batch (or the record table) moves to the front ====
                 if (qCount > (uint32_t)kWave || (kPartial && defMask != 0)) {
                     const uint32_t rem = qCount > (uint32_t)kWave ? qCount - kWave : 0u;
                     const uint32_t numDef = (uint32_t)__builtin_popcountll(defMask);
@@ -1310,19 +1388,9 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
             if (dskip & 128u) MRX_STAMP(5); else MRX_STAMP(2);
             __syncthreads();
             if (!(dskip & 128u)) MRX_STAMP(3);
-            if (!MULTI || left == 1) {
-                // (the priority of a younger workgroup with one view ends here -- of one with two, where it turns to its
-                // second; read from the argument block: no register held for it)
-                KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
-                asm volatile("" : "+s"(pk));
-                if (((pk->bvhGroupViews >> 17) & 7u) >= 2u)
-                    __builtin_amdgcn_s_setprio(0);
-            }
-            // -- the round's large triangles: wave = strip, lane = entry for the box
-            //    test, then four pixels of the lane per 32-pixel half.  From here to the
-            //    end of the round a wave touches only the pixels of its own strip (the
-            //    small-triangle walks ended at the barrier), so no barrier separates this
-            //    pass from the resolve below.
+            if (!MULTI || left == 1)
+                endYoungPriority();
+            // ==== round bookkeeping ====
             const bool allDone = rflu(ctrl[doneIdx]) == (uint32_t)kBvhWaves;
             // The record table lives on from round to round and from pass to pass until it is
             // full (records are per triangle, not per TLAS pass): only then are the round's
@@ -1344,6 +1412,12 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                 if (allDone && lastPass)
                     ctrl[doneIdx ^ 2u] = 0u;
             }
+            // ==== large pass ====
+            // -- the round's large triangles: wave = strip, lane = entry for the box
+            //    test, then four pixels of the lane per 32-pixel half.  From here to the
+            //    end of the round a wave touches only the pixels of its own strip (the
+            //    small-triangle walks ended at the barrier), so no barrier separates this
+            //    pass from the resolve below.
             {
                 const uint32_t listed = min(rflu(ctrl[2 + par]), (uint32_t)kBigCap);
                 for (uint32_t e0 = 0; e0 < listed; e0 += kWave) {
@@ -1417,6 +1491,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
                 }
             }
             if (!(dskip & 128u)) MRX_STAMP(4);
+            // ==== resolve ====
             // -- resolve (resolveStrip above).  The tile's last round -- this wave and all others
             //    done, no further pass -- leaves the loops and resolves + outputs in one go below;
             //    a round that filled the record table stashes its winners in the tensors, because
@@ -1424,11 +1499,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
             if (allDone && lastPass)
                 break;
             if (tableReset) {
-                // (the kernel's only argument sits at offset 0 of the kernel-argument segment)
-                KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
-                asm volatile("" : "+s"(pk));
-                const ResolveArgs ra = { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough,
-                                         NRM ? pk->normal : nullptr };
+                const ResolveArgs ra = resolveArgsOfLaunch<NRM>();
                 resolveStrip<IDS, TEX, TW, TH, false, ZS, kOutByPointer, NRM>(
                     ra, zbuf, shadeTab, coldTab, view, tileX0, tileY0, wave, lane,
                     (TEX && NRM) ? tileNormalTab<TEX, TW, TH, CLS, MULTI>(smem) : nullptr);
@@ -1446,16 +1517,14 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
         //      16-byte store per tensor and half
         if (!(dskip & 1u)) {
             if (!(dskip & 128u)) MRX_STAMP(5);
-            KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
-            asm volatile("" : "+s"(pk));
-            const ResolveArgs ra = { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough,
-                                     NRM ? pk->normal : nullptr };
+            const ResolveArgs ra = resolveArgsOfLaunch<NRM>();
             resolveStrip<IDS, TEX, TW, TH, true, ZS, kOutByPointer, NRM>(
                 ra, zbuf, shadeTab, coldTab, view, tileX0, tileY0, wave, lane,
                 (TEX && NRM) ? tileNormalTab<TEX, TW, TH, CLS, MULTI>(smem) : nullptr);
         }
         if (--left == 0)
             break;
+        // ==== next tile / next view ====
         // ---- the next tile of the group: this wave's strip of the depth buffer is cleared (nobody else
         //      touches it between the barrier ahead of the large pass and the one below), the rectangle
         //      moves on, the traversal state starts over; the TLAS, the view constants and the light
@@ -1465,7 +1534,7 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
         if (MULTI) {
             // the next view of the group: its TLAS is the next block (and its projection, per-view form)
             ++view;
-            instRec += MRX_TLAS_DW;
+            instRec += tlasDwords(passInst);
             if (PV) {
                 pr = viewProjOf(p, true, view);
                 isx = __builtin_amdgcn_rcpf(pr.sx);
@@ -1497,10 +1566,6 @@ __device__ __forceinline__ void tileKernelBody(const RasterParams p)
     if (MRX_BVH_DIAG && stamps && lane == 0)     // where this wave ran: HW_ID (reg 4) and XCC_ID (reg 20)
         stamps[7] = ((unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 20) << 32) |
                     (unsigned long long)__builtin_amdgcn_s_getreg((31 << 11) | 4);
-#undef MRX_STAMP
-#undef MRX_TLAS_DW
-#undef MRX_INST_RECT
-#undef MRX_TLAS_HDR
 }
 
 // May a form of the tile kernel be instantiated with CLS?  Every one but the per-view normals form of a textured scene
@@ -1631,11 +1696,6 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
 
     unsigned long long *stamps = (MRX_BVH_DIAG && p.debugStamps && wave < 4)
         ? p.debugStamps + ((size_t)blockIdx.x * 4 + wave) * 8 : nullptr;
-#define MRX_STAMP(i)                                                           \
-    do {                                                                       \
-        if (MRX_BVH_DIAG && stamps && lane == 0)                               \
-            stamps[i] = __builtin_amdgcn_s_memrealtime();                      \
-    } while (0)
     MRX_STAMP(0);
     const ViewProj pr = viewProjOf(p, PV, view);
     const float invNear = PV ? pr.invNear : p.invNear, invFar = p.invFar;
@@ -1682,12 +1742,7 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
             InstXform x;
             instanceTransform(p, vc, row, x);
             if (hasI) {
-                float4 *dst = reinterpret_cast<float4 *>(instRec + (size_t)lane * kInstRecDw);
-                dst[0] = make_float4(x.MV[0][0], x.MV[0][1], x.MV[0][2], x.MV[1][0]);
-                dst[1] = make_float4(x.MV[1][1], x.MV[1][2], x.MV[2][0], x.MV[2][1]);
-                dst[2] = make_float4(x.MV[2][2], x.tv[0], x.tv[1], x.tv[2]);
-                dst[3] = make_float4(x.qo[0], x.qo[1], x.qo[2], x.det);
-                dst[4] = make_float4(x.sc[0], x.sc[1], x.sc[2], __int_as_float(obj));
+                packInstRecord(reinterpret_cast<float4 *>(instRec + (size_t)lane * kInstRecDw), x, obj);
                 firstI = __float_as_uint(o0.x);
                 numI = __float_as_uint(o0.y);
             }
@@ -1751,12 +1806,9 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
                 nrmTab[lane + 1] = nrmv;
             const bool texRec = OUT != kOutDepth && valid && __float_as_int(shade[1]) >= 0;
             if (!TEX)
-                shadeTab[lane + 1] = make_float4(shade[0], NRM ? __uint_as_float(nrmv) : shade[1], shade[2], __int_as_float(lane));
-            else if (!texRec) {
-                float *dst = coldTab[lane + 1];
-                dst[0] = shade[0];
-                *reinterpret_cast<float2 *>(dst + 10) = make_float2(__uint_as_float(0u), shade[2]);
-            }
+                writeRecord<NRM>(shadeTab, lane + 1, shade, nrmv, __int_as_float(lane));
+            else if (!texRec)
+                writeUntexturedRecord(coldTab, lane + 1, shade);
             if (TEX && texRec) {
                 // (u/v planes as the general kernel derives them: uvPlanes() from the edge planes and |1/d|)
                 const float4 *tsrc = reinterpret_cast<const float4 *>(p.tris + myTri);
@@ -1777,9 +1829,7 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
             // a triangle that cannot own a pixel gets a box nothing meets
             const float inf = __builtin_inff();
             float4 *dst = reinterpret_cast<float4 *>(triRec[lane]);
-            dst[0] = make_float4(c.A0, c.A1, c.A2, c.Dx);
-            dst[1] = make_float4(c.B0, c.B1, c.B2, c.Dy);
-            dst[2] = make_float4(c.C0, c.C1, c.C2, c.Dc);
+            packPlanes(dst, c);
             dst[3] = valid ? make_float4(c.bbX0, c.bbX1, c.bbY0, c.bbY1) : make_float4(inf, -inf, inf, -inf);
         }
     }
@@ -1819,12 +1869,10 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
             const float itMin = __builtin_fmaf(c.Dx, c.Dx >= 0.0f ? TX0 : TX1, __builtin_fmaf(c.Dy, c.Dy >= 0.0f ? TY0 : TY1, c.Dc));
             live = live && fminf(fminf(eMax0, eMax1), eMax2) >= 0.0f && itMax > invFar && itMin <= invNear;
         }
-        const float kTrim = 0.96875f;
-        const float fx0 = ceilf(fmaxf(c.bbX0 + kTrim, TX0)), fx1 = floorf(fminf(c.bbX1 - kTrim, TX1));
-        const float fy0 = ceilf(fmaxf(c.bbY0 + kTrim, TY0)), fy1 = floorf(fminf(c.bbY1 - kTrim, TY1));
-        live = live && fx0 <= fx1 && fy0 <= fy1;
-        const int jx0 = live ? (int)fx0 - (int)gx0 : 0, jy0 = live ? (int)fy0 - (int)gy0 : 0;
-        const int jw = live ? (int)fx1 - (int)fx0 : 0, jh = live ? (int)fy1 - (int)fy0 : 0;       // size - 1
+        const TrimmedBox tb = trimBox(c, TX0, TX1, TY0, TY1);
+        live = live && tb.x0 <= tb.x1 && tb.y0 <= tb.y1;
+        const int jx0 = live ? (int)tb.x0 - (int)gx0 : 0, jy0 = live ? (int)tb.y0 - (int)gy0 : 0;
+        const int jw = live ? (int)tb.x1 - (int)tb.x0 : 0, jh = live ? (int)tb.y1 - (int)tb.y0 : 0;       // size - 1
         const bool sm = (jw + 1) * (jh + 1) <= smallArea;
         return live ? ((uint32_t)jx0 | ((uint32_t)jw << 6) | ((uint32_t)jy0 << 12) | ((uint32_t)jh << 18) |
                        (sm ? 1u << 24 : 0u) | (1u << 25)) : 0u;
@@ -1848,55 +1896,8 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
         const bool small = live && ((cls >> 24) & 1u) != 0u;
         const bool big = live && !small;
         // ---- small triangles by (triangle, row of its box), the items dealt over waves and lanes
-        {
-            const int rowsMine = small ? bh : 0;
-            const int incl = waveInclusiveSum(rowsMine);
-            const int total = __builtin_amdgcn_readlane(incl, kWave - 1);
-            const int packedBox = ix0 | (bw << 16);
-            for (int item0 = wave * kWave; item0 < total; item0 += kWaves * kWave) {
-                const int j = item0 + lane;
-                const bool act = j < total;
-                int t = 0;
-#pragma unroll
-                for (int step = kWave / 2; step >= 1; step >>= 1) {
-                    const int probe = __builtin_amdgcn_ds_bpermute((t + step - 1) << 2, incl);
-                    t += probe <= j ? step : 0;
-                }
-                t = act ? t : 0;
-                const int src = t << 2;
-                const int inclT = __builtin_amdgcn_ds_bpermute(src, incl);
-                const int rowsT = __builtin_amdgcn_ds_bpermute(src, rowsMine);
-                const int boxT = __builtin_amdgcn_ds_bpermute(src, packedBox);
-                const int y0T = __builtin_amdgcn_ds_bpermute(src, iy0);
-                const uint32_t lowT = (uint32_t)__builtin_amdgcn_ds_bpermute(src, (int)lowKey);
-#define MRX_GATHER(v) __int_as_float(__builtin_amdgcn_ds_bpermute(src, __float_as_int(v)))
-                const f32x2 A01 = { MRX_GATHER(c.A0), MRX_GATHER(c.A1) }, A2D = { MRX_GATHER(c.A2), MRX_GATHER(c.Dx) };
-                const f32x2 B01 = { MRX_GATHER(c.B0), MRX_GATHER(c.B1) }, B2D = { MRX_GATHER(c.B2), MRX_GATHER(c.Dy) };
-                const f32x2 C01 = { MRX_GATHER(c.C0), MRX_GATHER(c.C1) }, C2D = { MRX_GATHER(c.C2), MRX_GATHER(c.Dc) };
-#undef MRX_GATHER
-                const int xBeg = boxT & 0xFFFF, xEnd = xBeg + (boxT >> 16);
-                const int sy = y0T + (j - (inclT - rowsT));
-                const float py = (float)sy;
-                const f32x2 yy = { py, py };
-                const f32x2 r01 = fma2(B01, yy, C01);
-                const f32x2 r2d = fma2(B2D, yy, C2D);
-                unsigned long long *zline = zb + (sy - (int)tileY0) * kFlatZS - (int)tileX0;
-                for (int sx = xBeg; __ballot(act && sx < xEnd) != 0; sx += 4) {
-                    if (act && sx < xEnd) {
-#pragma unroll
-                        for (int q4 = 0; q4 < 4; ++q4) {
-                            const float px = (float)(sx + q4);
-                            const f32x2 pp = { px, px };
-                            const f32x2 e01 = fma2(A01, pp, r01);
-                            const f32x2 e2d = fma2(A2D, pp, r2d);
-                            if (sx + q4 < xEnd && fminf(fminf(e01.x, e01.y), e2d.x) >= 0.0f &&
-                                e2d.y > invFar && e2d.y <= invNear)
-                                atomicMax(zline + sx + q4, packHit(e2d.y, lowT));
-                        }
-                    }
-                }
-            }
-        }
+        walkSmallRows<kFlatZS>(c, small ? bh : 0, ix0, bw, iy0, lowKey, wave * kWave, kWaves * kWave, zb, tileX0, tileY0,
+                               invFar, invNear, lane);
         MRX_STAMP(2);
         // ---- large triangles: this wave's strip, each 32x8 half after the exact test of the
         //      triangle's planes at the half's most favourable corner pixel (lane = triangle)
@@ -1947,10 +1948,7 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
         __syncthreads();                              // every walk into this tile's buffer is done
         MRX_STAMP(4);
         {
-            KernargParams pk = (KernargParams)__builtin_amdgcn_kernarg_segment_ptr();
-            asm volatile("" : "+s"(pk));
-            const ResolveArgs ra = { pk->rgb, pk->depth, pk->ids, pk->texels, pk->nfast, pk->nslow, pk->writeThrough,
-                                     NRM ? pk->normal : nullptr };
+            const ResolveArgs ra = resolveArgsOfLaunch<NRM>();
             resolveStrip<IDS, TEX, TW, TH, true, kFlatZS, OUT, NRM, false>(ra, zb, shadeTab, coldTab, view, tileX0, tileY0, wave, lane,
                                                                     (TEX && NRM) ? nrmTab : nullptr);
         }
@@ -1968,7 +1966,6 @@ __device__ __forceinline__ void flatKernelBody(const RasterParams p)
         ++g;
     }
     MRX_STAMP(6);
-#undef MRX_STAMP
 }
 
 // launch bounds of the flat kernels, uniform and form alike
