@@ -391,7 +391,22 @@ enum {
      * the instance the pixel's visibility id belongs to and a change of projection all count.  An allocation of its
      * own, one per shard; it has no sample tensor. */
     MRX_BUF_FLOW = 22,
-    MRX_NUM_BUFFERS_EXT8 = 23
+    MRX_NUM_BUFFERS_EXT8 = 23,
+    /* The point-cloud output (mrx_cloud_create); all three need it and are per shard, like the
+     * other outputs; none has a sample tensor.
+     * f32 [views,N,4]: slot k of view v is the point (x, y, z, 1) of one valid pixel of the view -- bit for bit what
+     * MRX_BUF_POSITION holds at that pixel in the chosen frame -- or (0, 0, 0, 0) where the slot is empty.  A pixel is
+     * valid where its depth d, in the depth tensor the caller sees, has d > 0 and, with a max_depth, d <= max_depth (a
+     * NaN is not).  With M valid pixels, ranked in storage order (Raytracer mode: [x][y], column-major in image terms),
+     * slot k takes the pixel of rank floor(k * M / N) where M >= N, rank k where k < M < N, and is empty where k >= M:
+     * an even thinning that keeps storage order, the same from run to run. */
+    MRX_BUF_CLOUD = 23,
+    /* i32 [views,N]: y * W + x of the slot's pixel in image coordinates in both modes (Raytracer: W = res, the stage
+     * undoes the transposition) -- what a caller gathers rgb, labels or normals with -- and -1 in an empty slot. */
+    MRX_BUF_CLOUD_PIXEL = 24,
+    /* i32 [views]: M, the valid pixels of the view -- not min(M, N). */
+    MRX_BUF_CLOUD_COUNT = 25,
+    MRX_NUM_BUFFERS_EXT9 = 26
 };
 
 enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2, MRX_DTYPE_F16 = 3, MRX_DTYPE_BF16 = 4 };
@@ -550,6 +565,38 @@ int mrx_flow_host(const float *depth, const int32_t *ids, uint32_t views, uint32
                   const uint32_t *inst_kbase, const uint32_t *world_inst_start, const uint32_t *view_world,
                   uint32_t num_worlds, uint32_t num_instances, const float *const live[5], const float *const prev[5],
                   uint32_t pass_rows, float *out_flow);
+
+/* -- point-cloud output.  Attached after creation, as the sensor and the flow are:
+ *    mrx_cloud_create(r, N, frame, max_depth) allocates MRX_BUF_CLOUD, MRX_BUF_CLOUD_PIXEL and MRX_BUF_CLOUD_COUNT for N
+ *    points per view, 1 ... 65536 with views * N < 2^31, runs the stage once and waits.  frame is 1 for world space and
+ *    2 for view space, mrx_positions' values; max_depth is 0 for none, otherwise finite and > 0: pixels farther away
+ *    are dropped.  From then on mrx_step / mrx_render / mrx_time_renders enqueue the compaction stage last on the
+ *    render's stream, behind every other stage; bytes_per_step grows by 4 per native pixel and N * 20 + 4 per view.
+ *    MRX_E_INVALID for a null renderer, a shard, a second call, N out of range, views * N at 2^31 or more, another
+ *    frame, another max_depth, a renderer without depth (MRX_FLAG_NO_DEPTH), more than 2^32 - 1 native pixels or more
+ *    than 2^31 - 1 in one view; on a renderer of several shards it fans out, all or nothing.  MRX_CLOUD_PARTS=n in the
+ *    environment at that call splits every view over n workgroups (tests; the result does not depend on it).
+ *    mrx_cloud returns N, or 0 without the output; MRX_E_INVALID for a null renderer.  mrx_compact enqueues the stage
+ *    alone on the renderer's stream (every shard's on its own), as mrx_unproject does: what a caller that wrote depth, a
+ *    camera pose or a projection itself, or timed the stage, calls.  MRX_E_UNSUPPORTED without the output.
+ *    mrx_cloud_plan is host arithmetic, for tests: the answer of the stage's launch checks for `views` views of nslow
+ *    rows of nfast pixels and n points on num_cus compute units (null_pointers != 0: with null tensors; forced_parts:
+ *    MRX_CLOUD_PARTS, 0 = the automatic rule) -- MRX_E_INVALID where the launch would be refused, otherwise the number
+ *    of workgroups (0: nothing is enqueued), and out[0 ... 2], when not null, = workgroups per view, LDS bytes of a
+ *    workgroup, 1 where the slot rule runs in 64 bits (nfast * nslow * n reaches 2^32).  It touches no device.
+ *    mrx_cloud_host runs the stage's source on the CPU, part by part and segment by segment as the kernels walk them,
+ *    for tests; it touches no device and sets no error text.  depth is [views][nslow][nfast] in storage order
+ *    (transposed != 0: [x][y]), s the supersampling factor, consts sx ox sz oz [views][4], cam_pos [views][3], cam_rot
+ *    [views][4] (both may be null in view space), parts as MRX_CLOUD_PARTS (0: one).  It writes out_points
+ *    [views][n][4] (16-byte aligned), out_pixel [views][n] and out_count [views]. */
+int mrx_cloud_create(mrx_renderer *r, uint32_t points_per_view, int frame, float max_depth);
+int mrx_cloud(mrx_renderer *r);
+int mrx_compact(mrx_renderer *r);
+int mrx_cloud_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t n, uint32_t num_cus, uint32_t forced_parts,
+                   int null_pointers, uint32_t out[3]);
+int mrx_cloud_host(const float *depth, uint32_t views, uint32_t nfast, uint32_t nslow, int transposed, uint32_t s,
+                   const float *consts, const float *cam_pos, const float *cam_rot, int frame, float max_depth,
+                   uint32_t n, uint32_t parts, float *out_points, int32_t *out_pixel, int32_t *out_count);
 
 /* -- debug readback: waits for the stream, then copies the first `bytes`
  *    bytes of a buffer to host memory (what /root/reference/src/dump.cpp:53-70

@@ -18,8 +18,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "observe.hip", "rays.hip", "rays_host.cpp", "flow.hip", "flow_host.cpp", "bvh.cpp", "mrx_api.cpp", "scene.cpp", "stages.cpp", "shards.cpp", "host_tools.cpp", "assets.cpp", "ktx2.cpp"]
-HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "observe.hpp", "rays.hpp", "rays_core.hpp", "flow.hpp", "flow_core.hpp", "assets.hpp", "bc7_tables.inc",
+HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "observe.hip", "rays.hip", "rays_host.cpp", "flow.hip", "flow_host.cpp", "cloud.hip", "cloud_host.cpp", "bvh.cpp", "mrx_api.cpp", "scene.cpp", "stages.cpp", "shards.cpp", "host_tools.cpp", "assets.cpp", "ktx2.cpp"]
+HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "observe.hpp", "rays.hpp", "rays_core.hpp", "flow.hpp", "flow_core.hpp", "cloud.hpp", "cloud_core.hpp", "assets.hpp", "bc7_tables.inc",
                           "renderer.hpp", "shards.hpp", "error.hpp",
                           "../../include/mrx.h"]
 MGR_SOURCES = ["manager.cpp"]
@@ -208,6 +208,28 @@ def build_flow_driver(force=False, verbose=False):
     return out
 
 
+def cloud_driver_path():
+    return os.path.join(ROOT, "build", "cloud_host_driver")
+
+
+def build_cloud_driver(force=False, verbose=False):
+    """AddressSanitizer + UBSan build of the point-cloud output's host entry (cloud_host.cpp: cloud_core.hpp on the
+    CPU) with its driver, csrc/cloud_host_driver.cpp.  Host compiler only; run by tests/test_cloud_cpu.py on the
+    CPU, as a stand-alone program -- never on the GPU box."""
+    out = cloud_driver_path()
+    srcs = ["cloud_host_driver.cpp", "cloud_host.cpp"]
+    deps = srcs + ["cloud.hpp", "cloud_core.hpp", "raster.hpp", "../../include/mrx.h"]
+    if force or _stale(out, deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
+               "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+               "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
+        cmd += [os.path.join(CSRC, s) for s in srcs]
+        cmd += ["-o", out]
+        _run(cmd, verbose)
+    return out
+
+
 def shards_driver_path():
     return os.path.join(ROOT, "build", "shards_tsan_driver")
 
@@ -241,6 +263,8 @@ if __name__ == "__main__":
         print(build_asan(force="--force" in sys.argv, verbose=True))
     elif "--flow-driver" in sys.argv:
         print(build_flow_driver(force="--force" in sys.argv, verbose=True))
+    elif "--cloud-driver" in sys.argv:
+        print(build_cloud_driver(force="--force" in sys.argv, verbose=True))
     elif "--shards-driver" in sys.argv:
         print(build_shards_driver(force="--force" in sys.argv, verbose=True))
     elif "--rays-driver" in sys.argv:

@@ -54,6 +54,44 @@ int mrx_box_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t k, uin
     return (int)mrx::boxParts(views, nslow, num_cus, forced_parts);
 }
 
+int mrx_cloud_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t n, uint32_t num_cus, uint32_t forced_parts,
+                   int null_pointers, uint32_t out[3])
+{
+    // (never dereferenced: checkCloud looks at the pointers' values only)
+    alignas(16) static float f[4] = {};
+    static int32_t i = 0;
+    static uint32_t u = 0;
+    const uint64_t pxPerView = (uint64_t)nfast * nslow;
+    mrx::CloudParams q {};
+    if (!null_pointers) {
+        q.depth = f;
+        q.points = f;
+        q.pixel = &i;
+        q.count = &i;
+        q.scratch = &u;
+        q.camPos = q.camRot = f;
+    }
+    q.scratchCount = (uint64_t)views * mrx::kCloudMaxParts;     // (the renderer sizes the column by the same rule)
+    q.numViews = views; q.nfast = nfast; q.nslow = nslow;
+    q.N = n;
+    q.s = 1; q.half = 0;
+    q.frame = 1;
+    q.numCUs = num_cus;
+    q.forcedParts = forced_parts;
+    if (mrx::checkCloud(q) != hipSuccess)
+        return fail(MRX_E_INVALID, "the compaction stage refuses these arguments");
+    const uint32_t parts = mrx::cloudParts(views, pxPerView, num_cus, forced_parts);
+    const uint64_t units = pxPerView * views == 0 ? 0 : (uint64_t)views * parts;
+    if (units >= (1ull << 31))
+        return fail(MRX_E_INVALID, "the compaction stage refuses these arguments");
+    if (out) {
+        out[0] = parts;
+        out[1] = mrx::kCloudLdsBytes;
+        out[2] = mrx::cloudWide(pxPerView, n) ? 1u : 0u;
+    }
+    return (int)std::min<uint64_t>(units, (uint64_t)num_cus * 4u);
+}
+
 int mrx_ray_plan(uint32_t worlds, uint32_t rays_per_world, uint32_t bvh_depth, uint32_t num_cus, uint32_t pass_rows,
                  int null_pointers, uint32_t out[4])
 {

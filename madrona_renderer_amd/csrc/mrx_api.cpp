@@ -169,6 +169,7 @@ mrx_renderer::~mrx_renderer()
     obs.release(); obsReset.release();
     rays.release(); rayT.release(); rayFrame.release(); rayId.release(); rayBound.release();
     flowOut.release(); flowSnap.release();
+    cloudOut.release(); cloudPixel.release(); cloudCount.release(); cloudScratch.release();
     if (xccHost) (void)hipHostFree(xccHost);
     bvhNodes.release(); bvhLeafTris.release(); worldInstStart.release();
     viewWorld.release(); instKBase.release(); objInfo.release();
@@ -1063,7 +1064,7 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
     }
     if (sample && which != MRX_BUF_RGB && which != MRX_BUF_DEPTH && which != MRX_BUF_SEGMASK &&
         which != MRX_BUF_VISIBILITY && which != MRX_BUF_NORMAL) {
-        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT8 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
+        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT9 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
              "not a rendered output: only rgb, depth, normals and the ids tensor have samples");
         return nullptr;
     }
@@ -1136,6 +1137,19 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
         dims[0] = V; dims[1] = r->info.storage_slow; dims[2] = r->info.storage_fast; dims[3] = 4;
         *ndim = 4; *dtype = MRX_DTYPE_F32; ptr = r->flowOut.ptr;
         off = "no optical flow: mrx_flow_create was not called on this renderer";
+        break;
+    case MRX_BUF_CLOUD:         // the point-cloud output: indexed by view and slot, no samples
+    case MRX_BUF_CLOUD_PIXEL:
+    case MRX_BUF_CLOUD_COUNT:
+        if (!r->cloudPoints) {
+            fail(MRX_E_UNSUPPORTED, "no point cloud: mrx_cloud_create was not called on this renderer");
+            return nullptr;
+        }
+        dims[0] = V; dims[1] = r->cloudPoints; dims[2] = 4;
+        *ndim = which == MRX_BUF_CLOUD ? 3 : which == MRX_BUF_CLOUD_PIXEL ? 2 : 1;
+        *dtype = which == MRX_BUF_CLOUD ? MRX_DTYPE_F32 : MRX_DTYPE_I32;
+        ptr = which == MRX_BUF_CLOUD ? (void *)r->cloudOut.ptr : which == MRX_BUF_CLOUD_PIXEL ? (void *)r->cloudPixel.ptr
+                                                               : (void *)r->cloudCount.ptr;
         break;
     case MRX_BUF_DEPTH:     // mgr.cpp:570-590
         dims[0] = V; dims[1] = S; dims[2] = F; dims[3] = 1;

@@ -17,6 +17,7 @@
 #include "bvh.hpp"
 #include "raster.hpp"
 #include "flow.hpp"
+#include "cloud.hpp"
 #include "error.hpp"
 #include "shards.hpp"
 
@@ -211,6 +212,16 @@ struct mrx_renderer {
     // MRX_FLOW_PASS_ROWS, the forced number of rows per staging pass (0: the default).
     DevBuf<float> flowOut, flowSnap;
     uint32_t flowPassRows = 0;
+    // point-cloud output (mrx_cloud_create): N points per view, the frame (1 world, 2 view space:
+    // mrx_positions' values) and the far crop (0: none); the [views][N][4] points, the [views][N] pixel indices and the
+    // [views] counts the compaction stage writes from the depth tensor the caller sees, and the [views][parts] counts of
+    // a split view's parts -- allocations of their own, outside allocOutputs and the placement search.  N == 0: no
+    // pointer, no further launch.  cloudForcedParts: MRX_CLOUD_PARTS, the forced number of workgroups per view (0: automatic).
+    uint32_t cloudPoints = 0, cloudFrame = 0, cloudForcedParts = 0;
+    float cloudMaxDepth = 0.0f;
+    DevBuf<float> cloudOut;
+    DevBuf<int32_t> cloudPixel, cloudCount;
+    DevBuf<uint32_t> cloudScratch;
     DevBuf<unsigned long long> stamps;
     // XCD phase feedback (raster.hip): a host-mapped word workgroup 0 reports its XCC id to
     uint32_t *xccHost = nullptr, *xccDev = nullptr;
@@ -271,6 +282,7 @@ struct mrx_renderer {
     mrx::FlowParams flowParams();
     hipError_t launchFlow();
     hipError_t launchFlowSnapshot();
+    hipError_t launchCloud();
 
     ~mrx_renderer();
 };

@@ -1,6 +1,6 @@
 // The post-render stages: what each launches, the table that lists them once in step order (kStages) and everything
 // that goes through it -- the step's stage loop, the shards' "run stage i" command, the stage entry points, the
-// tensors a creation flag allocates and the stages attached later (mrx_rays_create, mrx_flow_create).
+// tensors a creation flag allocates and the stages attached later (mrx_rays_create, mrx_flow_create, mrx_cloud_create).
 #include "renderer.hpp"
 
 #include "resolve.hpp"
@@ -42,6 +42,35 @@ mrx::FlowParams mrx_renderer::flowParams()
 }
 hipError_t mrx_renderer::launchFlow() { return mrx::launchFlow(flowParams(), stream); }
 hipError_t mrx_renderer::launchFlowSnapshot() { return mrx::launchFlowSnapshot(flowParams(), stream); }
+
+// (depth, the constants and the table pointer are read from the render's parameters at every launch: the placement
+// search re-binds the first, mrx_set_view_projection the others; pose and table CONTENTS are read by the kernel)
+hipError_t mrx_renderer::launchCloud()
+{
+    mrx::CloudParams q {};
+    q.depth = ss > 1 ? outDepth.ptr : params.depth;
+    q.points = cloudOut.ptr;
+    q.pixel = cloudPixel.ptr;
+    q.count = cloudCount.ptr;
+    q.scratch = cloudScratch.ptr;
+    q.scratchCount = cloudScratch.count;
+    q.camPos = params.camPos;
+    q.camRot = params.camRot;
+    q.viewProj = params.viewProj;
+    q.sx = params.sx; q.ox = params.ox; q.sz = params.sz; q.oz = params.oz;
+    q.numViews = params.numViews;
+    q.nfast = info.storage_fast;
+    q.nslow = info.storage_slow;
+    q.N = cloudPoints;
+    q.s = ss;
+    q.half = ss / 2;
+    q.frame = (int32_t)cloudFrame;
+    q.transposed = params.transposed;
+    q.maxDepth = cloudMaxDepth;
+    q.numCUs = params.numCUs;
+    q.forcedParts = cloudForcedParts;
+    return mrx::launchCloud(q, stream);
+}
 
 // (every table pointer is read from the render's parameters at every launch: bindGeometry re-binds them; pose, scale,
 // ObjectID, label, ray and frame CONTENTS are read by the kernel)
@@ -266,9 +295,10 @@ struct Stage {
     const char *off;                            // the MRX_E_UNSUPPORTED text of its entry point
 };
 enum : int { kStageResolve = 0, kStageUnproject, kStageBoxes, kStageObserve, kStageTrace, kStageFlow, kStageFlowSnapshot,
-             kNumStages };
+             kStageCloud, kNumStages };
 
-// The stages in the order a step runs them; the snapshot after the flow that reads the one before it.  A new stage is
+// The stages in the order a step runs them; the snapshot after the flow that reads the one before it; the compaction
+// last: it reads the depth the caller sees, behind the resolve, and nothing reads what it writes.  A new stage is
 // an entry here, its launch, its fields in the renderer and its tensors in bufferOf.
 static const Stage kStages[kNumStages] = {
     { [](const mrx_renderer &r) { return r.ss > 1; }, [](mrx_renderer &r) { return r.launchResolve(); }, allocResolved,
@@ -287,6 +317,8 @@ static const Stage kStages[kNumStages] = {
       "launchFlow()", "no optical flow: mrx_flow_create was not called on this renderer" },
     { [](const mrx_renderer &r) { return flowOn(&r); }, [](mrx_renderer &r) { return r.launchFlowSnapshot(); }, nullptr,
       "launchFlowSnapshot()", "no optical flow: mrx_flow_create was not called on this renderer" },
+    { [](const mrx_renderer &r) { return r.cloudPoints != 0; }, [](mrx_renderer &r) { return r.launchCloud(); }, nullptr,
+      "launchCloud()", "no point cloud: mrx_cloud_create was not called on this renderer" },
 };
 
 int allocStages(mrx_renderer &r)
@@ -417,7 +449,7 @@ static int runStage(mrx_renderer *r, int stage)
     return stageLaunch(s, *r, "r->");
 }
 
-// an attached stage (mrx_rays_create, mrx_flow_create) on the renderer or on every shard of it, all or nothing: a
+// an attached stage (mrx_rays_create, mrx_flow_create, mrx_cloud_create) on the renderer or on every shard of it, all or nothing: a
 // shard that fails takes the stage of the shards before it along
 static int attachAll(mrx_renderer *r, uint32_t arg, int (*createOne)(mrx_renderer *, uint32_t),
                      void (*destroyOne)(mrx_renderer *))
@@ -445,6 +477,7 @@ int mrx_observe(mrx_renderer *r) { return runStage(r, kStageObserve); }
 int mrx_trace(mrx_renderer *r) { return runStage(r, kStageTrace); }
 int mrx_flow(mrx_renderer *r) { return runStage(r, kStageFlow); }
 int mrx_flow_snapshot(mrx_renderer *r) { return runStage(r, kStageFlowSnapshot); }
+int mrx_compact(mrx_renderer *r) { return runStage(r, kStageCloud); }
 
 int mrx_supersample(mrx_renderer *r)
 {
@@ -627,6 +660,104 @@ int mrx_flow_enabled(mrx_renderer *r)
     if (!r)
         return fail(MRX_E_INVALID, "null renderer");
     return flowOn(r) ? 1 : 0;
+}
+
+// what the compaction stage reads and writes per step: 4 bytes of depth per native pixel; 20 bytes per slot and a count
+static uint64_t cloudBytes(const mrx_renderer *r)
+{
+    return (uint64_t)r->info.num_views * r->info.storage_fast * r->info.storage_slow * 4ull +
+           (uint64_t)r->info.num_views * ((uint64_t)r->cloudPoints * 20ull + 4ull);
+}
+
+// the output of one renderer on one device: the three tensors, the counts of a split view's parts, the first run of
+// the stage.  Frame and far crop are in the renderer already (mrx_cloud_create).
+static int cloudCreateOne(mrx_renderer *r, uint32_t N)
+{
+    MRX_HIP(hipSetDevice(r->device));
+    const uint64_t views = r->info.num_views, slots = views * N;
+    const uint64_t pxPerView = (uint64_t)r->info.storage_fast * r->info.storage_slow;
+    // (a failure leaves the renderer without the output: cloudPoints is cleared again)
+    auto undo = [&](hipError_t e) {
+        r->cloudPoints = 0;
+        r->cloudOut.release(); r->cloudPixel.release(); r->cloudCount.release(); r->cloudScratch.release();
+        return fail(MRX_E_HIP, std::string("point cloud: ") + hipGetErrorString(e));
+    };
+    r->cloudForcedParts = 0;
+    if (const char *dbg = std::getenv("MRX_CLOUD_PARTS"))       // tests: the split at tiny sizes
+        r->cloudForcedParts = (uint32_t)std::max(0, std::atoi(dbg));
+    const uint64_t parts = mrx::cloudParts(r->info.num_views, pxPerView, r->params.numCUs, r->cloudForcedParts);
+    hipError_t e = r->cloudOut.alloc((size_t)slots * 4u);
+    if (e == hipSuccess) e = r->cloudPixel.alloc((size_t)slots);
+    if (e == hipSuccess) e = r->cloudCount.alloc((size_t)views);
+    if (e == hipSuccess) e = r->cloudScratch.alloc((size_t)(views * parts));
+    // the empty cloud: zero points, pixel -1 (all bytes 0xFF), count 0
+    if (e == hipSuccess) e = hipMemsetAsync(r->cloudOut.ptr, 0, (size_t)slots * 16u, r->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r->cloudPixel.ptr, 0xFF, (size_t)slots * 4u, r->stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r->cloudCount.ptr, 0, (size_t)views * 4u, r->stream);
+    if (e != hipSuccess)
+        return undo(e);
+    r->cloudPoints = N;
+    e = r->launchCloud();
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess)
+        return undo(e);
+    r->info.bytes_per_step += cloudBytes(r);
+    return MRX_OK;
+}
+
+// takes the output off a shard again (mrx_cloud_create failed on a later one)
+static void cloudDestroyOne(mrx_renderer *r)
+{
+    (void)hipSetDevice(r->device);
+    (void)hipStreamSynchronize(r->stream);
+    r->info.bytes_per_step -= cloudBytes(r);
+    r->cloudPoints = 0;
+    r->cloudOut.release(); r->cloudPixel.release(); r->cloudCount.release(); r->cloudScratch.release();
+}
+
+int mrx_cloud_create(mrx_renderer *r, uint32_t points_per_view, int frame, float max_depth)
+{
+    if (const int src = settle(r))
+        return src;
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (r->parent)
+        return fail(MRX_E_INVALID, "mrx_cloud_create on a shard: attach the output to the renderer it belongs to");
+    if (r->cloudPoints)
+        return fail(MRX_E_INVALID, "this renderer already has the point-cloud output");
+    if (points_per_view < 1 || points_per_view > mrx::kCloudMaxPoints)
+        return fail(MRX_E_INVALID, "points_per_view " + std::to_string(points_per_view) + " is not in 1 ... 65536");
+    if (frame != 1 && frame != 2)
+        return fail(MRX_E_INVALID, "point cloud: frame " + std::to_string(frame) + " is neither 1 (world space) nor 2 (view space)");
+    if (!(max_depth == 0.0f || (std::isfinite(max_depth) && max_depth > 0.0f)))
+        return fail(MRX_E_INVALID, "point cloud: max_depth is 0 (none) or finite and positive");
+    const mrx_renderer *first = r->shards.empty() ? r : r->shards[0];
+    if (!first->depth.ptr)
+        return fail(MRX_E_INVALID, "the point cloud needs depth: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)");
+    mrx_info_t whole {};
+    if (infoFull(r, &whole) != MRX_OK)
+        return MRX_E_INVALID;
+    if ((uint64_t)whole.num_views * points_per_view >= (1ull << 31))
+        return fail(MRX_E_INVALID, "point cloud: views * points_per_view reaches 2^31");
+    if ((uint64_t)whole.storage_fast * whole.storage_slow > mrx::kCloudMaxViewPixels ||
+        (uint64_t)whole.num_views * whole.storage_fast * whole.storage_slow > mrx::kCloudMaxPixels)
+        return fail(MRX_E_INVALID, "point cloud: more than 2^32 - 1 native pixels, or more than 2^31 - 1 in a view");
+    const auto store = [&](mrx_renderer &sh) {
+        sh.cloudFrame = (uint32_t)frame;
+        sh.cloudMaxDepth = max_depth;
+    };
+    store(*r);
+    for (mrx_renderer *sh : r->shards)
+        store(*sh);
+    const int rc = attachAll(r, points_per_view, cloudCreateOne, cloudDestroyOne);
+    if (rc == MRX_OK)
+        r->cloudPoints = points_per_view;           // (of a renderer of several devices: the parent's, too)
+    return rc;
+}
+
+int mrx_cloud(mrx_renderer *r)
+{
+    return r ? (int)r->cloudPoints : fail(MRX_E_INVALID, "null renderer");
 }
 
 int mrx_observations(mrx_renderer *r)
