@@ -406,7 +406,13 @@ enum {
     MRX_BUF_CLOUD_PIXEL = 24,
     /* i32 [views]: M, the valid pixels of the view -- not min(M, N). */
     MRX_BUF_CLOUD_COUNT = 25,
-    MRX_NUM_BUFFERS_EXT9 = 26
+    MRX_NUM_BUFFERS_EXT9 = 26,
+    /* The shadow mask (mrx_shadow_create); per shard, like the other outputs; it has no sample
+     * tensor.  u8 [views,H,W] (Raytracer: [views,res,res], transposed), stored exactly like depth: 0 where the pixel's
+     * point, in the depth tensor the caller sees, is cut off from the light of its world by a triangle of that world,
+     * 255 on every other pixel, background included. */
+    MRX_BUF_SHADOW = 26,
+    MRX_NUM_BUFFERS_EXT10 = 27
 };
 
 enum { MRX_DTYPE_U8 = 0, MRX_DTYPE_I32 = 1, MRX_DTYPE_F32 = 2, MRX_DTYPE_F16 = 3, MRX_DTYPE_BF16 = 4 };
@@ -597,6 +603,51 @@ int mrx_cloud_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t n, u
 int mrx_cloud_host(const float *depth, uint32_t views, uint32_t nfast, uint32_t nslow, int transposed, uint32_t s,
                    const float *consts, const float *cam_pos, const float *cam_rot, int frame, float max_depth,
                    uint32_t n, uint32_t parts, float *out_points, int32_t *out_pixel, int32_t *out_count);
+
+/* -- cast shadows.  Attached after creation, as the sensor, the flow and the cloud are:
+ *    mrx_shadow_create(r, apply, bias, max_distance) allocates MRX_BUF_SHADOW, runs the stage once in its mask-only form
+ *    and waits.  Per native pixel with depth z > 0 one ray leaves the pixel's world point (MRX_BUF_POSITION's, world
+ *    space) towards the light of the view's world, from t = bias * z (bias finite and >= 0; MRX_SHADOW_DEFAULT_BIAS) to
+ *    t = max_distance (MRX_SHADOW_NO_MAX_DISTANCE = FLT_MAX for none, otherwise finite and > 0); the mask holds 0 where
+ *    some triangle of a visible row of the world is in its way, 255 elsewhere.  From then on mrx_step / mrx_render /
+ *    mrx_time_renders enqueue the shadow stage behind the unprojection and ahead of the boxes and the observation; with
+ *    apply != 0 that launch also scales the rgb of an occluded pixel down to its ambient term, lit = diffuse * max(n . l,
+ *    0) + ambient from the normal tensor's bytes, f = ambient / lit where lit > ambient, so a packed observation holds the
+ *    shadowed colours.  bytes_per_step grows by 5 per native pixel.  MRX_E_INVALID, each with its own text, for a null
+ *    renderer, a shard, a second call, a bias or max_distance out of range, a renderer without depth, apply on a
+ *    renderer without rgb or without MRX_FLAG_NORMALS, more than 2^32 - 1 native pixels; on a renderer of several
+ *    shards it fans out, all or nothing.  MRX_SHADOW_BRUTE=1 in the environment at that call selects the form of the
+ *    kernel that skips every cull, MRX_SHADOW_PASS_ROWS=n stages n rows of a world at a time (tests).
+ *    mrx_shadows returns 0 (off), 1 (mask) or 2 (mask and rgb); MRX_E_INVALID for a null renderer.  mrx_shadow enqueues
+ *    the stage alone on the renderer's stream (every shard's on its own) in its MASK-ONLY form whatever apply is: calling
+ *    it any number of times leaves rgb as the last step left it.  MRX_E_UNSUPPORTED without the stage.
+ *    mrx_shadow_plan is host arithmetic, for tests: the answer of the stage's launch checks for `views` views of nslow
+ *    rows of nfast pixels at supersampling factor s over a scene whose deepest BLAS has bvh_depth levels, on num_cus
+ *    compute units (pass_rows: MRX_SHADOW_PASS_ROWS, 0 = the default; bad_pointers: 0 none, 1 null tensors, 2 a depth
+ *    tensor off a 4-byte boundary, 3 an rgb tensor off one) -- MRX_E_INVALID where the launch would be refused,
+ *    otherwise the number of workgroups (0: nothing is enqueued), and out[0 ... 3], when not null, = workgroups per view,
+ *    stack entries per lane, rows per staging pass, dynamic LDS bytes.  It touches no device.
+ *    mrx_shadow_host runs the stage's source on the CPU, for tests; it touches no device and sets no error text.
+ *    Geometry as mrx_trace_rays_host takes it; depth [views][nslow][nfast] in storage order (transposed != 0: [x][y]), s
+ *    the supersampling factor, consts sx ox sz oz [views][4], cam_pos [views][3], cam_rot [views][4] as mrx_cloud_host
+ *    takes them; view_world [views]; lights [views][5] = toLight xyz, ambient, diffuse as mrx_light_constants resolves
+ *    them; pass_rows as MRX_SHADOW_PASS_ROWS; brute != 0 skips every cull.  rgb_or_null and normal_or_null
+ *    [views][nslow][nfast] packed pixels, both or neither: with them the applying form runs and rgb is changed in
+ *    place.  It builds the BLAS as mrx_create does and writes out_mask [views][nslow][nfast]. */
+#define MRX_SHADOW_DEFAULT_BIAS (1.0f / 1024.0f)
+#define MRX_SHADOW_NO_MAX_DISTANCE 3.402823466e+38f
+int mrx_shadow_create(mrx_renderer *r, int apply, float bias, float max_distance);
+int mrx_shadows(mrx_renderer *r);
+int mrx_shadow(mrx_renderer *r);
+int mrx_shadow_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t s, uint32_t bvh_depth, uint32_t num_cus,
+                    uint32_t pass_rows, int apply, float bias, float max_distance, int bad_pointers, uint32_t out[4]);
+int mrx_shadow_host(const float *tri_pos, uint32_t num_tris, const int32_t *obj_first, const int32_t *obj_count,
+                    uint32_t num_objects, const mrx_instance *instances, uint32_t num_instances,
+                    const uint32_t *world_inst_start, uint32_t num_worlds, const float *depth, uint32_t views,
+                    uint32_t nfast, uint32_t nslow, int transposed, uint32_t s, const float *consts,
+                    const float *cam_pos, const float *cam_rot, const uint32_t *view_world, const float *lights,
+                    float bias, float max_distance, uint32_t pass_rows, int brute, uint32_t *rgb_or_null,
+                    const uint32_t *normal_or_null, uint8_t *out_mask);
 
 /* -- debug readback: waits for the stream, then copies the first `bytes`
  *    bytes of a buffer to host memory (what /root/reference/src/dump.cpp:53-70

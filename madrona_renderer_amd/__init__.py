@@ -15,7 +15,7 @@ import sys
 
 from . import build as _build
 
-__all__ = ["load_module", "load_capi", "lib_path", "module_path", "scenes", "cloud"]
+__all__ = ["load_module", "load_capi", "lib_path", "module_path", "scenes", "cloud", "shadows"]
 
 _MODULE = None
 _CAPI = None

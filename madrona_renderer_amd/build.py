@@ -18,8 +18,8 @@ ROOT = os.path.dirname(HERE)
 CSRC = os.path.join(HERE, "csrc")
 ARCH = "gfx950"
 
-HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "observe.hip", "rays.hip", "rays_host.cpp", "flow.hip", "flow_host.cpp", "cloud.hip", "cloud_host.cpp", "bvh.cpp", "mrx_api.cpp", "scene.cpp", "stages.cpp", "shards.cpp", "host_tools.cpp", "assets.cpp", "ktx2.cpp"]
-HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "observe.hpp", "rays.hpp", "rays_core.hpp", "flow.hpp", "flow_core.hpp", "cloud.hpp", "cloud_core.hpp", "assets.hpp", "bc7_tables.inc",
+HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "observe.hip", "rays.hip", "rays_host.cpp", "flow.hip", "flow_host.cpp", "cloud.hip", "cloud_host.cpp", "shadow.hip", "shadow_host.cpp", "bvh.cpp", "mrx_api.cpp", "scene.cpp", "stages.cpp", "shards.cpp", "host_tools.cpp", "assets.cpp", "ktx2.cpp"]
+HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "observe.hpp", "rays.hpp", "rays_core.hpp", "flow.hpp", "flow_core.hpp", "cloud.hpp", "cloud_core.hpp", "shadow.hpp", "shadow_core.hpp", "assets.hpp", "bc7_tables.inc",
                           "renderer.hpp", "shards.hpp", "error.hpp",
                           "../../include/mrx.h"]
 MGR_SOURCES = ["manager.cpp"]
@@ -230,6 +230,29 @@ def build_cloud_driver(force=False, verbose=False):
     return out
 
 
+def shadow_driver_path():
+    return os.path.join(ROOT, "build", "shadow_host_driver")
+
+
+def build_shadow_driver(force=False, verbose=False):
+    """AddressSanitizer + UBSan build of the shadow stage's host entry (shadow_host.cpp: shadow_core.hpp on the CPU,
+    over the host scene of rays_host.cpp and the BLAS builder) with its driver, csrc/shadow_host_driver.cpp.  Host
+    compiler only; run by tests/test_shadow_cpu.py on the CPU, as a stand-alone program -- never on the GPU box."""
+    out = shadow_driver_path()
+    srcs = ["shadow_host_driver.cpp", "shadow_host.cpp", "rays_host.cpp", "bvh.cpp", "assets.cpp", "ktx2.cpp"]
+    deps = srcs + ["shadow.hpp", "shadow_core.hpp", "cloud_core.hpp", "rays.hpp", "rays_core.hpp", "assets.hpp",
+                   "bvh.hpp", "raster.hpp", "bc7_tables.inc", "../../include/mrx.h"]
+    if force or _stale(out, deps):
+        os.makedirs(os.path.dirname(out), exist_ok=True)
+        cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
+               "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+               "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
+        cmd += [os.path.join(CSRC, s) for s in srcs]
+        cmd += ["-lz", "-ldl", "-o", out]
+        _run(cmd, verbose)
+    return out
+
+
 def shards_driver_path():
     return os.path.join(ROOT, "build", "shards_tsan_driver")
 
@@ -265,6 +288,8 @@ if __name__ == "__main__":
         print(build_flow_driver(force="--force" in sys.argv, verbose=True))
     elif "--cloud-driver" in sys.argv:
         print(build_cloud_driver(force="--force" in sys.argv, verbose=True))
+    elif "--shadow-driver" in sys.argv:
+        print(build_shadow_driver(force="--force" in sys.argv, verbose=True))
     elif "--shards-driver" in sys.argv:
         print(build_shards_driver(force="--force" in sys.argv, verbose=True))
     elif "--rays-driver" in sys.argv:

@@ -15,97 +15,15 @@ import ctypes
 import math
 
 from . import load_capi
+from . import _dlpack
+# (the DLPack helpers live in _dlpack.py, shared with shadows.py; the names this module always had stay)
+from ._dlpack import Exported as _Exported, _LIVE, kDLCPU as _kDLCPU, kDLInt as _kDLInt, kDLFloat as _kDLFloat  # noqa: F401
 
 __all__ = ["attach", "Cloud", "MAX_POINTS", "FRAMES"]
 
 MAX_POINTS = 65536
 FRAMES = {"world": 1, "view": 2}                    # mrx_positions' values
 MRX_BUF_CLOUD, MRX_BUF_CLOUD_PIXEL, MRX_BUF_CLOUD_COUNT = 23, 24, 25
-_MRX_DTYPE_I32, _MRX_DTYPE_F32 = 1, 2
-
-# ---- minimal DLPack (v0.8 ABI), as the compiled module's Tensor.__dlpack__ builds it
-_kDLCPU, _kDLROCM = 1, 10
-_kDLInt, _kDLFloat = 0, 2
-
-
-class _DLDevice(ctypes.Structure):
-    _fields_ = [("device_type", ctypes.c_int32), ("device_id", ctypes.c_int32)]
-
-
-class _DLDataType(ctypes.Structure):
-    _fields_ = [("code", ctypes.c_uint8), ("bits", ctypes.c_uint8), ("lanes", ctypes.c_uint16)]
-
-
-class _DLTensor(ctypes.Structure):
-    _fields_ = [("data", ctypes.c_void_p), ("device", _DLDevice), ("ndim", ctypes.c_int32), ("dtype", _DLDataType),
-                ("shape", ctypes.POINTER(ctypes.c_int64)), ("strides", ctypes.POINTER(ctypes.c_int64)),
-                ("byte_offset", ctypes.c_uint64)]
-
-
-class _DLManagedTensor(ctypes.Structure):
-    pass
-
-
-_DELETER = ctypes.CFUNCTYPE(None, ctypes.POINTER(_DLManagedTensor))
-_DLManagedTensor._fields_ = [("dl_tensor", _DLTensor), ("manager_ctx", ctypes.c_void_p), ("deleter", _DELETER)]
-
-# what the capsules in flight point into, by address: the managed tensor, its shape array and the owner of the memory
-_LIVE = {}
-
-
-@_DELETER
-def _dl_deleter(managed):
-    _LIVE.pop(ctypes.addressof(managed.contents), None)
-
-
-_CAPSULE_DTOR = ctypes.CFUNCTYPE(None, ctypes.c_void_p)
-
-
-@_CAPSULE_DTOR
-def _capsule_destructor(capsule):
-    # a capsule nobody consumed still owns its tensor (a consumed one is renamed "used_dltensor" and owns nothing)
-    api = ctypes.pythonapi
-    if api.PyCapsule_IsValid(ctypes.c_void_p(capsule), b"dltensor"):
-        _LIVE.pop(api.PyCapsule_GetPointer(ctypes.c_void_p(capsule), b"dltensor"), None)
-
-
-def _capsule(ptr, shape, code, bits, device_type, device_id, owner):
-    """A "dltensor" capsule for a dense row-major tensor at address `ptr`; `owner` lives as long as the consumer's
-    tensor does."""
-    api = ctypes.pythonapi
-    api.PyCapsule_New.restype = ctypes.py_object
-    api.PyCapsule_New.argtypes = [ctypes.c_void_p, ctypes.c_char_p, ctypes.c_void_p]
-    api.PyCapsule_IsValid.restype = ctypes.c_int
-    api.PyCapsule_IsValid.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
-    api.PyCapsule_GetPointer.restype = ctypes.c_void_p
-    api.PyCapsule_GetPointer.argtypes = [ctypes.c_void_p, ctypes.c_char_p]
-    dims = (ctypes.c_int64 * len(shape))(*shape)
-    m = _DLManagedTensor()
-    m.dl_tensor.data = ptr
-    m.dl_tensor.device = _DLDevice(device_type, device_id)
-    m.dl_tensor.ndim = len(shape)
-    m.dl_tensor.dtype = _DLDataType(code, bits, 1)
-    m.dl_tensor.shape = ctypes.cast(dims, ctypes.POINTER(ctypes.c_int64))
-    m.dl_tensor.strides = None
-    m.dl_tensor.byte_offset = 0
-    m.manager_ctx = None
-    m.deleter = _dl_deleter
-    addr = ctypes.addressof(m)
-    _LIVE[addr] = (m, dims, owner)
-    return api.PyCapsule_New(addr, b"dltensor", ctypes.cast(_capsule_destructor, ctypes.c_void_p))
-
-
-class _Exported:
-    """What torch.from_dlpack takes: one tensor of the renderer's memory"""
-
-    def __init__(self, ptr, shape, code, bits, device_type, device_id, owner):
-        self._args = (ptr, tuple(shape), code, bits, device_type, device_id, owner)
-
-    def __dlpack__(self, **kwargs):
-        return _capsule(*self._args)
-
-    def __dlpack_device__(self):
-        return (self._args[4], self._args[5])
 
 
 def _check_arguments(points, frame, max_depth):
@@ -141,23 +59,12 @@ def _capi():
     for name in ("mrx_compact", "mrx_cloud"):
         getattr(lib, name).restype = ctypes.c_int
         getattr(lib, name).argtypes = [ctypes.c_void_p]
-    lib.mrx_num_shards.restype = ctypes.c_int
-    lib.mrx_num_shards.argtypes = [ctypes.c_void_p]
-    lib.mrx_last_error.restype = ctypes.c_char_p
-    lib.mrx_last_error.argtypes = []
-    for name in ("mrx_buffer", "mrx_buffer_shard"):
-        getattr(lib, name).restype = ctypes.c_void_p
-    lib.mrx_buffer.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
-                               ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]
-    lib.mrx_buffer_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
-                                     ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
-                                     ctypes.POINTER(ctypes.c_int)]
+    _dlpack.declare_buffers(lib)
     _LIB = lib
     return lib
 
 
-def _error(lib):
-    return (lib.mrx_last_error() or b"").decode("utf-8", "replace")
+_error = _dlpack.last_error
 
 
 class Cloud:
@@ -173,22 +80,7 @@ class Cloud:
     max_depth = property(lambda self: self._max_depth, doc="the far crop, or None")
 
     def _tensor(self, which, shard):
-        import torch
-        lib = _capi()
-        dims = (ctypes.c_int64 * 4)(1, 1, 1, 1)
-        nd, dt, dev = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
-        if shard is None:
-            n = lib.mrx_num_shards(self._h)
-            if n > 1:
-                raise ValueError("this renderer spans %d devices: say which shard's tensor (shard=i)" % n)
-            ptr = lib.mrx_buffer(self._h, which, dims, ctypes.byref(nd), ctypes.byref(dt), ctypes.byref(dev))
-        else:
-            ptr = lib.mrx_buffer_shard(self._h, int(shard), which, dims, ctypes.byref(nd), ctypes.byref(dt),
-                                       ctypes.byref(dev))
-        if not ptr:
-            raise RuntimeError(_error(lib))
-        code = _kDLFloat if dt.value == _MRX_DTYPE_F32 else _kDLInt
-        return torch.from_dlpack(_Exported(ptr, list(dims)[:nd.value], code, 32, _kDLROCM, dev.value, self._r))
+        return _dlpack.buffer_tensor(_capi(), self._h, which, shard, self._r)
 
     def points_tensor(self, shard=None):
         """float32 [views, N, 4]: (x, y, z, 1) per filled slot, (0, 0, 0, 0) per empty one"""

@@ -132,6 +132,51 @@ int mrx_ray_plan(uint32_t worlds, uint32_t rays_per_world, uint32_t bvh_depth, u
     return (int)plan.workgroups;
 }
 
+int mrx_shadow_plan(uint32_t views, uint32_t nfast, uint32_t nslow, uint32_t s, uint32_t bvh_depth, uint32_t num_cus,
+                    uint32_t pass_rows, int apply, float bias, float max_distance, int bad_pointers, uint32_t out[4])
+{
+    // (never dereferenced: planShadow looks at the pointers' values only)
+    alignas(4) static char bytes[8] = {};
+    static float f = 0.0f;
+    static int32_t i = 0;
+    static uint32_t u = 0;
+    static uint8_t b = 0;
+    mrx::ShadowParams q {};
+    if (bad_pointers != 1) {
+        q.s.tris = reinterpret_cast<const mrx::ObjTri *>(&f);
+        q.s.nodes = reinterpret_cast<const mrx::BvhNode *>(&f);
+        q.s.leafTris = &u;
+        q.s.instInfo = reinterpret_cast<const mrx::ObjInfo *>(&f);
+        q.s.worldInstStart = &u;
+        q.s.instPos = q.s.instRot = q.s.instScale = &f;
+        q.s.instObj = &i;
+        q.viewWorld = &u;
+        q.depth = bad_pointers == 2 ? reinterpret_cast<const float *>(bytes + 1) : &f;
+        q.mask = &b;
+        q.rgb = bad_pointers == 3 ? reinterpret_cast<uint32_t *>(bytes + 2) : &u;
+        q.normal = &u;
+        q.camPos = q.camRot = &f;
+    }
+    q.numViews = views; q.nfast = nfast; q.nslow = nslow;
+    q.ss = s; q.half = s / 2;
+    q.apply = apply;
+    q.bias = bias;
+    q.maxDistance = max_distance;
+    q.bvhDepth = bvh_depth;
+    q.numCUs = num_cus;
+    q.passRows = pass_rows;
+    mrx::ShadowPlan plan;
+    if (mrx::planShadow(q, plan) != hipSuccess)
+        return fail(MRX_E_INVALID, "the shadow stage refuses these arguments");
+    if (out) {
+        out[0] = plan.blocksPerView;
+        out[1] = plan.stackEntries;
+        out[2] = plan.passRows;
+        out[3] = plan.ldsBytes;
+    }
+    return (int)plan.workgroups;
+}
+
 int mrx_load_obj(const char *path, float **tri_pos, float **tri_uv, uint32_t *num_tris)
 {
     if (!path || !tri_pos || !tri_uv || !num_tris)

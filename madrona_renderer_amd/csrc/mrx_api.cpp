@@ -170,6 +170,7 @@ mrx_renderer::~mrx_renderer()
     rays.release(); rayT.release(); rayFrame.release(); rayId.release(); rayBound.release();
     flowOut.release(); flowSnap.release();
     cloudOut.release(); cloudPixel.release(); cloudCount.release(); cloudScratch.release();
+    shadowMask.release();
     if (xccHost) (void)hipHostFree(xccHost);
     bvhNodes.release(); bvhLeafTris.release(); worldInstStart.release();
     viewWorld.release(); instKBase.release(); objInfo.release();
@@ -1064,7 +1065,7 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
     }
     if (sample && which != MRX_BUF_RGB && which != MRX_BUF_DEPTH && which != MRX_BUF_SEGMASK &&
         which != MRX_BUF_VISIBILITY && which != MRX_BUF_NORMAL) {
-        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT9 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
+        fail(which >= 0 && which < MRX_NUM_BUFFERS_EXT10 ? MRX_E_UNSUPPORTED : MRX_E_INVALID,
              "not a rendered output: only rgb, depth, normals and the ids tensor have samples");
         return nullptr;
     }
@@ -1150,6 +1151,11 @@ static void *bufferOf(mrx_renderer *r, int which, int64_t dims[4], int *ndim, in
         *dtype = which == MRX_BUF_CLOUD ? MRX_DTYPE_F32 : MRX_DTYPE_I32;
         ptr = which == MRX_BUF_CLOUD ? (void *)r->cloudOut.ptr : which == MRX_BUF_CLOUD_PIXEL ? (void *)r->cloudPixel.ptr
                                                                : (void *)r->cloudCount.ptr;
+        break;
+    case MRX_BUF_SHADOW:    // the shadow mask: stored exactly like depth, native size, no samples
+        dims[0] = V; dims[1] = r->info.storage_slow; dims[2] = r->info.storage_fast;
+        *ndim = 3; *dtype = MRX_DTYPE_U8; ptr = r->shadowMask.ptr;
+        off = "no shadow mask: mrx_shadow_create was not called on this renderer";
         break;
     case MRX_BUF_DEPTH:     // mgr.cpp:570-590
         dims[0] = V; dims[1] = S; dims[2] = F; dims[3] = 1;

@@ -6,9 +6,11 @@
 #pragma once
 
 #include <cstdint>
+#include <vector>
 
 #include <hip/hip_runtime_api.h>
 
+#include "../../include/mrx.h"
 #include "rays_core.hpp"
 
 namespace mrx {
@@ -46,5 +48,21 @@ hipError_t launchRays(const RayParams &p, hipStream_t stream);
 
 // The same source on the CPU, ray by ray (mrx_trace_rays_host): no device is touched.
 void traceRaysHost(const RayParams &p);
+
+// What the host entries (mrx_trace_rays_host, mrx_shadow_host) make of the geometry a caller hands them: the pool, the
+// BLAS buildBlas gives it, the columns and per-row tables as bindGeometry lays them out, and `tables` pointing at them
+// (instLabel null).  MRX_E_INVALID for ranges that do not fit, MRX_E_UNSUPPORTED for a BLAS deeper than the stack.
+struct RayHostScene {
+    std::vector<ObjTri> tris;
+    BlasSet blas;
+    std::vector<float> pos, rot, scale;
+    std::vector<int32_t> obj, bound;
+    std::vector<uint32_t> kBase;
+    std::vector<ObjInfo> info;
+    RayTables tables;
+};
+int rayHostScene(const float *tri_pos, uint32_t num_tris, const int32_t *obj_first, const int32_t *obj_count,
+                 uint32_t num_objects, const mrx_instance *instances, uint32_t num_instances,
+                 const uint32_t *world_inst_start, uint32_t num_worlds, RayHostScene &g);
 
 }  // namespace mrx

@@ -104,8 +104,9 @@ MRX_HD inline Ray rayFromFrame(const float *in, int32_t frame, uint32_t rowLo, u
 }
 
 // Phase A: row `row` of the instance tables -> its staged record.  A candidate has a live ObjectID >= 0, a bound object
-// that is drawn and holds triangles, and a scale whose components are all finite and not zero.
-MRX_HD inline void rayStageRow(uint32_t row, const RayTables &s, RayRow &out)
+// that is drawn and holds triangles, and a scale whose components are all finite and not zero.  rayStageFrame: the
+// record without kBase and id, which only a stage that names what it hit reads (the shadow stage does not: S19).
+MRX_HD inline void rayStageFrame(uint32_t row, const RayTables &s, RayRow &out)
 {
     const ObjInfo info = s.instInfo[row];
     const float *sc = s.instScale + 3 * (size_t)row;
@@ -122,6 +123,11 @@ MRX_HD inline void rayStageRow(uint32_t row, const RayTables &s, RayRow &out)
     out.firstTri = info.firstTri;
     out.numTris = cand ? info.numTris : 0u;
     out.root = info.root;
+}
+
+MRX_HD inline void rayStageRow(uint32_t row, const RayTables &s, RayRow &out)
+{
+    rayStageFrame(row, s, out);
     out.kBase = s.instKBase[row];
     const int32_t lab = s.instLabel ? s.instLabel[row] : kLabelObject;
     out.id = lab == kLabelObject ? s.boundObj[row] : lab;
@@ -138,22 +144,55 @@ MRX_HD inline void rayToInstance(const RayRow &row, const Ray &r, float *o, floa
 }
 
 // Moeller-Trumbore, two-sided, on the vertices as stored; a NaN anywhere fails a comparison and rejects.  The winner
-// is the smallest t, among equal t the lowest k: no order of the calls changes it.
+// is the smallest t, among equal t the lowest k: no order of the calls changes it.  rayTriangleTest: is the triangle
+// accepted, and at which t -- all an any-hit query asks (S19).  The test in two halves: what the triangle and the
+// direction give alone (RayTriPrep: 16 dwords, one 64-byte record), and the rest, which needs the origin.  Rays of one
+// direction share the first half (the shadow stage computes it once per triangle); the operations and their order are
+// the same however the halves are called.
+struct alignas(16) RayTriPrep {
+    float v0[3], e1[3], e2[3], p[3];
+    float det, inv;
+    float pad[2];
+};
+static_assert(sizeof(RayTriPrep) == 64, "RayTriPrep is four 16-byte loads");
+
+MRX_HD inline void rayTrianglePrep(const float *v, const float *d, RayTriPrep &k)
+{
+    for (int c = 0; c < 3; ++c) {
+        k.v0[c] = v[c];
+        k.e1[c] = v[3 + c] - v[c];
+        k.e2[c] = v[6 + c] - v[c];
+    }
+    rayCross(d, k.e2, k.p);
+    k.det = rayDot(k.e1, k.p);
+    k.inv = 1.0f / k.det;
+    k.pad[0] = k.pad[1] = 0.0f;
+}
+
+MRX_HD inline bool rayTrianglePrepped(const RayTriPrep &k, const float *o, const float *d, float tmin, float tmax,
+                                      float &t)
+{
+    float q[3];
+    const float sv[3] = { o[0] - k.v0[0], o[1] - k.v0[1], o[2] - k.v0[2] };
+    const float u = rayDot(sv, k.p) * k.inv;
+    rayCross(sv, k.e1, q);
+    const float w = rayDot(d, q) * k.inv;
+    t = rayDot(k.e2, q) * k.inv;
+    return k.det != 0.0f && u >= 0.0f && w >= 0.0f && u + w <= 1.0f && t > tmin && t <= tmax;
+}
+
+MRX_HD inline bool rayTriangleTest(const float *v, const float *o, const float *d, float tmin, float tmax, float &t)
+{
+    RayTriPrep k;
+    rayTrianglePrep(v, d, k);
+    return rayTrianglePrepped(k, o, d, tmin, tmax, t);
+}
+
 MRX_HD inline void rayTriangle(const float *v, const float *o, const float *d, float tmin, float tmax, uint32_t k,
                                int32_t id, RayBest &best)
 {
-    const float e1[3] = { v[3] - v[0], v[4] - v[1], v[5] - v[2] };
-    const float e2[3] = { v[6] - v[0], v[7] - v[1], v[8] - v[2] };
-    float p[3], q[3];
-    rayCross(d, e2, p);
-    const float det = rayDot(e1, p);
-    const float inv = 1.0f / det;
-    const float sv[3] = { o[0] - v[0], o[1] - v[1], o[2] - v[2] };
-    const float u = rayDot(sv, p) * inv;
-    rayCross(sv, e1, q);
-    const float w = rayDot(d, q) * inv;
-    const float t = rayDot(e2, q) * inv;
-    const bool hit = det != 0.0f && u >= 0.0f && w >= 0.0f && u + w <= 1.0f && t > tmin && t <= tmax;
+    float t;
+    const bool hit = rayTriangleTest(v, o, d, tmin, tmax, t);
     if (hit && (best.k == kRayNoHit || t < best.t || (t == best.t && k < best.k))) {
         best.t = t;
         best.k = k;

@@ -66,17 +66,14 @@ void traceRaysHost(const RayParams &p)
 
 }  // namespace mrx
 
-extern "C" int mrx_trace_rays_host(const float *tri_pos, uint32_t num_tris, const int32_t *obj_first,
-                                   const int32_t *obj_count, uint32_t num_objects, const mrx_instance *instances,
-                                   uint32_t num_instances, const int32_t *labels_or_null,
-                                   const uint32_t *world_inst_start, uint32_t num_worlds, const int32_t *frame_or_null,
-                                   const float *rays, uint32_t rays_per_world, int brute, float *out_t, int32_t *out_id)
+namespace mrx {
+
+int rayHostScene(const float *tri_pos, uint32_t num_tris, const int32_t *obj_first, const int32_t *obj_count,
+                 uint32_t num_objects, const mrx_instance *instances, uint32_t num_instances,
+                 const uint32_t *world_inst_start, uint32_t num_worlds, RayHostScene &g)
 {
-    using namespace mrx;
-    if (rays_per_world < 1 || rays_per_world > kRayMaxPerWorld || (uint64_t)num_worlds * rays_per_world >= (1ull << 31))
-        return MRX_E_INVALID;
-    if (!world_inst_start || !rays || !out_t || !out_id || (num_tris && !tri_pos) ||
-        (num_objects && (!obj_first || !obj_count)) || (num_instances && !instances))
+    if (!world_inst_start || (num_tris && !tri_pos) || (num_objects && (!obj_first || !obj_count)) ||
+        (num_instances && !instances))
         return MRX_E_INVALID;
     std::vector<int32_t> first(num_objects), count(num_objects);
     for (uint32_t o = 0; o < num_objects; ++o) {
@@ -88,52 +85,73 @@ extern "C" int mrx_trace_rays_host(const float *tri_pos, uint32_t num_tris, cons
     for (uint32_t w = 0; w < num_worlds; ++w)
         if (world_inst_start[w] > world_inst_start[w + 1] || world_inst_start[w + 1] > num_instances)
             return MRX_E_INVALID;
-    std::vector<ObjTri> tris(num_tris);
+    g.tris.resize(num_tris);
     for (uint32_t t = 0; t < num_tris; ++t) {
-        std::memset(&tris[t], 0, sizeof(ObjTri));
-        std::memcpy(tris[t].p, tri_pos + 9 * (size_t)t, sizeof tris[t].p);
-        tris[t].mat = -1;
+        std::memset(&g.tris[t], 0, sizeof(ObjTri));
+        std::memcpy(g.tris[t].p, tri_pos + 9 * (size_t)t, sizeof g.tris[t].p);
+        g.tris[t].mat = -1;
     }
-    BlasSet blas;
-    buildBlas(tris.data(), first, count, blas);
-    if (1u + 7u * blas.maxDepth > kBvhStackCap)
+    buildBlas(g.tris.data(), first, count, g.blas);
+    if (1u + 7u * g.blas.maxDepth > kBvhStackCap)
         return MRX_E_UNSUPPORTED;
     // the columns and per-row tables as bindGeometry lays them out: a row draws the object its id names
     const size_t n = num_instances;
-    std::vector<float> pos(3 * n + 1), rot(4 * n + 1), scale(3 * n + 1);
-    std::vector<int32_t> obj(n + 1), bound(n + 1);
-    std::vector<uint32_t> kBase(n + 1, 0);
-    std::vector<ObjInfo> info(n + 1);
+    g.pos.assign(3 * n + 1, 0.0f); g.rot.assign(4 * n + 1, 0.0f); g.scale.assign(3 * n + 1, 0.0f);
+    g.obj.assign(n + 1, 0); g.bound.assign(n + 1, 0);
+    g.kBase.assign(n + 1, 0u);
+    g.info.assign(n + 1, ObjInfo {});
     for (size_t i = 0; i < n; ++i) {
-        std::memcpy(&pos[3 * i], instances[i].position, 12);
-        std::memcpy(&rot[4 * i], instances[i].rotation, 16);
-        std::memcpy(&scale[3 * i], instances[i].scale, 12);
-        obj[i] = bound[i] = instances[i].object_id;
+        std::memcpy(&g.pos[3 * i], instances[i].position, 12);
+        std::memcpy(&g.rot[4 * i], instances[i].rotation, 16);
+        std::memcpy(&g.scale[3 * i], instances[i].scale, 12);
+        g.obj[i] = g.bound[i] = instances[i].object_id;
         ObjInfo oi {};
         oi.root = -1;
-        if (obj[i] >= 0 && (uint32_t)obj[i] < num_objects)
-            oi = blas.objects[obj[i]];
-        info[i] = oi;
+        if (g.obj[i] >= 0 && (uint32_t)g.obj[i] < num_objects)
+            oi = g.blas.objects[g.obj[i]];
+        g.info[i] = oi;
     }
     for (uint32_t w = 0; w < num_worlds; ++w) {
         uint32_t k = 0;
         for (uint32_t row = world_inst_start[w]; row < world_inst_start[w + 1]; ++row) {
-            kBase[row] = k;
-            k += info[row].numTris;
+            g.kBase[row] = k;
+            k += g.info[row].numTris;
         }
     }
+    g.tables = RayTables {};
+    g.tables.tris = g.tris.data();
+    g.tables.nodes = g.blas.nodes.data();
+    g.tables.leafTris = g.blas.leafTris.data();
+    g.tables.instInfo = g.info.data();
+    g.tables.instKBase = g.kBase.data();
+    g.tables.boundObj = g.bound.data();
+    g.tables.worldInstStart = world_inst_start;
+    g.tables.instPos = g.pos.data();
+    g.tables.instRot = g.rot.data();
+    g.tables.instScale = g.scale.data();
+    g.tables.instObj = g.obj.data();
+    return MRX_OK;
+}
+
+}  // namespace mrx
+
+extern "C" int mrx_trace_rays_host(const float *tri_pos, uint32_t num_tris, const int32_t *obj_first,
+                                   const int32_t *obj_count, uint32_t num_objects, const mrx_instance *instances,
+                                   uint32_t num_instances, const int32_t *labels_or_null,
+                                   const uint32_t *world_inst_start, uint32_t num_worlds, const int32_t *frame_or_null,
+                                   const float *rays, uint32_t rays_per_world, int brute, float *out_t, int32_t *out_id)
+{
+    using namespace mrx;
+    if (rays_per_world < 1 || rays_per_world > kRayMaxPerWorld || (uint64_t)num_worlds * rays_per_world >= (1ull << 31))
+        return MRX_E_INVALID;
+    if (!rays || !out_t || !out_id)
+        return MRX_E_INVALID;
+    RayHostScene g;
+    if (const int rc = rayHostScene(tri_pos, num_tris, obj_first, obj_count, num_objects, instances, num_instances,
+                                    world_inst_start, num_worlds, g))
+        return rc;
     RayParams p {};
-    p.s.tris = tris.data();
-    p.s.nodes = blas.nodes.data();
-    p.s.leafTris = blas.leafTris.data();
-    p.s.instInfo = info.data();
-    p.s.instKBase = kBase.data();
-    p.s.boundObj = bound.data();
-    p.s.worldInstStart = world_inst_start;
-    p.s.instPos = pos.data();
-    p.s.instRot = rot.data();
-    p.s.instScale = scale.data();
-    p.s.instObj = obj.data();
+    p.s = g.tables;
     p.s.instLabel = labels_or_null;
     p.rays = rays;
     p.frame = frame_or_null;
@@ -141,7 +159,7 @@ extern "C" int mrx_trace_rays_host(const float *tri_pos, uint32_t num_tris, cons
     p.outId = out_id;
     p.numWorlds = num_worlds;
     p.R = rays_per_world;
-    p.bvhDepth = blas.maxDepth;
+    p.bvhDepth = g.blas.maxDepth;
     p.numCUs = 1;
     p.brute = brute;
     traceRaysHost(p);

@@ -18,6 +18,7 @@
 #include "raster.hpp"
 #include "flow.hpp"
 #include "cloud.hpp"
+#include "shadow.hpp"
 #include "error.hpp"
 #include "shards.hpp"
 
@@ -222,6 +223,15 @@ struct mrx_renderer {
     DevBuf<float> cloudOut;
     DevBuf<int32_t> cloudPixel, cloudCount;
     DevBuf<uint32_t> cloudScratch;
+    // cast shadows (mrx_shadow_create): 0 off, 1 the mask, 2 the mask and the darkened rgb
+    // (mrx_shadows); the bias and the reach of the shadow rays; the [views][storage_slow][storage_fast] u8 mask the
+    // shadow stage writes from the depth tensor the caller sees -- an allocation of its own, outside allocOutputs and
+    // the placement search.  0: no pointer, no further launch.  shadowBrute: MRX_SHADOW_BRUTE, the form without culls;
+    // shadowPassRows: MRX_SHADOW_PASS_ROWS, the forced number of rows per staging pass (0: the default).
+    uint32_t shadows = 0, shadowPassRows = 0;
+    bool shadowBrute = false;
+    float shadowBias = 0.0f, shadowMaxDistance = 0.0f;
+    DevBuf<uint8_t> shadowMask;
     DevBuf<unsigned long long> stamps;
     // XCD phase feedback (raster.hip): a host-mapped word workgroup 0 reports its XCC id to
     uint32_t *xccHost = nullptr, *xccDev = nullptr;
@@ -283,6 +293,7 @@ struct mrx_renderer {
     hipError_t launchFlow();
     hipError_t launchFlowSnapshot();
     hipError_t launchCloud();
+    hipError_t launchShadow(bool apply);        // apply: a step's form of a renderer with shadows == 2
 
     ~mrx_renderer();
 };

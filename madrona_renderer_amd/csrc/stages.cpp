@@ -1,6 +1,7 @@
 // The post-render stages: what each launches, the table that lists them once in step order (kStages) and everything
 // that goes through it -- the step's stage loop, the shards' "run stage i" command, the stage entry points, the
-// tensors a creation flag allocates and the stages attached later (mrx_rays_create, mrx_flow_create, mrx_cloud_create).
+// tensors a creation flag allocates and the stages attached later (mrx_rays_create, mrx_flow_create, mrx_cloud_create,
+// mrx_shadow_create).
 #include "renderer.hpp"
 
 #include "resolve.hpp"
@@ -70,6 +71,52 @@ hipError_t mrx_renderer::launchCloud()
     q.numCUs = params.numCUs;
     q.forcedParts = cloudForcedParts;
     return mrx::launchCloud(q, stream);
+}
+
+// (depth, rgb, normals, the constants, the light and every table pointer are read from the render's parameters at every
+// launch: the placement search re-binds the tensors, mrx_set_view_projection / mrx_set_world_light the constants and
+// the light tables, bindGeometry the geometry tables; pose, scale, ObjectID, camera and table CONTENTS are read by the
+// kernel)
+hipError_t mrx_renderer::launchShadow(bool apply)
+{
+    mrx::ShadowParams q {};
+    q.s.tris = params.tris;
+    q.s.nodes = params.bvhNodes;
+    q.s.leafTris = params.bvhLeafTris;
+    q.s.instInfo = params.instInfo;
+    q.s.worldInstStart = params.worldInstStart;
+    q.s.instPos = params.instPos;
+    q.s.instRot = params.instRot;
+    q.s.instScale = params.instScale;
+    q.s.instObj = params.instObj;
+    q.viewWorld = params.viewWorld;
+    q.depth = ss > 1 ? outDepth.ptr : params.depth;
+    q.mask = shadowMask.ptr;
+    q.rgb = ss > 1 ? outRgb.ptr : params.rgb;
+    q.normal = ss > 1 ? outNormal.ptr : params.normal;
+    q.camPos = params.camPos;
+    q.camRot = params.camRot;
+    q.viewProj = params.viewProj;
+    q.sx = params.sx; q.ox = params.ox; q.sz = params.sz; q.oz = params.oz;
+    q.viewLight = params.viewLight;
+    for (int k = 0; k < 3; ++k)
+        q.toLight[k] = params.toLight[k];
+    q.ambient = params.ambient;
+    q.diffuse = params.diffuse;
+    q.numViews = params.numViews;
+    q.nfast = info.storage_fast;
+    q.nslow = info.storage_slow;
+    q.ss = ss;
+    q.half = ss / 2;
+    q.transposed = params.transposed;
+    q.apply = apply ? 1 : 0;
+    q.bias = shadowBias;
+    q.maxDistance = shadowMaxDistance;
+    q.bvhDepth = info.bvh_depth;
+    q.numCUs = params.numCUs;
+    q.passRows = shadowPassRows;
+    q.brute = shadowBrute ? 1 : 0;
+    return mrx::launchShadow(q, stream);
 }
 
 // (every table pointer is read from the render's parameters at every launch: bindGeometry re-binds them; pose, scale,
@@ -293,19 +340,25 @@ struct Stage {
     int (*alloc)(mrx_renderer &r);              // at creation, of a stage the flags switch on; null: an attached stage
     const char *call;                           // the launch as a HIP failure's text names it
     const char *off;                            // the MRX_E_UNSUPPORTED text of its entry point
+    bool inStep = true;                         // false: an entry point's form of a stage, never part of a step
 };
-enum : int { kStageResolve = 0, kStageUnproject, kStageBoxes, kStageObserve, kStageTrace, kStageFlow, kStageFlowSnapshot,
-             kStageCloud, kNumStages };
+enum : int { kStageResolve = 0, kStageUnproject, kStageShadow, kStageBoxes, kStageObserve, kStageTrace, kStageFlow,
+             kStageFlowSnapshot, kStageCloud, kStageShadowMask, kNumStages };
 
 // The stages in the order a step runs them; the snapshot after the flow that reads the one before it; the compaction
-// last: it reads the depth the caller sees, behind the resolve, and nothing reads what it writes.  A new stage is
-// an entry here, its launch, its fields in the renderer and its tensors in bufferOf.
+// last: it reads the depth the caller sees, behind the resolve, and nothing reads what it writes.  The shadow stage
+// runs behind the unprojection and ahead of the boxes and the observation: the observation packs the rgb it has
+// darkened, and neither the flow nor the cloud reads rgb.  Its last entry is mrx_shadow's: the mask-only form whatever
+// the renderer's, which no step runs.  A new stage is an entry here, its launch, its fields in the renderer and its
+// tensors in bufferOf.
 static const Stage kStages[kNumStages] = {
     { [](const mrx_renderer &r) { return r.ss > 1; }, [](mrx_renderer &r) { return r.launchResolve(); }, allocResolved,
       "launchResolve()", "nothing to resolve: this renderer was created without supersampling" },
     { [](const mrx_renderer &r) { return r.positions != 0; }, [](mrx_renderer &r) { return r.launchUnproject(); },
       allocPositions, "launchUnproject()",
       "nothing to unproject: this renderer was created without MRX_FLAG_POSITIONS" },
+    { [](const mrx_renderer &r) { return r.shadows != 0; }, [](mrx_renderer &r) { return r.launchShadow(r.shadows == 2); },
+      nullptr, "launchShadow()", "no shadows to cast: mrx_shadow_create was not called on this renderer" },
     { [](const mrx_renderer &r) { return r.boxLabels != 0; }, [](mrx_renderer &r) { return r.launchBoxes(); }, allocBoxes,
       "launchBoxes()", "no boxes to compute: this renderer was created without MRX_FLAG_BOX_LABELS" },
     { [](const mrx_renderer &r) { return r.obsLayout != 0; }, [](mrx_renderer &r) { return r.launchObserve(); },
@@ -319,6 +372,8 @@ static const Stage kStages[kNumStages] = {
       "launchFlowSnapshot()", "no optical flow: mrx_flow_create was not called on this renderer" },
     { [](const mrx_renderer &r) { return r.cloudPoints != 0; }, [](mrx_renderer &r) { return r.launchCloud(); }, nullptr,
       "launchCloud()", "no point cloud: mrx_cloud_create was not called on this renderer" },
+    { [](const mrx_renderer &r) { return r.shadows != 0; }, [](mrx_renderer &r) { return r.launchShadow(false); }, nullptr,
+      "launchShadow()", "no shadows to cast: mrx_shadow_create was not called on this renderer", false },
 };
 
 int allocStages(mrx_renderer &r)
@@ -334,7 +389,7 @@ hipError_t mrx_renderer::launch()
 {
     hipError_t e = launchRender();
     for (const Stage &s : kStages)
-        if (e == hipSuccess && s.on(*this))
+        if (e == hipSuccess && s.inStep && s.on(*this))
             e = s.launch(*this);
     return e;
 }
@@ -449,7 +504,7 @@ static int runStage(mrx_renderer *r, int stage)
     return stageLaunch(s, *r, "r->");
 }
 
-// an attached stage (mrx_rays_create, mrx_flow_create, mrx_cloud_create) on the renderer or on every shard of it, all or nothing: a
+// an attached stage (mrx_rays_create, mrx_flow_create, mrx_cloud_create, mrx_shadow_create) on the renderer or on every shard of it, all or nothing: a
 // shard that fails takes the stage of the shards before it along
 static int attachAll(mrx_renderer *r, uint32_t arg, int (*createOne)(mrx_renderer *, uint32_t),
                      void (*destroyOne)(mrx_renderer *))
@@ -478,6 +533,7 @@ int mrx_trace(mrx_renderer *r) { return runStage(r, kStageTrace); }
 int mrx_flow(mrx_renderer *r) { return runStage(r, kStageFlow); }
 int mrx_flow_snapshot(mrx_renderer *r) { return runStage(r, kStageFlowSnapshot); }
 int mrx_compact(mrx_renderer *r) { return runStage(r, kStageCloud); }
+int mrx_shadow(mrx_renderer *r) { return runStage(r, kStageShadowMask); }
 
 int mrx_supersample(mrx_renderer *r)
 {
@@ -758,6 +814,99 @@ int mrx_cloud_create(mrx_renderer *r, uint32_t points_per_view, int frame, float
 int mrx_cloud(mrx_renderer *r)
 {
     return r ? (int)r->cloudPoints : fail(MRX_E_INVALID, "null renderer");
+}
+
+// what the shadow stage reads and writes per step: 4 bytes of depth and the mask's byte per native pixel (what the
+// applying form touches on top depends on the image: no fixed term)
+static uint64_t shadowBytes(const mrx_renderer *r)
+{
+    return (uint64_t)r->info.num_views * r->info.storage_fast * r->info.storage_slow * 5ull;
+}
+
+// the stage of one renderer on one device: the mask, the first run in the mask-only form.  Bias and reach are in the
+// renderer already (mrx_shadow_create); `mode` is 1 or 2.
+static int shadowCreateOne(mrx_renderer *r, uint32_t mode)
+{
+    MRX_HIP(hipSetDevice(r->device));
+    const uint64_t px = (uint64_t)r->info.num_views * r->info.storage_fast * r->info.storage_slow;
+    // (a failure leaves the renderer without the stage: shadows is cleared again)
+    auto undo = [&](hipError_t e) {
+        r->shadows = 0;
+        r->shadowMask.release();
+        return fail(MRX_E_HIP, std::string("shadows: ") + hipGetErrorString(e));
+    };
+    const char *brute = std::getenv("MRX_SHADOW_BRUTE");
+    r->shadowBrute = brute && std::atoi(brute) != 0;
+    r->shadowPassRows = 0;
+    if (const char *dbg = std::getenv("MRX_SHADOW_PASS_ROWS"))  // tests: several staging passes at tiny sizes
+        r->shadowPassRows = (uint32_t)std::max(0, std::atoi(dbg));
+    hipError_t e = r->shadowMask.alloc((size_t)px);
+    if (e == hipSuccess) e = mrx::prepareShadow();
+    if (e == hipSuccess) e = hipMemsetAsync(r->shadowMask.ptr, 0xFF, (size_t)px, r->stream);
+    if (e != hipSuccess)
+        return undo(e);
+    r->shadows = mode;
+    e = r->launchShadow(false);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess)
+        return undo(e);
+    r->info.bytes_per_step += shadowBytes(r);
+    return MRX_OK;
+}
+
+// takes the stage off a shard again (mrx_shadow_create failed on a later one)
+static void shadowDestroyOne(mrx_renderer *r)
+{
+    (void)hipSetDevice(r->device);
+    (void)hipStreamSynchronize(r->stream);
+    r->info.bytes_per_step -= shadowBytes(r);
+    r->shadows = 0;
+    r->shadowMask.release();
+}
+
+int mrx_shadow_create(mrx_renderer *r, int apply, float bias, float max_distance)
+{
+    if (const int src = settle(r))
+        return src;
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (r->parent)
+        return fail(MRX_E_INVALID, "mrx_shadow_create on a shard: attach the stage to the renderer it belongs to");
+    if (r->shadows)
+        return fail(MRX_E_INVALID, "this renderer already casts shadows");
+    if (!(std::isfinite(bias) && bias >= 0.0f))
+        return fail(MRX_E_INVALID, "shadows: bias is finite and >= 0");
+    if (!(std::isfinite(max_distance) && max_distance > 0.0f))
+        return fail(MRX_E_INVALID, "shadows: max_distance is FLT_MAX (none) or finite and > 0");
+    const mrx_renderer *first = r->shards.empty() ? r : r->shards[0];
+    if (!first->depth.ptr)
+        return fail(MRX_E_INVALID, "shadows need depth: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)");
+    if (apply && !first->rgb.ptr)
+        return fail(MRX_E_INVALID, "shadows with apply need rgb: this renderer was created depth-only (MRX_FLAG_NO_RGB)");
+    if (apply && !first->normal.ptr)
+        return fail(MRX_E_INVALID, "shadows with apply need the normal tensor: create the renderer with MRX_FLAG_NORMALS");
+    mrx_info_t whole {};
+    if (infoFull(r, &whole) != MRX_OK)
+        return MRX_E_INVALID;
+    if ((uint64_t)whole.num_views * whole.storage_fast * whole.storage_slow > mrx::kShadowMaxPixels)
+        return fail(MRX_E_INVALID, "shadows: more than 2^32 - 1 native pixels");
+    const auto store = [&](mrx_renderer &sh) {
+        sh.shadowBias = bias;
+        sh.shadowMaxDistance = max_distance;
+    };
+    store(*r);
+    for (mrx_renderer *sh : r->shards)
+        store(*sh);
+    const uint32_t mode = apply ? 2u : 1u;
+    const int rc = attachAll(r, mode, shadowCreateOne, shadowDestroyOne);
+    if (rc == MRX_OK)
+        r->shadows = mode;                          // (of a renderer of several devices: the parent's, too)
+    return rc;
+}
+
+int mrx_shadows(mrx_renderer *r)
+{
+    return r ? (int)r->shadows : fail(MRX_E_INVALID, "null renderer");
 }
 
 int mrx_observations(mrx_renderer *r)
