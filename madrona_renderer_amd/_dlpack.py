@@ -1,7 +1,9 @@
 """Minimal DLPack (v0.8 ABI) export of the renderer's own memory, as the compiled module's Tensor.__dlpack__ builds it:
 what the pure-Python outputs (cloud.py, shadows.py) hand to torch.from_dlpack.  ctypes only; each capsule keeps its
-owner alive for as long as the consumer's tensor lives."""
+owner alive for as long as the consumer's tensor lives.  With it, what those modules share beside it: their handle of
+the C-ABI and the check of a float argument."""
 import ctypes
+import math
 
 kDLCPU, kDLROCM = 1, 10
 kDLInt, kDLUInt, kDLFloat = 0, 1, 2
@@ -103,6 +105,41 @@ def declare_buffers(lib):
     lib.mrx_buffer_shard.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.POINTER(ctypes.c_int64),
                                      ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int),
                                      ctypes.POINTER(ctypes.c_int)]
+
+
+_HANDLES = {}
+
+
+def private_capi(module, prototypes):
+    """The library load_capi() mapped, through a handle of `module`'s own: the prototypes set here -- `prototypes`, name
+    -> argument types of an entry that returns int, and the tensor export's -- are not imposed on other users of the
+    shared handle."""
+    if module not in _HANDLES:
+        from . import load_capi
+        lib = ctypes.CDLL(load_capi()._name)
+        for name, argtypes in prototypes.items():
+            getattr(lib, name).restype = ctypes.c_int
+            getattr(lib, name).argtypes = argtypes
+        declare_buffers(lib)
+        _HANDLES[module] = lib
+    return _HANDLES[module]
+
+
+def float32_argument(name, value, what, holds):
+    """`value` as a float where holds(value), for a finite number, also in single precision; else the ValueError that
+    says `name` must be `what`."""
+    if isinstance(value, bool) or not isinstance(value, (int, float)) or not math.isfinite(value) or not holds(value):
+        raise ValueError("%s must be %s, not %r" % (name, what, value))
+    # (the C-ABI takes a float32: a number that is finite, or positive, only in double precision is neither there)
+    as_f32 = ctypes.c_float(value).value
+    if not math.isfinite(as_f32) or not holds(as_f32):
+        raise ValueError("%s must be %s in single precision, not %r" % (name, what, value))
+    return float(value)
+
+
+def positive_or_none(name, value):
+    """None, or a finite positive number, also in single precision"""
+    return None if value is None else float32_argument(name, value, "None or a finite positive number", lambda v: v > 0)
 
 
 def last_error(lib):

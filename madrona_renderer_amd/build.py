@@ -19,7 +19,7 @@ CSRC = os.path.join(HERE, "csrc")
 ARCH = "gfx950"
 
 HIP_SOURCES = ["raster.hip", "bvh.hip", "resolve.hip", "unproject.hip", "boxes.hip", "observe.hip", "rays.hip", "rays_host.cpp", "flow.hip", "flow_host.cpp", "cloud.hip", "cloud_host.cpp", "shadow.hip", "shadow_host.cpp", "bvh.cpp", "mrx_api.cpp", "scene.cpp", "stages.cpp", "shards.cpp", "host_tools.cpp", "assets.cpp", "ktx2.cpp"]
-HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "observe.hpp", "rays.hpp", "rays_core.hpp", "flow.hpp", "flow_core.hpp", "cloud.hpp", "cloud_core.hpp", "shadow.hpp", "shadow_core.hpp", "assets.hpp", "bc7_tables.inc",
+HIP_DEPS = HIP_SOURCES + ["raster.hpp", "raster_dev.hpp", "bvh.hpp", "resolve.hpp", "unproject.hpp", "boxes.hpp", "observe.hpp", "rays.hpp", "rays_core.hpp", "flow.hpp", "flow_core.hpp", "cloud.hpp", "cloud_core.hpp", "shadow.hpp", "shadow_core.hpp", "stage_core.hpp", "assets.hpp", "bc7_tables.inc",
                           "renderer.hpp", "shards.hpp", "error.hpp",
                           "../../include/mrx.h"]
 MGR_SOURCES = ["manager.cpp"]
@@ -140,137 +140,65 @@ def build_headless(force=False, verbose=False):
     return out
 
 
-def asan_driver_path():
-    return os.path.join(ROOT, "build", "host_asan_driver")
+# The sanitizer builds of host code, each with its stand-alone driver csrc/<name>.cpp: host compiler only (the HIP
+# runtime header bvh.hpp pulls in is declarations), run by the CPU tests as stand-alone programs -- never on the GPU box.
+# name -> (sources behind the driver, headers, flags, libraries)
+_ASAN = ["-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
+         "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
+_STRICT = ["-ffp-contract=off"] + _ASAN             # the stages' arithmetic: one rounding per operation
+_ASSETS = ["bvh.cpp", "assets.cpp", "ktx2.cpp"]
+_ASSET_DEPS = ["assets.hpp", "bvh.hpp", "raster.hpp", "bc7_tables.inc"]
+_STAGE_DEPS = ["stage_core.hpp", "bvh.hpp", "raster.hpp", "host_driver.hpp", "../../include/mrx.h"]
+DRIVERS = {
+    # the host code that reads untrusted input: OBJ / MTL / PNG / KTX2 / BC7 readers, BLAS builder (test_sanitizers.py)
+    "host_asan_driver": (["assets.cpp", "ktx2.cpp", "bvh.cpp"], _ASSET_DEPS + ["host_driver.hpp"], _ASAN, ["-lz", "-ldl"]),
+    # the ray-cast sensor's host entry: rays_core.hpp on the CPU, over the BLAS builder (test_ray_cpu.py)
+    "rays_host_driver": (["rays_host.cpp"] + _ASSETS, ["rays.hpp", "rays_core.hpp"] + _STAGE_DEPS + _ASSET_DEPS,
+                         _STRICT, ["-lz", "-ldl"]),
+    # the optical-flow output's host entry: flow_core.hpp on the CPU (test_flow_cpu.py)
+    "flow_host_driver": (["flow_host.cpp"], ["flow.hpp", "flow_core.hpp"] + _STAGE_DEPS, _STRICT, []),
+    # the point-cloud output's host entry: cloud_core.hpp on the CPU (test_cloud_cpu.py)
+    "cloud_host_driver": (["cloud_host.cpp"], ["cloud.hpp", "cloud_core.hpp"] + _STAGE_DEPS, _STRICT, []),
+    # the shadow stage's host entry: shadow_core.hpp on the CPU, over the host scene of rays_host.cpp and the BLAS
+    # builder (test_shadow_cpu.py)
+    "shadow_host_driver": (["shadow_host.cpp", "rays_host.cpp"] + _ASSETS,
+                           ["shadow.hpp", "shadow_core.hpp", "cloud_core.hpp", "rays.hpp", "rays_core.hpp"] +
+                           _STAGE_DEPS + _ASSET_DEPS, _STRICT, ["-lz", "-ldl"]),
+    # ThreadSanitizer: the shard-worker protocol (shards.cpp: no HIP in it); the driver's stub callback stands in for
+    # the renderer (test_sanitizers.py)
+    "shards_tsan_driver": (["shards.cpp"], ["shards.hpp", "error.hpp", "../../include/mrx.h"],
+                           ["-fsanitize=thread", "-fno-omit-frame-pointer"], ["-lpthread"]),
+}
 
 
-def build_asan(force=False, verbose=False):
-    """AddressSanitizer + UBSan build of the host code that reads untrusted input (OBJ / MTL /
-    PNG / KTX2 / BC7 readers, BLAS builder) with its driver, csrc/host_asan_driver.cpp.  Host
-    compiler only (the HIP runtime header bvh.hpp pulls in is declarations); run by
-    tests/test_sanitizers.py on the CPU -- never on the GPU box."""
-    out = asan_driver_path()
-    srcs = ["host_asan_driver.cpp", "assets.cpp", "ktx2.cpp", "bvh.cpp"]
-    deps = srcs + ["assets.hpp", "bvh.hpp", "raster.hpp", "bc7_tables.inc"]
-    if force or _stale(out, deps):
+def driver_path(name):
+    return os.path.join(ROOT, "build", name)
+
+
+def build_driver(name, force=False, verbose=False):
+    srcs, deps, flags, libs = DRIVERS[name]
+    srcs = [name + ".cpp"] + srcs
+    out = driver_path(name)
+    if force or _stale(out, srcs + deps):
         os.makedirs(os.path.dirname(out), exist_ok=True)
-        cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=address,undefined",
-               "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-               "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
-        cmd += [os.path.join(CSRC, s) for s in srcs]
-        cmd += ["-lz", "-ldl", "-o", out]
-        _run(cmd, verbose)
+        _run(["g++", "-O1", "-g", "-std=c++17", "-Wall"] + flags + [os.path.join(CSRC, s) for s in srcs] + libs +
+             ["-o", out], verbose)
     return out
 
 
-def rays_driver_path():
-    return os.path.join(ROOT, "build", "rays_host_driver")
-
-
-def build_rays_driver(force=False, verbose=False):
-    """AddressSanitizer + UBSan build of the ray-cast sensor's host entry (rays_host.cpp: rays_core.hpp on the
-    CPU, over the BLAS builder) with its driver, csrc/rays_host_driver.cpp.  Host compiler only; run by
-    tests/test_ray_cpu.py on the CPU -- never on the GPU box."""
-    out = rays_driver_path()
-    srcs = ["rays_host_driver.cpp", "rays_host.cpp", "bvh.cpp", "assets.cpp", "ktx2.cpp"]
-    deps = srcs + ["rays.hpp", "rays_core.hpp", "assets.hpp", "bvh.hpp", "raster.hpp", "bc7_tables.inc",
-                   "../../include/mrx.h"]
-    if force or _stale(out, deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
-               "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-               "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
-        cmd += [os.path.join(CSRC, s) for s in srcs]
-        cmd += ["-lz", "-ldl", "-o", out]
-        _run(cmd, verbose)
-    return out
-
-
-def flow_driver_path():
-    return os.path.join(ROOT, "build", "flow_host_driver")
-
-
-def build_flow_driver(force=False, verbose=False):
-    """AddressSanitizer + UBSan build of the optical-flow output's host entry (flow_host.cpp: flow_core.hpp on the
-    CPU) with its driver, csrc/flow_host_driver.cpp.  Host compiler only; run by tests/test_flow_cpu.py on the
-    CPU, as a stand-alone program -- never on the GPU box."""
-    out = flow_driver_path()
-    srcs = ["flow_host_driver.cpp", "flow_host.cpp"]
-    deps = srcs + ["flow.hpp", "flow_core.hpp", "raster.hpp", "../../include/mrx.h"]
-    if force or _stale(out, deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
-               "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-               "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
-        cmd += [os.path.join(CSRC, s) for s in srcs]
-        cmd += ["-o", out]
-        _run(cmd, verbose)
-    return out
-
-
-def cloud_driver_path():
-    return os.path.join(ROOT, "build", "cloud_host_driver")
-
-
-def build_cloud_driver(force=False, verbose=False):
-    """AddressSanitizer + UBSan build of the point-cloud output's host entry (cloud_host.cpp: cloud_core.hpp on the
-    CPU) with its driver, csrc/cloud_host_driver.cpp.  Host compiler only; run by tests/test_cloud_cpu.py on the
-    CPU, as a stand-alone program -- never on the GPU box."""
-    out = cloud_driver_path()
-    srcs = ["cloud_host_driver.cpp", "cloud_host.cpp"]
-    deps = srcs + ["cloud.hpp", "cloud_core.hpp", "raster.hpp", "../../include/mrx.h"]
-    if force or _stale(out, deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
-               "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-               "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
-        cmd += [os.path.join(CSRC, s) for s in srcs]
-        cmd += ["-o", out]
-        _run(cmd, verbose)
-    return out
-
-
-def shadow_driver_path():
-    return os.path.join(ROOT, "build", "shadow_host_driver")
-
-
-def build_shadow_driver(force=False, verbose=False):
-    """AddressSanitizer + UBSan build of the shadow stage's host entry (shadow_host.cpp: shadow_core.hpp on the CPU,
-    over the host scene of rays_host.cpp and the BLAS builder) with its driver, csrc/shadow_host_driver.cpp.  Host
-    compiler only; run by tests/test_shadow_cpu.py on the CPU, as a stand-alone program -- never on the GPU box."""
-    out = shadow_driver_path()
-    srcs = ["shadow_host_driver.cpp", "shadow_host.cpp", "rays_host.cpp", "bvh.cpp", "assets.cpp", "ktx2.cpp"]
-    deps = srcs + ["shadow.hpp", "shadow_core.hpp", "cloud_core.hpp", "rays.hpp", "rays_core.hpp", "assets.hpp",
-                   "bvh.hpp", "raster.hpp", "bc7_tables.inc", "../../include/mrx.h"]
-    if force or _stale(out, deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-ffp-contract=off", "-fsanitize=address,undefined",
-               "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer",
-               "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include"]
-        cmd += [os.path.join(CSRC, s) for s in srcs]
-        cmd += ["-lz", "-ldl", "-o", out]
-        _run(cmd, verbose)
-    return out
-
-
-def shards_driver_path():
-    return os.path.join(ROOT, "build", "shards_tsan_driver")
-
-
-def build_shards_driver(force=False, verbose=False):
-    """ThreadSanitizer build of the shard-worker protocol (shards.cpp: no HIP in it) with its driver,
-    csrc/shards_tsan_driver.cpp, whose stub callback stands in for the renderer.  Host compiler only; run by
-    tests/test_sanitizers.py on the CPU, as a stand-alone program -- never on the GPU box."""
-    out = shards_driver_path()
-    srcs = ["shards_tsan_driver.cpp", "shards.cpp"]
-    deps = srcs + ["shards.hpp", "error.hpp", "../../include/mrx.h"]
-    if force or _stale(out, deps):
-        os.makedirs(os.path.dirname(out), exist_ok=True)
-        cmd = ["g++", "-O1", "-g", "-std=c++17", "-Wall", "-fsanitize=thread", "-fno-omit-frame-pointer"]
-        cmd += [os.path.join(CSRC, s) for s in srcs]
-        cmd += ["-lpthread", "-o", out]
-        _run(cmd, verbose)
-    return out
+# the names the tests and the scripts use
+def build_asan(force=False, verbose=False): return build_driver("host_asan_driver", force, verbose)
+def build_rays_driver(force=False, verbose=False): return build_driver("rays_host_driver", force, verbose)
+def build_flow_driver(force=False, verbose=False): return build_driver("flow_host_driver", force, verbose)
+def build_cloud_driver(force=False, verbose=False): return build_driver("cloud_host_driver", force, verbose)
+def build_shadow_driver(force=False, verbose=False): return build_driver("shadow_host_driver", force, verbose)
+def build_shards_driver(force=False, verbose=False): return build_driver("shards_tsan_driver", force, verbose)
+def asan_driver_path(): return driver_path("host_asan_driver")
+def rays_driver_path(): return driver_path("rays_host_driver")
+def flow_driver_path(): return driver_path("flow_host_driver")
+def cloud_driver_path(): return driver_path("cloud_host_driver")
+def shadow_driver_path(): return driver_path("shadow_host_driver")
+def shards_driver_path(): return driver_path("shards_tsan_driver")
 
 
 def build_all(force=False, verbose=False):
@@ -282,17 +210,12 @@ def build_all(force=False, verbose=False):
 
 
 if __name__ == "__main__":
-    if "--asan" in sys.argv:
-        print(build_asan(force="--force" in sys.argv, verbose=True))
-    elif "--flow-driver" in sys.argv:
-        print(build_flow_driver(force="--force" in sys.argv, verbose=True))
-    elif "--cloud-driver" in sys.argv:
-        print(build_cloud_driver(force="--force" in sys.argv, verbose=True))
-    elif "--shadow-driver" in sys.argv:
-        print(build_shadow_driver(force="--force" in sys.argv, verbose=True))
-    elif "--shards-driver" in sys.argv:
-        print(build_shards_driver(force="--force" in sys.argv, verbose=True))
-    elif "--rays-driver" in sys.argv:
-        print(build_rays_driver(force="--force" in sys.argv, verbose=True))
+    force = "--force" in sys.argv
+    flags = {"--asan": build_asan, "--rays-driver": build_rays_driver, "--flow-driver": build_flow_driver,
+             "--cloud-driver": build_cloud_driver, "--shadow-driver": build_shadow_driver,
+             "--shards-driver": build_shards_driver}
+    chosen = [fn for flag, fn in flags.items() if flag in sys.argv]
+    if chosen:
+        print(chosen[0](force=force, verbose=True))
     else:
-        print("\n".join(build_all(force="--force" in sys.argv, verbose=True)))
+        print("\n".join(build_all(force=force, verbose=True)))

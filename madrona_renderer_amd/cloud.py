@@ -12,9 +12,7 @@ Pure Python over ``load_capi()``: no rendering code, no fallback.  The tensors a
 handed to torch as DLPack capsules built with ctypes; each keeps the renderer alive.
 """
 import ctypes
-import math
 
-from . import load_capi
 from . import _dlpack
 # (the DLPack helpers live in _dlpack.py, shared with shadows.py; the names this module always had stay)
 from ._dlpack import Exported as _Exported, _LIVE, kDLCPU as _kDLCPU, kDLInt as _kDLInt, kDLFloat as _kDLFloat  # noqa: F401
@@ -32,36 +30,13 @@ def _check_arguments(points, frame, max_depth):
         raise ValueError("points must be an int in 1 ... %d, not %r" % (MAX_POINTS, points))
     if not isinstance(frame, str) or frame not in FRAMES:
         raise ValueError("frame must be \"world\" or \"view\", not %r" % (frame,))
-    if max_depth is None:
-        return points, FRAMES[frame], 0.0
-    if isinstance(max_depth, bool) or not isinstance(max_depth, (int, float)) or not math.isfinite(max_depth) \
-            or not max_depth > 0:
-        raise ValueError("max_depth must be None or a finite positive number, not %r" % (max_depth,))
-    # (the C-ABI takes a float32: a number that is finite and positive only in double precision is neither there)
-    as_f32 = ctypes.c_float(max_depth).value
-    if not math.isfinite(as_f32) or not as_f32 > 0:
-        raise ValueError("max_depth must be None or a finite positive number in single precision, not %r" % (max_depth,))
-    return points, FRAMES[frame], float(max_depth)
-
-
-_LIB = None
+    return points, FRAMES[frame], _dlpack.positive_or_none("max_depth", max_depth) or 0.0
 
 
 def _capi():
-    """The library load_capi() mapped, through a handle of this module's own: the prototypes set here are not imposed
-    on other users of the shared handle."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    lib = ctypes.CDLL(load_capi()._name)
-    lib.mrx_cloud_create.restype = ctypes.c_int
-    lib.mrx_cloud_create.argtypes = [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_float]
-    for name in ("mrx_compact", "mrx_cloud"):
-        getattr(lib, name).restype = ctypes.c_int
-        getattr(lib, name).argtypes = [ctypes.c_void_p]
-    _dlpack.declare_buffers(lib)
-    _LIB = lib
-    return lib
+    return _dlpack.private_capi(__name__, {
+        "mrx_cloud_create": [ctypes.c_void_p, ctypes.c_uint32, ctypes.c_int, ctypes.c_float],
+        "mrx_compact": [ctypes.c_void_p], "mrx_cloud": [ctypes.c_void_p]})
 
 
 _error = _dlpack.last_error

@@ -5,15 +5,11 @@
 // of a background pixel chosen by a select -- so that a filled slot holds the bits MRX_BUF_POSITION holds at its pixel.
 #pragma once
 
-#include <cstddef>
 #include <cstdint>
 
-#include "raster.hpp"
+#include "stage_core.hpp"
 
 namespace mrx {
-
-static_assert(offsetof(ViewProj, sx) == 0 && offsetof(ViewProj, ox) == 4 && offsetof(ViewProj, sz) == 8 &&
-              offsetof(ViewProj, oz) == 12, "ViewProj begins with sx ox sz oz");
 
 constexpr uint32_t kCloudBlock = 512;           // lanes of a workgroup: eight waves
 constexpr uint32_t kCloudWaves = 8;
@@ -70,21 +66,9 @@ MRX_HD inline CloudView cloudLoadView(const float *camRot, const float *camPos, 
                                       const float *uniform, uint32_t v)
 {
     CloudView o;
-    if (viewProj) {
-        o.sx = viewProj[v].sx; o.ox = viewProj[v].ox; o.sz = viewProj[v].sz; o.oz = viewProj[v].oz;
-    } else {
-        o.sx = uniform[0]; o.ox = uniform[1]; o.sz = uniform[2]; o.oz = uniform[3];
-    }
+    loadProjection(viewProj, uniform, v, o.sx, o.ox, o.sz, o.oz);
     if constexpr (WORLD) {
-        const float *q = camRot + 4 * (size_t)v;
-        const float w = q[0], x = q[1], y = q[2], z = q[3];
-        const float x2 = x + x, y2 = y + y, z2 = z + z;
-        const float xx = x * x2, yy = y * y2, zz = z * z2;
-        const float xy = x * y2, xz = x * z2, yz = y * z2;
-        const float wx = w * x2, wy = w * y2, wz = w * z2;
-        o.R[0] = 1.0f - (yy + zz); o.R[1] = xy - wz;          o.R[2] = xz + wy;
-        o.R[3] = xy + wz;          o.R[4] = 1.0f - (xx + zz); o.R[5] = yz - wx;
-        o.R[6] = xz - wy;          o.R[7] = yz + wx;          o.R[8] = 1.0f - (xx + yy);
+        quatRotation(camRot + 4 * (size_t)v, o.R);
         for (int i = 0; i < 3; ++i)
             o.c[i] = camPos[3 * (size_t)v + i];
     } else {
@@ -100,21 +84,14 @@ template <bool WORLD>
 MRX_HD inline void cloudUnproject(const CloudView &v, uint32_t s, uint32_t half, uint32_t x, uint32_t y, float d,
                                   float *out)
 {
-    const float px = (float)(s * x + half);
-    const float py = (float)(s * y + half);
-    const float rx = px * v.sx + v.ox;
-    const float rz = py * v.sz + v.oz;
-    const float vx = d * rx, vy = d, vz = d * rz;
-    float ox = vx, oy = vy, oz = vz;
-    if constexpr (WORLD) {
-        ox = ((v.R[0] * vx + v.R[1] * vy) + v.R[2] * vz) + v.c[0];
-        oy = ((v.R[3] * vx + v.R[4] * vy) + v.R[5] * vz) + v.c[1];
-        oz = ((v.R[6] * vx + v.R[7] * vy) + v.R[8] * vz) + v.c[2];
-    }
+    const ViewPoint q = viewPoint(v.sx, v.ox, v.sz, v.oz, s, half, x, y, d);
+    float o[3] = { q.v[0], q.v[1], q.v[2] };
+    if constexpr (WORLD)
+        rotateAdd(v.R, q.v, v.c, o);
     const bool hit = !(d == 0.0f);
-    out[0] = hit ? ox : 0.0f;
-    out[1] = hit ? oy : 0.0f;
-    out[2] = hit ? oz : 0.0f;
+    out[0] = hit ? o[0] : 0.0f;
+    out[1] = hit ? o[1] : 0.0f;
+    out[2] = hit ? o[2] : 0.0f;
     out[3] = hit ? 1.0f : 0.0f;
 }
 

@@ -9,32 +9,7 @@
 // both frames, with and without a far crop, over a sparse and a dense depth, with 1, 2, 3 and 7 parts per view, which
 // must agree bit for bit; every output is checked against the definition -- count, order, slot rule --; a disagreement
 // or a sanitizer report fails the run.
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-#include <vector>
-
-#include "../../include/mrx.h"
-
-namespace {
-
-uint64_t rng(uint64_t &s)
-{
-    s += 0x9E3779B97F4A7C15ull;
-    uint64_t z = s;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-float uni(uint64_t &s, float lo, float hi) { return lo + (hi - lo) * (float)((rng(s) >> 40) * (1.0 / 16777216.0)); }
-
-template <typename T>
-std::unique_ptr<T[]> block(size_t n) { return std::unique_ptr<T[]>(new T[n ? n : 1]); }
-
-}  // namespace
+#include "host_driver.hpp"
 
 int main(int argc, char **argv)
 {
@@ -51,14 +26,7 @@ int main(int argc, char **argv)
     auto camPos = block<float>(3 * (size_t)views), camRot = block<float>(4 * (size_t)views);
     auto consts = block<float>(4 * (size_t)views);
     for (size_t v = 0; v < views; ++v) {
-        float len = 0.0f;
-        for (int c = 0; c < 4; ++c) {
-            camRot[4 * v + c] = uni(s, -1.0f, 1.0f);
-            len += camRot[4 * v + c] * camRot[4 * v + c];
-        }
-        len = std::sqrt(len > 0.0f ? len : 1.0f);
-        for (int c = 0; c < 4; ++c)
-            camRot[4 * v + c] /= len;
+        unit(s, &camRot[4 * v], 4);
         for (int c = 0; c < 3; ++c)
             camPos[3 * v + c] = uni(s, -20.0f, 20.0f);
         consts[4 * v] = uni(s, 0.002f, 0.2f); consts[4 * v + 1] = uni(s, -1.5f, -0.5f);

@@ -5,16 +5,11 @@
 // (tests/flow_oracle.py).  The divisions are IEEE divisions: no fast-math flag on either compile line.
 #pragma once
 
-#include <cstddef>
 #include <cstdint>
 
-#include "raster.hpp"
+#include "stage_core.hpp"
 
 namespace mrx {
-
-// the snapshot kernel and the host entry take sx ox sz oz as the first 16 bytes of a view's record
-static_assert(offsetof(ViewProj, sx) == 0 && offsetof(ViewProj, ox) == 4 && offsetof(ViewProj, sz) == 8 &&
-              offsetof(ViewProj, oz) == 12, "ViewProj begins with sx ox sz oz");
 
 constexpr uint32_t kFlowBlock = 256;        // pixels of one work item, one per lane
 constexpr uint32_t kFlowPassRows = 64;      // staged rows of one pass (MRX_FLOW_PASS_ROWS forces fewer)
@@ -48,38 +43,11 @@ struct FlowView {
     float sxp, oxp, szp, ozp;   // the snapshot's
 };
 
-// S1, the quaternion (w, x, y, z) used as given
-MRX_HD inline void flowRotation(const float *q, float *R)
-{
-    const float w = q[0], x = q[1], y = q[2], z = q[3];
-    const float x2 = x + x, y2 = y + y, z2 = z + z;
-    const float xx = x * x2, yy = y * y2, zz = z * z2;
-    const float xy = x * y2, xz = x * z2, yz = y * z2;
-    const float wx = w * x2, wy = w * y2, wz = w * z2;
-    R[0] = 1.0f - (yy + zz); R[1] = xy - wz;          R[2] = xz + wy;
-    R[3] = xy + wz;          R[4] = 1.0f - (xx + zz); R[5] = yz - wx;
-    R[6] = xz - wy;          R[7] = yz + wx;          R[8] = 1.0f - (xx + yy);
-}
-
-// R * v + t, S13's order
-MRX_HD inline void flowApply(const float *R, const float *v, const float *t, float *out)
-{
-    for (int i = 0; i < 3; ++i)
-        out[i] = ((R[3 * i] * v[0] + R[3 * i + 1] * v[1]) + R[3 * i + 2] * v[2]) + t[i];
-}
-
-// R^T * v, step 4's order
-MRX_HD inline void flowApplyT(const float *R, const float *v, float *out)
-{
-    for (int j = 0; j < 3; ++j)
-        out[j] = (R[j] * v[0] + R[3 + j] * v[1]) + R[6 + j] * v[2];
-}
-
 MRX_HD inline void flowStageRow(uint32_t row, uint32_t kBase, const FlowPose &live, const FlowPose &prev, FlowRow &out)
 {
     out.kBase = kBase;
-    flowRotation(live.instRot + 4 * (size_t)row, out.R);
-    flowRotation(prev.instRot + 4 * (size_t)row, out.Rp);
+    quatRotation(live.instRot + 4 * (size_t)row, out.R);
+    quatRotation(prev.instRot + 4 * (size_t)row, out.Rp);
     for (int c = 0; c < 3; ++c) {
         out.is[c] = 1.0f / live.instScale[3 * (size_t)row + c];
         out.p[c] = live.instPos[3 * (size_t)row + c];
@@ -92,12 +60,13 @@ MRX_HD inline void flowStageRow(uint32_t row, uint32_t kBase, const FlowPose &li
 MRX_HD inline void flowLoadView(uint32_t v, const FlowPose &live, const FlowPose &prev, const ViewProj *viewProj,
                                 const float *uniform, const float *prevProj, FlowView &o)
 {
-    flowRotation(live.camRot + 4 * (size_t)v, o.R);
-    flowRotation(prev.camRot + 4 * (size_t)v, o.Rp);
+    quatRotation(live.camRot + 4 * (size_t)v, o.R);
+    quatRotation(prev.camRot + 4 * (size_t)v, o.Rp);
     for (int c = 0; c < 3; ++c) {
         o.c[c] = live.camPos[3 * (size_t)v + c];
         o.cp[c] = prev.camPos[3 * (size_t)v + c];
     }
+    // (stage_core.hpp's loadProjection, written out: `o` is in LDS, and through the call the kernel's stores to it change)
     if (viewProj) {
         o.sx = viewProj[v].sx; o.ox = viewProj[v].ox; o.sz = viewProj[v].sz; o.oz = viewProj[v].oz;
     } else {
@@ -127,24 +96,26 @@ MRX_HD inline uint32_t flowFindRow(const FlowRow *rows, uint32_t n, uint32_t k)
 MRX_HD inline void flowPixel(const FlowView &v, const FlowRow &row, uint32_t s, uint32_t half, uint32_t x, uint32_t y,
                              float d, float *out)
 {
+    // (S13's view-space point, written out: through stage_core.hpp's viewPoint the kernel's instructions come in another
+    // order)
     const float px = (float)(s * x + half);
     const float py = (float)(s * y + half);
     const float rx = px * v.sx + v.ox;
     const float rz = py * v.sz + v.oz;
     const float pv[3] = { d * rx, d, d * rz };
     float P[3];
-    flowApply(v.R, pv, v.c, P);
+    rotateAdd(v.R, pv, v.c, P);
     // into the instance's frame, out again with the previous pose
     const float u[3] = { P[0] - row.p[0], P[1] - row.p[1], P[2] - row.p[2] };
     float l[3];
-    flowApplyT(row.R, u, l);
+    rotateT(row.R, u, l);
     const float n[3] = { (l[0] * row.is[0]) * row.sp[0], (l[1] * row.is[1]) * row.sp[1], (l[2] * row.is[2]) * row.sp[2] };
     float Pp[3];
-    flowApply(row.Rp, n, row.pp, Pp);
+    rotateAdd(row.Rp, n, row.pp, Pp);
     // into the previous view
     const float up[3] = { Pp[0] - v.cp[0], Pp[1] - v.cp[1], Pp[2] - v.cp[2] };
     float pvp[3];
-    flowApplyT(v.Rp, up, pvp);
+    rotateT(v.Rp, up, pvp);
     const float Y = pvp[1];
     const bool valid = Y > 0.0f;        // false for a NaN
     const float pxp = (pvp[0] / Y - v.oxp) / v.sxp;

@@ -9,45 +9,7 @@
 // write, so that a read or write past an end is a report.  Each case runs in both storage orders, with uniform and
 // with per-view constants, and with the default staging pass and passes of 1 and 3 rows, which must agree bit for bit;
 // a disagreement or a sanitizer report fails the run.
-#include <cmath>
-#include <cstdint>
-#include <cstdio>
-#include <cstdlib>
-#include <cstring>
-#include <memory>
-
-#include "../../include/mrx.h"
-
-namespace {
-
-uint64_t rng(uint64_t &s)
-{
-    s += 0x9E3779B97F4A7C15ull;
-    uint64_t z = s;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-float uni(uint64_t &s, float lo, float hi) { return lo + (hi - lo) * (float)((rng(s) >> 40) * (1.0 / 16777216.0)); }
-
-template <typename T>
-std::unique_ptr<T[]> block(size_t n) { return std::unique_ptr<T[]>(new T[n]); }
-
-void fillQuats(float *q, size_t n, uint64_t &s)
-{
-    for (size_t i = 0; i < n; ++i) {
-        float len = 0.0f;
-        for (int c = 0; c < 4; ++c) {
-            q[4 * i + c] = uni(s, -1.0f, 1.0f);
-            len += q[4 * i + c] * q[4 * i + c];
-        }
-        len = std::sqrt(len > 0.0f ? len : 1.0f);
-        for (int c = 0; c < 4; ++c)
-            q[4 * i + c] /= len;
-    }
-}
-
-}  // namespace
+#include "host_driver.hpp"
 
 int main(int argc, char **argv)
 {
@@ -96,8 +58,10 @@ int main(int argc, char **argv)
         }
         for (size_t i = 0; i < 3 * (size_t)views; ++i)
             pose[t][3][i] = uni(s, -20.0f, 20.0f);
-        fillQuats(pose[t][1].get(), I, s);
-        fillQuats(pose[t][4].get(), views, s);
+        for (size_t i = 0; i < I; ++i)
+            unit(s, &pose[t][1][4 * i], 4);
+        for (size_t v = 0; v < views; ++v)
+            unit(s, &pose[t][4][4 * v], 4);
     }
     auto consts = block<float>(4 * (size_t)views), prevConsts = block<float>(4 * (size_t)views);
     for (size_t v = 0; v < views; ++v)

@@ -22,6 +22,7 @@
 
 #include "assets.hpp"
 #include "bvh.hpp"
+#include "host_driver.hpp"
 
 namespace {
 
@@ -79,15 +80,6 @@ uint64_t readOne(const std::string &path, bool &ok)
         }
     }
     return h;
-}
-
-uint64_t rng(uint64_t &s)
-{
-    s += 0x9E3779B97F4A7C15ull;
-    uint64_t z = s;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
 }
 
 int fuzz(const std::string &path, int iters, uint64_t seed)

@@ -167,10 +167,7 @@ mrx_renderer::~mrx_renderer()
     position.release();
     boxes.release();
     obs.release(); obsReset.release();
-    rays.release(); rayT.release(); rayFrame.release(); rayId.release(); rayBound.release();
-    flowOut.release(); flowSnap.release();
-    cloudOut.release(); cloudPixel.release(); cloudCount.release(); cloudScratch.release();
-    shadowMask.release();
+    releaseAttached(*this);
     if (xccHost) (void)hipHostFree(xccHost);
     bvhNodes.release(); bvhLeafTris.release(); worldInstStart.release();
     viewWorld.release(); instKBase.release(); objInfo.release();

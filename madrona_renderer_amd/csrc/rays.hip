@@ -26,36 +26,6 @@ namespace mrx {
 
 namespace {
 
-// the traversal stack of one lane: entry e lies at base[e * kRayBlock], the lanes of an entry side by side
-struct LdsStack {
-    uint32_t *base;
-    uint32_t sp, cap;
-    __device__ __forceinline__ bool push(uint32_t v)
-    {
-        if (sp >= cap)
-            return false;
-        base[sp * kRayBlock] = v;
-        ++sp;
-        return true;
-    }
-    __device__ __forceinline__ bool pop(uint32_t &v)
-    {
-        if (sp == 0)
-            return false;
-        --sp;
-        v = base[sp * kRayBlock];
-        return true;
-    }
-};
-
-typedef __attribute__((address_space(4))) float ConstFloat;
-
-__device__ __forceinline__ float uniformF(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ uint32_t uniformU(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
 // a staged row, the same in every lane, moved to SGPRs
 __device__ __forceinline__ RayRow uniformRow(const RayRow &in)
 {
@@ -112,7 +82,7 @@ __global__ __launch_bounds__(kRayBlock) void rayKernel(const RayArgs a)
     // any other ray
     const bool dead = !BRUTE && rayDegenerate(ray);
     RayBest best { 0.0f, kRayNoHit, -1 };
-    LdsStack stack { stackMem + threadIdx.x, 0u, a.stackCap };
+    LaneStack<kRayBlock> stack { stackMem + threadIdx.x, 0u, a.stackCap };
 
     for (uint32_t base = rowLo; base < rowHi; base += a.passRows) {
         const uint32_t n = min(a.passRows, rowHi - base);

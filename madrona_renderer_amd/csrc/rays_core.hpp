@@ -9,7 +9,7 @@
 
 #include <cstdint>
 
-#include "bvh.hpp"
+#include "stage_core.hpp"
 
 namespace mrx {
 
@@ -63,19 +63,6 @@ MRX_HD inline void rayCross(const float *a, const float *b, float *c)
     c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// S1, the quaternion (w, x, y, z) used as given
-MRX_HD inline void rayRotation(const float *q, float *R)
-{
-    const float w = q[0], x = q[1], y = q[2], z = q[3];
-    const float x2 = x + x, y2 = y + y, z2 = z + z;
-    const float xx = x * x2, yy = y * y2, zz = z * z2;
-    const float xy = x * y2, xz = x * z2, yz = y * z2;
-    const float wx = w * x2, wy = w * y2, wz = w * z2;
-    R[0] = 1.0f - (yy + zz); R[1] = xy - wz;          R[2] = xz + wy;
-    R[3] = xy + wz;          R[4] = 1.0f - (xx + zz); R[5] = yz - wx;
-    R[6] = xz - wy;          R[7] = yz + wx;          R[8] = 1.0f - (xx + yy);
-}
-
 MRX_HD inline bool rayFinite(float v) { return v - v == 0.0f; }
 
 // The ray of world `w` as the caller wrote it, (ox, oy, oz, tmin, dx, dy, dz, tmax), taken out of the frame of the
@@ -88,7 +75,7 @@ MRX_HD inline Ray rayFromFrame(const float *in, int32_t frame, uint32_t rowLo, u
     if (frame >= 0 && (uint32_t)frame < rowHi - rowLo) {
         const uint32_t row = rowLo + (uint32_t)frame;
         float Rf[9];
-        rayRotation(s.instRot + 4 * (size_t)row, Rf);
+        quatRotation(s.instRot + 4 * (size_t)row, Rf);
         const float *p = s.instPos + 3 * (size_t)row;
         for (int c = 0; c < 3; ++c) {
             r.o[c] = ((Rf[3 * c] * in[0] + Rf[3 * c + 1] * in[1]) + Rf[3 * c + 2] * in[2]) + p[c];
@@ -113,7 +100,7 @@ MRX_HD inline void rayStageFrame(uint32_t row, const RayTables &s, RayRow &out)
     const bool scaleOk = sc[0] != 0.0f && sc[1] != 0.0f && sc[2] != 0.0f && rayFinite(sc[0]) && rayFinite(sc[1]) &&
                          rayFinite(sc[2]);
     const bool cand = s.instObj[row] >= 0 && info.numTris > 0 && scaleOk;
-    rayRotation(s.instRot + 4 * (size_t)row, out.R);
+    quatRotation(s.instRot + 4 * (size_t)row, out.R);
     for (int c = 0; c < 3; ++c) {
         out.is[c] = 1.0f / sc[c];
         out.t[c] = s.instPos[3 * (size_t)row + c];

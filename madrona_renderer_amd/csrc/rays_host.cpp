@@ -10,29 +10,6 @@
 
 namespace mrx {
 
-namespace {
-
-struct HostStack {
-    uint32_t v[kBvhStackCap];
-    uint32_t sp = 0;
-    bool push(uint32_t x)
-    {
-        if (sp >= kBvhStackCap)
-            return false;
-        v[sp++] = x;
-        return true;
-    }
-    bool pop(uint32_t &x)
-    {
-        if (sp == 0)
-            return false;
-        x = v[--sp];
-        return true;
-    }
-};
-
-}  // namespace
-
 void traceRaysHost(const RayParams &p)
 {
     std::vector<RayRow> rows;

@@ -182,6 +182,12 @@ struct mrx_renderer {
     DevBuf<float> outDepth;
     DevBuf<int32_t> outIds;
     DevBuf<uint32_t> outNormal;
+    // the tensors the caller sees, as the stages behind the resolve read them (at every launch: the placement search
+    // re-binds the render's)
+    uint32_t *seenRgb() const { return ss > 1 ? outRgb.ptr : params.rgb; }
+    float *seenDepth() const { return ss > 1 ? outDepth.ptr : params.depth; }
+    int32_t *seenIds() const { return ss > 1 ? outIds.ptr : params.ids; }
+    uint32_t *seenNormal() const { return ss > 1 ? outNormal.ptr : params.normal; }
     // position output: 0 none, 1 world space, 2 view space (mrx_positions); the xyzw tensor the
     // unprojection stage writes from the depth tensor the caller sees -- an allocation of its own, outside allocOutputs
     // and the placement search.  0: no pointer, no further launch.
@@ -303,6 +309,8 @@ struct mrx_renderer {
 void decodeStageFlags(uint32_t flags, mrx_renderer &r);
 // at creation, behind buildScene: the tensors of the stages the flags switch on
 int allocStages(mrx_renderer &r);
+// at teardown: the buffers of the stages attached later (mrx_rays_create ... mrx_shadow_create)
+void releaseAttached(mrx_renderer &r);
 uint32_t supersampleOf(uint32_t flags);
 uint32_t positionsOf(uint32_t flags);
 uint32_t boxLabelsOf(uint32_t flags);

@@ -31,36 +31,6 @@ namespace mrx {
 
 namespace {
 
-// the traversal stack of one lane: entry e lies at base[e * kShadowBlock], the lanes of an entry side by side
-struct LdsStack {
-    uint32_t *base;
-    uint32_t sp, cap;
-    __device__ __forceinline__ bool push(uint32_t v)
-    {
-        if (sp >= cap)
-            return false;
-        base[sp * kShadowBlock] = v;
-        ++sp;
-        return true;
-    }
-    __device__ __forceinline__ bool pop(uint32_t &v)
-    {
-        if (sp == 0)
-            return false;
-        --sp;
-        v = base[sp * kShadowBlock];
-        return true;
-    }
-};
-
-typedef __attribute__((address_space(4))) float ConstFloat;
-
-__device__ __forceinline__ float uniformF(float v)
-{
-    return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, v)));
-}
-__device__ __forceinline__ uint32_t uniformU(uint32_t v) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)v); }
-
 // a staged row, the same in every lane, moved to SGPRs (kBase and id are never staged)
 __device__ __forceinline__ ShadowRow uniformRow(const ShadowRow &in)
 {
@@ -130,7 +100,7 @@ __global__ __launch_bounds__(kShadowBlock) void shadowKernel(const ShadowArgs a)
     // brute form tests them like any other ray
     const bool dead = !BRUTE && rayDegenerate(ray);
     bool occluded = false;
-    LdsStack stack { stackMem + threadIdx.x, 0u, a.stackCap };
+    LaneStack<kShadowBlock> stack { stackMem + threadIdx.x, 0u, a.stackCap };
 
     for (uint32_t base = rowLo; base < rowHi; base += a.passRows) {
         const uint32_t n = min(a.passRows, rowHi - base);
@@ -213,8 +183,8 @@ __global__ __launch_bounds__(kShadowBlock) void shadowKernel(const ShadowArgs a)
         a.mask[item] = dark ? (uint8_t)0 : (uint8_t)255;
         if (APPLY && dark) {
             float Rc[9], lv[3];
-            rayRotation(a.camRot + 4 * (size_t)view, Rc);
-            shadowViewLight(Rc, lt.toLight, lv);
+            quatRotation(a.camRot + 4 * (size_t)view, Rc);
+            rotateT(Rc, lt.toLight, lv);
             a.rgb[item] = shadowApply(a.rgb[item], a.normal[item], lv, lt.ambient, lt.diffuse);
         }
     }

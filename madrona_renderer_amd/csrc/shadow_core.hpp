@@ -1,8 +1,8 @@
 // The arithmetic of the shadow stage, written once for the device kernel (shadow.hip) and for
 // the host entry (mrx_shadow_host): the shadow ray of a pixel, a row's staging, the any-hit BLAS traversal and the
-// darkening of an occluded pixel.  Everything that decides a result is another stage's: the pixel's point is
-// cloud_core.hpp's S13, the row's frame, the transform into it, the triangle test and the slab test are rays_core.hpp's
-// S16.  binary32, every operation rounded on its own: no fma is written and both compilers run with contraction off,
+// darkening of an occluded pixel.  Everything that decides a result is written elsewhere: the pixel's point is S13 as
+// stage_core.hpp and cloud_core.hpp have it, the row's frame, the transform into it, the triangle test and the slab test
+// are rays_core.hpp's S16.  binary32, every operation rounded on its own: no fma is written and both compilers run with contraction off,
 // so NumPy float32 reproduces every bit (tests/shadow_oracle.py).
 //
 // The answer is an OR over a world's candidate triangles: no order of the tests, no cull and no early return changes it.
@@ -142,15 +142,9 @@ MRX_HD inline bool shadowRowOccludes(const ShadowRow &row, const RayTables &s, c
     return false;
 }
 
-// S19's application: the light of the view in view space, lv = Rc^T * toLight (S2's axes)
-MRX_HD inline void shadowViewLight(const float *Rc, const float *toLight, float *lv)
-{
-    for (int c = 0; c < 3; ++c)
-        lv[c] = (Rc[c] * toLight[0] + Rc[3 + c] * toLight[1]) + Rc[6 + c] * toLight[2];
-}
-
-// an occluded pixel's colour: scaled down to the ambient term where the diffuse term had lit it, otherwise as it is.
-// rgb and normal are the packed pixels (r, nx lowest); alpha is kept.
+// S19's application to an occluded pixel: its colour scaled down to the ambient term where the diffuse term had lit it,
+// otherwise as it is.  lv: the light of the view in view space, Rc^T * toLight (S2's axes); rgb and normal are the
+// packed pixels (r, nx lowest); alpha is kept.
 MRX_HD inline uint32_t shadowApply(uint32_t rgb, uint32_t normal, const float *lv, float ambient, float diffuse)
 {
     float c[3];

@@ -12,29 +12,6 @@
 
 namespace mrx {
 
-namespace {
-
-struct HostStack {
-    uint32_t v[kBvhStackCap];
-    uint32_t sp = 0;
-    bool push(uint32_t x)
-    {
-        if (sp >= kBvhStackCap)
-            return false;
-        v[sp++] = x;
-        return true;
-    }
-    bool pop(uint32_t &x)
-    {
-        if (sp == 0)
-            return false;
-        x = v[--sp];
-        return true;
-    }
-};
-
-}  // namespace
-
 void shadowHost(const ShadowParams &p)
 {
     const uint64_t pxPerView = (uint64_t)p.nfast * p.nslow;
@@ -83,8 +60,8 @@ void shadowHost(const ShadowParams &p)
             p.mask[item] = dark ? (uint8_t)0 : (uint8_t)255;
             if (p.apply && dark) {
                 float Rc[9], lv[3];
-                rayRotation(p.camRot + 4 * (size_t)view, Rc);
-                shadowViewLight(Rc, lt.toLight, lv);
+                quatRotation(p.camRot + 4 * (size_t)view, Rc);
+                rotateT(Rc, lt.toLight, lv);
                 p.rgb[item] = shadowApply(p.rgb[item], p.normal[item], lv, lt.ambient, lt.diffuse);
             }
         }

@@ -1,7 +1,12 @@
 // The post-render stages: what each launches, the table that lists them once in step order (kStages) and everything
-// that goes through it -- the step's stage loop, the shards' "run stage i" command, the stage entry points, the
-// tensors a creation flag allocates and the stages attached later (mrx_rays_create, mrx_flow_create, mrx_cloud_create,
-// mrx_shadow_create).
+// that goes through it -- the step's stage loop, the shards' "run stage i" command, the stage entry points and the
+// tensors a creation flag allocates -- and the stages attached later (mrx_rays_create, mrx_flow_create,
+// mrx_cloud_create, mrx_shadow_create), which share one life cycle (Attached, attachPrologue, attachAll).
+//
+// A new attached stage supplies: its launch filler (the blocks every stage has come from fillImage / fillCamera), its
+// entry in kStages, its create / release / bytes functions and its Attached record, its mrx_*_create -- the texts of
+// the prologue, its own argument and size checks --, its fields in the renderer and its tensors in bufferOf.  The
+// arithmetic the stages share is in stage_core.hpp.
 #include "renderer.hpp"
 
 #include "resolve.hpp"
@@ -10,14 +15,51 @@
 #include "rays.hpp"
 #include "observe.hpp"
 
+// What the stages' parameter blocks have in common, under the same names, filled once.  The image as the caller sees
+// it: the native size, whichever the sample render's.
+template <typename P>
+static void fillImage(const mrx_renderer &r, P &q)
+{
+    q.numViews = r.params.numViews;
+    q.nfast = r.info.storage_fast;
+    q.nslow = r.info.storage_slow;
+    q.transposed = r.params.transposed;
+    q.numCUs = r.params.numCUs;
+}
+
+// ... of a stage that works out which sample a native pixel's value was taken from: the supersampling factor, too
+template <typename P>
+static void fillSampledImage(const mrx_renderer &r, P &q, uint32_t P::*s)
+{
+    fillImage(r, q);
+    q.*s = r.ss;
+    q.half = r.ss / 2;
+}
+
+// the projection constants of the views: the per-view table, else the uniform four
+template <typename P>
+static void fillProjection(const mrx_renderer &r, P &q)
+{
+    q.viewProj = r.params.viewProj;
+    q.sx = r.params.sx; q.ox = r.params.ox; q.sz = r.params.sz; q.oz = r.params.oz;
+}
+
+template <typename P>
+static void fillCamera(const mrx_renderer &r, P &q)
+{
+    q.camPos = r.params.camPos;
+    q.camRot = r.params.camRot;
+    fillProjection(r, q);
+}
+
 // (depth, ids, the constants and every table pointer are read from the render's parameters at every launch: the
 // placement search re-binds the first two, mrx_set_view_projection the constants, bindGeometry the tables; pose,
 // table and snapshot CONTENTS are read by the kernel)
 mrx::FlowParams mrx_renderer::flowParams()
 {
     mrx::FlowParams q {};
-    q.depth = ss > 1 ? outDepth.ptr : params.depth;
-    q.ids = ss > 1 ? outIds.ptr : params.ids;
+    q.depth = seenDepth();
+    q.ids = seenIds();
     q.flow = flowOut.ptr;
     q.instKBase = params.instKBase;
     q.worldInstStart = params.worldInstStart;
@@ -27,16 +69,9 @@ mrx::FlowParams mrx_renderer::flowParams()
     q.live.instScale = params.instScale;
     q.live.camPos = params.camPos;
     q.live.camRot = params.camRot;
-    q.viewProj = params.viewProj;
-    q.sx = params.sx; q.ox = params.ox; q.sz = params.sz; q.oz = params.oz;
-    q.numViews = params.numViews;
+    fillProjection(*this, q);
+    fillSampledImage(*this, q, &mrx::FlowParams::s);
     q.numInstances = info.num_instances;
-    q.nfast = info.storage_fast;
-    q.nslow = info.storage_slow;
-    q.s = ss;
-    q.half = ss / 2;
-    q.transposed = params.transposed;
-    q.numCUs = params.numCUs;
     q.passRows = flowPassRows;
     mrx::flowBindSnapshot(flowSnap.ptr, q);
     return q;
@@ -49,26 +84,17 @@ hipError_t mrx_renderer::launchFlowSnapshot() { return mrx::launchFlowSnapshot(f
 hipError_t mrx_renderer::launchCloud()
 {
     mrx::CloudParams q {};
-    q.depth = ss > 1 ? outDepth.ptr : params.depth;
+    q.depth = seenDepth();
     q.points = cloudOut.ptr;
     q.pixel = cloudPixel.ptr;
     q.count = cloudCount.ptr;
     q.scratch = cloudScratch.ptr;
     q.scratchCount = cloudScratch.count;
-    q.camPos = params.camPos;
-    q.camRot = params.camRot;
-    q.viewProj = params.viewProj;
-    q.sx = params.sx; q.ox = params.ox; q.sz = params.sz; q.oz = params.oz;
-    q.numViews = params.numViews;
-    q.nfast = info.storage_fast;
-    q.nslow = info.storage_slow;
+    fillCamera(*this, q);
+    fillSampledImage(*this, q, &mrx::CloudParams::s);
     q.N = cloudPoints;
-    q.s = ss;
-    q.half = ss / 2;
     q.frame = (int32_t)cloudFrame;
-    q.transposed = params.transposed;
     q.maxDepth = cloudMaxDepth;
-    q.numCUs = params.numCUs;
     q.forcedParts = cloudForcedParts;
     return mrx::launchCloud(q, stream);
 }
@@ -90,30 +116,21 @@ hipError_t mrx_renderer::launchShadow(bool apply)
     q.s.instScale = params.instScale;
     q.s.instObj = params.instObj;
     q.viewWorld = params.viewWorld;
-    q.depth = ss > 1 ? outDepth.ptr : params.depth;
+    q.depth = seenDepth();
     q.mask = shadowMask.ptr;
-    q.rgb = ss > 1 ? outRgb.ptr : params.rgb;
-    q.normal = ss > 1 ? outNormal.ptr : params.normal;
-    q.camPos = params.camPos;
-    q.camRot = params.camRot;
-    q.viewProj = params.viewProj;
-    q.sx = params.sx; q.ox = params.ox; q.sz = params.sz; q.oz = params.oz;
+    q.rgb = seenRgb();
+    q.normal = seenNormal();
+    fillCamera(*this, q);
+    fillSampledImage(*this, q, &mrx::ShadowParams::ss);
     q.viewLight = params.viewLight;
     for (int k = 0; k < 3; ++k)
         q.toLight[k] = params.toLight[k];
     q.ambient = params.ambient;
     q.diffuse = params.diffuse;
-    q.numViews = params.numViews;
-    q.nfast = info.storage_fast;
-    q.nslow = info.storage_slow;
-    q.ss = ss;
-    q.half = ss / 2;
-    q.transposed = params.transposed;
     q.apply = apply ? 1 : 0;
     q.bias = shadowBias;
     q.maxDistance = shadowMaxDistance;
     q.bvhDepth = info.bvh_depth;
-    q.numCUs = params.numCUs;
     q.passRows = shadowPassRows;
     q.brute = shadowBrute ? 1 : 0;
     return mrx::launchShadow(q, stream);
@@ -153,21 +170,17 @@ hipError_t mrx_renderer::launchRays()
 hipError_t mrx_renderer::launchObserve()
 {
     mrx::ObserveParams q {};
-    q.rgb = ss > 1 ? outRgb.ptr : params.rgb;
-    q.depth = ss > 1 ? outDepth.ptr : params.depth;
+    q.rgb = seenRgb();
+    q.depth = seenDepth();
     q.obs = obs.ptr;
     q.reset = obsReset.ptr;
-    q.numViews = params.numViews;
-    q.nfast = info.storage_fast;
-    q.nslow = info.storage_slow;
+    fillImage(*this, q);
     q.layout = obsLayout;
     q.dtype = obsDtype;
     q.stack = obsStack;
     q.hasRange = obsHi > 0.0f ? 1 : 0;
     q.lo = obsLo;
     q.inv = obsInv;
-    q.transposed = params.transposed;
-    q.numCUs = params.numCUs;
     return mrx::launchObserve(q, stream);
 }
 
@@ -181,14 +194,10 @@ hipError_t mrx_renderer::markObservationsReset()
 hipError_t mrx_renderer::launchBoxes()
 {
     mrx::BoxParams q {};
-    q.ids = ss > 1 ? outIds.ptr : params.ids;
+    q.ids = seenIds();
     q.out = boxes.ptr;
-    q.numViews = params.numViews;
-    q.nfast = info.storage_fast;
-    q.nslow = info.storage_slow;
+    fillImage(*this, q);
     q.K = boxLabels;
-    q.transposed = params.transposed;
-    q.numCUs = params.numCUs;
     q.forcedParts = boxParts;
     return mrx::launchBoxes(q, stream);
 }
@@ -198,20 +207,11 @@ hipError_t mrx_renderer::launchBoxes()
 hipError_t mrx_renderer::launchUnproject()
 {
     mrx::UnprojectParams q {};
-    q.depth = ss > 1 ? outDepth.ptr : params.depth;
+    q.depth = seenDepth();
     q.pos = position.ptr;
-    q.camPos = params.camPos;
-    q.camRot = params.camRot;
-    q.viewProj = params.viewProj;
-    q.sx = params.sx; q.ox = params.ox; q.sz = params.sz; q.oz = params.oz;
-    q.numViews = params.numViews;
-    q.nfast = info.storage_fast;
-    q.nslow = info.storage_slow;
-    q.s = ss;
-    q.half = ss / 2;
+    fillCamera(*this, q);
+    fillSampledImage(*this, q, &mrx::UnprojectParams::s);
     q.frame = positions == 2 ? mrx::kFrameView : mrx::kFrameWorld;
-    q.transposed = params.transposed;
-    q.numCUs = params.numCUs;
     return mrx::launchUnproject(q, stream);
 }
 
@@ -232,6 +232,15 @@ hipError_t mrx_renderer::launchResolve()
     q.numCUs = params.numCUs;
     return mrx::launchResolve(q, (int)ss, stream);
 }
+
+// The test knobs: an environment variable read as an integer where it is set.  envCount: a count, never below 0, and
+// `absent` where the variable is not set.
+static int envInt(const char *name, int absent)
+{
+    const char *v = std::getenv(name);
+    return v ? std::atoi(v) : absent;
+}
+static uint32_t envCount(const char *name, uint32_t absent) { return (uint32_t)std::max(0, envInt(name, (int)absent)); }
 
 uint32_t supersampleOf(uint32_t flags) { return 1u + ((flags & MRX_FLAG_SUPERSAMPLE_MASK) >> MRX_FLAG_SUPERSAMPLE_SHIFT); }
 
@@ -282,8 +291,7 @@ static int allocBoxes(mrx_renderer &r)
     const uint64_t cells = (uint64_t)r.params.numViews * r.boxLabels * 5u;
     MRX_HIP(r.boxes.alloc((size_t)cells));
     r.info.bytes_per_step += px * 4ull + cells * 4ull;
-    if (const char *dbg = std::getenv("MRX_BOX_PARTS"))     // tests: the merge path at tiny sizes
-        r.boxParts = (uint32_t)std::max(0, std::atoi(dbg));
+    r.boxParts = envCount("MRX_BOX_PARTS", r.boxParts);     // tests: the merge path at tiny sizes
     return MRX_OK;
 }
 
@@ -349,8 +357,7 @@ enum : int { kStageResolve = 0, kStageUnproject, kStageShadow, kStageBoxes, kSta
 // last: it reads the depth the caller sees, behind the resolve, and nothing reads what it writes.  The shadow stage
 // runs behind the unprojection and ahead of the boxes and the observation: the observation packs the rgb it has
 // darkened, and neither the flow nor the cloud reads rgb.  Its last entry is mrx_shadow's: the mask-only form whatever
-// the renderer's, which no step runs.  A new stage is an entry here, its launch, its fields in the renderer and its
-// tensors in bufferOf.
+// the renderer's, which no step runs.
 static const Stage kStages[kNumStages] = {
     { [](const mrx_renderer &r) { return r.ss > 1; }, [](mrx_renderer &r) { return r.launchResolve(); }, allocResolved,
       "launchResolve()", "nothing to resolve: this renderer was created without supersampling" },
@@ -504,23 +511,222 @@ static int runStage(mrx_renderer *r, int stage)
     return stageLaunch(s, *r, "r->");
 }
 
-// an attached stage (mrx_rays_create, mrx_flow_create, mrx_cloud_create, mrx_shadow_create) on the renderer or on every shard of it, all or nothing: a
-// shard that fails takes the stage of the shards before it along
-static int attachAll(mrx_renderer *r, uint32_t arg, int (*createOne)(mrx_renderer *, uint32_t),
-                     void (*destroyOne)(mrx_renderer *))
+// ---- the stages attached after creation (mrx_rays_create, mrx_flow_create, mrx_cloud_create, mrx_shadow_create).  Each
+// supplies a `create` -- its buffers, their first contents, its test knobs, its "on" field and its first launch, in
+// that order --, a `release` -- the buffers freed and the field cleared: the failure path, the way back when a later
+// shard fails, the renderer's teardown -- and a `bytes`, what it adds to info.bytes_per_step while it is on.
+struct Attached {
+    const char *what;                                       // how the text of a HIP failure begins
+    hipError_t (*create)(mrx_renderer &r, uint32_t arg);
+    void (*release)(mrx_renderer &r);
+    uint64_t (*bytes)(const mrx_renderer &r);
+    uint32_t mrx_renderer::*on;                             // the field that holds `arg` while the stage is on (null: none)
+};
+
+static uint64_t nativePixels(const mrx_info_t &i) { return (uint64_t)i.num_views * i.storage_fast * i.storage_slow; }
+
+// the sensor: the four tensors, the bound-object table, the first trace
+static hipError_t raysCreate(mrx_renderer &r, uint32_t R)
 {
-    if (r->shards.empty())
-        return createOne(r, arg);
+    const uint64_t worlds = r.info.num_worlds, n = worlds * R;
+    hipError_t e = r.rays.alloc((size_t)n * 8u);
+    if (e == hipSuccess) e = r.rayT.alloc((size_t)n);
+    if (e == hipSuccess) e = r.rayId.alloc((size_t)n);
+    if (e == hipSuccess) e = r.rayFrame.alloc((size_t)worlds);
+    if (e == hipSuccess) e = uploadRayBound(r);
+    if (e == hipSuccess) e = mrx::prepareRays();
+    // zero rays, world frame (-1 is all bytes 0xFF), and what the zero ray gives: tmax = 0, id -1
+    if (e == hipSuccess) e = hipMemsetAsync(r.rays.ptr, 0, (size_t)n * 32u, r.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r.rayT.ptr, 0, (size_t)n * 4u, r.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r.rayId.ptr, 0xFF, (size_t)n * 4u, r.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r.rayFrame.ptr, 0xFF, (size_t)worlds * 4u, r.stream);
+    if (e != hipSuccess)
+        return e;
+    r.rayBrute = envInt("MRX_RAYS_BRUTE", 0) != 0;
+    r.rayPassRows = envCount("MRX_RAY_PASS_ROWS", r.rayPassRows);   // tests: several staging passes at tiny sizes
+    r.raysPerWorld = R;
+    return r.launchRays();
+}
+static void raysRelease(mrx_renderer &r)
+{
+    r.raysPerWorld = 0;
+    r.rays.release(); r.rayT.release(); r.rayFrame.release(); r.rayId.release(); r.rayBound.release();
+}
+// per ray 32 bytes read, 8 written (the tables it walks depend on the rays)
+static uint64_t raysBytes(const mrx_renderer &r) { return (uint64_t)r.info.num_worlds * r.raysPerWorld * 40ull; }
+static const Attached kRays = { "ray-cast sensor: ", raysCreate, raysRelease, raysBytes, &mrx_renderer::raysPerWorld };
+
+// the flow output: the tensor, the snapshot of the state as it is, the first flow.  The two pointers are the sign of it.
+static hipError_t flowCreate(mrx_renderer &r, uint32_t)
+{
+    const uint64_t px = nativePixels(r.info);
+    const uint64_t snap = mrx::flowSnapshotLayout(r.info.num_instances, r.info.num_views).total;
+    // (one spare 16 bytes each: a renderer without a pixel or a row still has two pointers)
+    hipError_t e = r.flowOut.alloc((size_t)px * 4u + 4u);
+    if (e == hipSuccess) e = r.flowSnap.alloc((size_t)snap + 4u);
+    if (e == hipSuccess) e = hipMemsetAsync(r.flowOut.ptr, 0, ((size_t)px * 4u + 4u) * 4u, r.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r.flowSnap.ptr, 0, ((size_t)snap + 4u) * 4u, r.stream);
+    if (e != hipSuccess)
+        return e;
+    r.flowPassRows = envCount("MRX_FLOW_PASS_ROWS", r.flowPassRows);    // tests: several staging passes at tiny sizes
+    // the initial state is the previous state of the first frame: a still scene
+    e = r.launchFlowSnapshot();
+    return e == hipSuccess ? r.launchFlow() : e;
+}
+static void flowRelease(mrx_renderer &r) { r.flowOut.release(); r.flowSnap.release(); }
+// per native pixel 4 bytes of depth and 4 of ids read, 16 written
+static uint64_t flowBytes(const mrx_renderer &r) { return nativePixels(r.info) * 24ull; }
+static const Attached kFlow = { "optical flow: ", flowCreate, flowRelease, flowBytes, nullptr };
+
+// the point cloud: the three tensors, the counts of a split view's parts, the first run of the stage.  Frame and far
+// crop are in the renderer already (mrx_cloud_create).
+static hipError_t cloudCreate(mrx_renderer &r, uint32_t N)
+{
+    const uint64_t views = r.info.num_views, slots = views * N;
+    const uint64_t pxPerView = (uint64_t)r.info.storage_fast * r.info.storage_slow;
+    r.cloudForcedParts = envCount("MRX_CLOUD_PARTS", 0);    // tests: the split at tiny sizes
+    const uint64_t parts = mrx::cloudParts(r.info.num_views, pxPerView, r.params.numCUs, r.cloudForcedParts);
+    hipError_t e = r.cloudOut.alloc((size_t)slots * 4u);
+    if (e == hipSuccess) e = r.cloudPixel.alloc((size_t)slots);
+    if (e == hipSuccess) e = r.cloudCount.alloc((size_t)views);
+    if (e == hipSuccess) e = r.cloudScratch.alloc((size_t)(views * parts));
+    // the empty cloud: zero points, pixel -1 (all bytes 0xFF), count 0
+    if (e == hipSuccess) e = hipMemsetAsync(r.cloudOut.ptr, 0, (size_t)slots * 16u, r.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r.cloudPixel.ptr, 0xFF, (size_t)slots * 4u, r.stream);
+    if (e == hipSuccess) e = hipMemsetAsync(r.cloudCount.ptr, 0, (size_t)views * 4u, r.stream);
+    if (e != hipSuccess)
+        return e;
+    r.cloudPoints = N;
+    return r.launchCloud();
+}
+static void cloudRelease(mrx_renderer &r)
+{
+    r.cloudPoints = 0;
+    r.cloudOut.release(); r.cloudPixel.release(); r.cloudCount.release(); r.cloudScratch.release();
+}
+// what the compaction stage reads and writes per step: 4 bytes of depth per native pixel; 20 bytes per slot and a count
+static uint64_t cloudBytes(const mrx_renderer &r)
+{
+    return nativePixels(r.info) * 4ull + (uint64_t)r.info.num_views * ((uint64_t)r.cloudPoints * 20ull + 4ull);
+}
+static const Attached kCloud = { "point cloud: ", cloudCreate, cloudRelease, cloudBytes, &mrx_renderer::cloudPoints };
+
+// the shadow stage: the mask, the first run in the mask-only form.  Bias and reach are in the renderer already
+// (mrx_shadow_create); `mode` is 1 or 2.
+static hipError_t shadowCreate(mrx_renderer &r, uint32_t mode)
+{
+    const uint64_t px = nativePixels(r.info);
+    r.shadowBrute = envInt("MRX_SHADOW_BRUTE", 0) != 0;
+    r.shadowPassRows = envCount("MRX_SHADOW_PASS_ROWS", 0);     // tests: several staging passes at tiny sizes
+    hipError_t e = r.shadowMask.alloc((size_t)px);
+    if (e == hipSuccess) e = mrx::prepareShadow();
+    if (e == hipSuccess) e = hipMemsetAsync(r.shadowMask.ptr, 0xFF, (size_t)px, r.stream);
+    if (e != hipSuccess)
+        return e;
+    r.shadows = mode;
+    return r.launchShadow(false);
+}
+static void shadowRelease(mrx_renderer &r)
+{
+    r.shadows = 0;
+    r.shadowMask.release();
+}
+// what the shadow stage reads and writes per step: 4 bytes of depth and the mask's byte per native pixel (what the
+// applying form touches on top depends on the image: no fixed term)
+static uint64_t shadowBytes(const mrx_renderer &r) { return nativePixels(r.info) * 5ull; }
+static const Attached kShadow = { "shadows: ", shadowCreate, shadowRelease, shadowBytes, &mrx_renderer::shadows };
+
+void releaseAttached(mrx_renderer &r)
+{
+    for (const Attached *a : { &kRays, &kFlow, &kCloud, &kShadow })
+        a->release(r);
+}
+
+// the stage of one renderer on one device; a failure leaves the renderer without it
+static int attachOne(mrx_renderer *r, uint32_t arg, const Attached &a)
+{
+    MRX_HIP(hipSetDevice(r->device));
+    hipError_t e = a.create(*r, arg);
+    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
+    if (e != hipSuccess) {
+        a.release(*r);
+        return fail(MRX_E_HIP, std::string(a.what) + hipGetErrorString(e));
+    }
+    r->info.bytes_per_step += a.bytes(*r);
+    return MRX_OK;
+}
+
+// takes the stage off a shard again (a later one failed)
+static void detachOne(mrx_renderer *r, const Attached &a)
+{
+    (void)hipSetDevice(r->device);
+    (void)hipStreamSynchronize(r->stream);
+    r->info.bytes_per_step -= a.bytes(*r);
+    a.release(*r);
+}
+
+// an attached stage on the renderer or on every shard of it, all or nothing: a shard that fails takes the stage of the
+// shards before it along.  Of a renderer of several devices the parent's "on" field is set, too.
+static int attachAll(mrx_renderer *r, uint32_t arg, const Attached &a)
+{
     for (size_t i = 0; i < r->shards.size(); ++i) {
-        const int rc = createOne(r->shards[i], arg);
+        const int rc = attachOne(r->shards[i], arg, a);
         if (rc != MRX_OK) {
             const std::string why = g_err;
             for (size_t k = 0; k < i; ++k)
-                destroyOne(r->shards[k]);
+                detachOne(r->shards[k], a);
             return fail(rc, why);
         }
     }
+    if (r->shards.empty())
+        if (const int rc = attachOne(r, arg, a))
+            return rc;
+    if (a.on)
+        r->*a.on = arg;
     return MRX_OK;
+}
+
+// The prologue of the four mrx_*_create entries, in the order every one of them had it: the device threads caught up,
+// the handle, "on a shard", "already attached", the entry's own argument check (made by the caller, who passes the
+// text of what failed or an empty string), the tensors the stage needs -- of the first shard: all shards have the same
+// --, and the whole renderer's info for the caller's size limits.
+struct AttachTexts {
+    const char *onShard, *already;
+    std::string badArgument;
+    const char *needIds = nullptr, *needDepth = nullptr, *needRgb = nullptr, *needNormal = nullptr;    // null: not needed
+};
+static int attachPrologue(mrx_renderer *r, int stage, const AttachTexts &t, mrx_info_t &whole)
+{
+    if (const int src = settle(r))
+        return src;
+    if (!r)
+        return fail(MRX_E_INVALID, "null renderer");
+    if (r->parent)
+        return fail(MRX_E_INVALID, t.onShard);
+    if (kStages[stage].on(*r))
+        return fail(MRX_E_INVALID, t.already);
+    if (!t.badArgument.empty())
+        return fail(MRX_E_INVALID, t.badArgument);
+    const mrx_renderer *first = r->shards.empty() ? r : r->shards[0];
+    if (t.needIds && (!first->ids.ptr || first->params.idsAreSegmask))
+        return fail(MRX_E_INVALID, t.needIds);
+    if (t.needDepth && !first->depth.ptr)
+        return fail(MRX_E_INVALID, t.needDepth);
+    if (t.needRgb && !first->rgb.ptr)
+        return fail(MRX_E_INVALID, t.needRgb);
+    if (t.needNormal && !first->normal.ptr)
+        return fail(MRX_E_INVALID, t.needNormal);
+    whole = mrx_info_t {};
+    return infoFull(r, &whole) != MRX_OK ? (int)MRX_E_INVALID : (int)MRX_OK;
+}
+
+// `set` on the renderer and on every shard of it
+template <typename F>
+static void onAll(mrx_renderer *r, F set)
+{
+    set(*r);
+    for (mrx_renderer *sh : r->shards)
+        set(*sh);
 }
 
 extern "C" {
@@ -550,76 +756,18 @@ int mrx_box_labels(mrx_renderer *r)
     return r ? (int)r->boxLabels : fail(MRX_E_INVALID, "null renderer");
 }
 
-// the sensor of one renderer on one device: the four tensors, the bound-object table, the first trace
-static int raysCreateOne(mrx_renderer *r, uint32_t R)
-{
-    MRX_HIP(hipSetDevice(r->device));
-    const uint64_t worlds = r->info.num_worlds, n = worlds * R;
-    // (a failure leaves the renderer without a sensor: raysPerWorld is set last)
-    auto undo = [&](hipError_t e) {
-        r->rays.release(); r->rayT.release(); r->rayFrame.release(); r->rayId.release(); r->rayBound.release();
-        return fail(MRX_E_HIP, std::string("ray-cast sensor: ") + hipGetErrorString(e));
-    };
-    hipError_t e = r->rays.alloc((size_t)n * 8u);
-    if (e == hipSuccess) e = r->rayT.alloc((size_t)n);
-    if (e == hipSuccess) e = r->rayId.alloc((size_t)n);
-    if (e == hipSuccess) e = r->rayFrame.alloc((size_t)worlds);
-    if (e == hipSuccess) e = uploadRayBound(*r);
-    if (e == hipSuccess) e = mrx::prepareRays();
-    // zero rays, world frame (-1 is all bytes 0xFF), and what the zero ray gives: tmax = 0, id -1
-    if (e == hipSuccess) e = hipMemsetAsync(r->rays.ptr, 0, (size_t)n * 32u, r->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(r->rayT.ptr, 0, (size_t)n * 4u, r->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(r->rayId.ptr, 0xFF, (size_t)n * 4u, r->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(r->rayFrame.ptr, 0xFF, (size_t)worlds * 4u, r->stream);
-    if (e != hipSuccess)
-        return undo(e);
-    const char *brute = std::getenv("MRX_RAYS_BRUTE");
-    r->rayBrute = brute && std::atoi(brute) != 0;
-    if (const char *dbg = std::getenv("MRX_RAY_PASS_ROWS"))     // tests: several staging passes at tiny sizes
-        r->rayPassRows = (uint32_t)std::max(0, std::atoi(dbg));
-    r->raysPerWorld = R;
-    e = r->launchRays();
-    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-    if (e != hipSuccess) {
-        r->raysPerWorld = 0;
-        return undo(e);
-    }
-    // per ray 32 bytes read, 8 written (the tables it walks depend on the rays)
-    r->info.bytes_per_step += n * 40ull;
-    return MRX_OK;
-}
-
-// takes the sensor off a shard again (mrx_rays_create failed on a later one)
-static void raysDestroyOne(mrx_renderer *r)
-{
-    (void)hipSetDevice(r->device);
-    (void)hipStreamSynchronize(r->stream);
-    r->info.bytes_per_step -= (uint64_t)r->info.num_worlds * r->raysPerWorld * 40ull;
-    r->raysPerWorld = 0;
-    r->rays.release(); r->rayT.release(); r->rayFrame.release(); r->rayId.release(); r->rayBound.release();
-}
-
 int mrx_rays_create(mrx_renderer *r, uint32_t rays_per_world)
 {
-    if (const int src = settle(r))
-        return src;
-    if (!r)
-        return fail(MRX_E_INVALID, "null renderer");
-    if (r->parent)
-        return fail(MRX_E_INVALID, "mrx_rays_create on a shard: attach the sensor to the renderer it belongs to");
-    if (r->raysPerWorld)
-        return fail(MRX_E_INVALID, "this renderer already has a ray-cast sensor");
+    AttachTexts t { "mrx_rays_create on a shard: attach the sensor to the renderer it belongs to",
+                    "this renderer already has a ray-cast sensor" };
     if (rays_per_world < 1 || rays_per_world > mrx::kRayMaxPerWorld)
-        return fail(MRX_E_INVALID, "rays_per_world " + std::to_string(rays_per_world) + " is not in 1 ... 65536");
-    mrx_info_t whole {};
-    if (infoFull(r, &whole) != MRX_OK)
-        return MRX_E_INVALID;
+        t.badArgument = "rays_per_world " + std::to_string(rays_per_world) + " is not in 1 ... 65536";
+    mrx_info_t whole;
+    if (const int rc = attachPrologue(r, kStageTrace, t, whole))
+        return rc;
     if ((uint64_t)whole.num_worlds * rays_per_world >= (1ull << 31))
         return fail(MRX_E_INVALID, "ray-cast sensor: worlds * rays_per_world reaches 2^31");
-    const int rc = attachAll(r, rays_per_world, raysCreateOne, raysDestroyOne);
-    if (rc == MRX_OK)
-        r->raysPerWorld = rays_per_world;             // (of a renderer of several devices: the parent's, too)
-    return rc;
+    return attachAll(r, rays_per_world, kRays);
 }
 
 int mrx_rays(mrx_renderer *r)
@@ -649,66 +797,18 @@ int mrx_set_rays(mrx_renderer *r, uint32_t first_world, uint32_t count, const fl
     return MRX_OK;
 }
 
-// the output of one renderer on one device: the tensor, the snapshot of the state as it is, the first flow
-static int flowCreateOne(mrx_renderer *r)
-{
-    MRX_HIP(hipSetDevice(r->device));
-    const uint64_t px = (uint64_t)r->info.num_views * r->info.storage_fast * r->info.storage_slow;
-    const uint64_t snap = mrx::flowSnapshotLayout(r->info.num_instances, r->info.num_views).total;
-    auto undo = [&](hipError_t e) {
-        r->flowOut.release(); r->flowSnap.release();
-        return fail(MRX_E_HIP, std::string("optical flow: ") + hipGetErrorString(e));
-    };
-    // (one spare 16 bytes each: a renderer without a pixel or a row still has two pointers, the sign of the output)
-    hipError_t e = r->flowOut.alloc((size_t)px * 4u + 4u);
-    if (e == hipSuccess) e = r->flowSnap.alloc((size_t)snap + 4u);
-    if (e == hipSuccess) e = hipMemsetAsync(r->flowOut.ptr, 0, ((size_t)px * 4u + 4u) * 4u, r->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(r->flowSnap.ptr, 0, ((size_t)snap + 4u) * 4u, r->stream);
-    if (e != hipSuccess)
-        return undo(e);
-    if (const char *dbg = std::getenv("MRX_FLOW_PASS_ROWS"))    // tests: several staging passes at tiny sizes
-        r->flowPassRows = (uint32_t)std::max(0, std::atoi(dbg));
-    // the initial state is the previous state of the first frame: a still scene
-    e = r->launchFlowSnapshot();
-    if (e == hipSuccess) e = r->launchFlow();
-    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-    if (e != hipSuccess)
-        return undo(e);
-    // per native pixel 4 bytes of depth and 4 of ids read, 16 written
-    r->info.bytes_per_step += px * 24ull;
-    return MRX_OK;
-}
-
-// takes the output off a shard again (mrx_flow_create failed on a later one)
-static void flowDestroyOne(mrx_renderer *r)
-{
-    (void)hipSetDevice(r->device);
-    (void)hipStreamSynchronize(r->stream);
-    r->info.bytes_per_step -= (uint64_t)r->info.num_views * r->info.storage_fast * r->info.storage_slow * 24ull;
-    r->flowOut.release(); r->flowSnap.release();
-}
-
 int mrx_flow_create(mrx_renderer *r)
 {
-    if (const int src = settle(r))
-        return src;
-    if (!r)
-        return fail(MRX_E_INVALID, "null renderer");
-    if (r->parent)
-        return fail(MRX_E_INVALID, "mrx_flow_create on a shard: attach the output to the renderer it belongs to");
-    if (flowOn(r))
-        return fail(MRX_E_INVALID, "this renderer already has the optical-flow output");
-    const mrx_renderer *first = r->shards.empty() ? r : r->shards[0];
-    if (!first->ids.ptr || first->params.idsAreSegmask)
-        return fail(MRX_E_INVALID, "optical flow needs visibility ids: create the renderer with MRX_FLAG_VISIBILITY_IDS");
-    if (!first->depth.ptr)
-        return fail(MRX_E_INVALID, "optical flow needs depth: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)");
-    mrx_info_t whole {};
-    if (infoFull(r, &whole) != MRX_OK)
-        return MRX_E_INVALID;
-    if ((uint64_t)whole.num_views * whole.storage_fast * whole.storage_slow > mrx::kFlowMaxPixels)
+    AttachTexts t { "mrx_flow_create on a shard: attach the output to the renderer it belongs to",
+                    "this renderer already has the optical-flow output" };
+    t.needIds = "optical flow needs visibility ids: create the renderer with MRX_FLAG_VISIBILITY_IDS";
+    t.needDepth = "optical flow needs depth: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)";
+    mrx_info_t whole;
+    if (const int rc = attachPrologue(r, kStageFlow, t, whole))
+        return rc;
+    if (nativePixels(whole) > mrx::kFlowMaxPixels)
         return fail(MRX_E_INVALID, "optical flow: more than 2^32 - 1 native pixels");
-    return attachAll(r, 0, [](mrx_renderer *sh, uint32_t) { return flowCreateOne(sh); }, flowDestroyOne);
+    return attachAll(r, 0, kFlow);
 }
 
 int mrx_flow_enabled(mrx_renderer *r)
@@ -718,97 +818,30 @@ int mrx_flow_enabled(mrx_renderer *r)
     return flowOn(r) ? 1 : 0;
 }
 
-// what the compaction stage reads and writes per step: 4 bytes of depth per native pixel; 20 bytes per slot and a count
-static uint64_t cloudBytes(const mrx_renderer *r)
-{
-    return (uint64_t)r->info.num_views * r->info.storage_fast * r->info.storage_slow * 4ull +
-           (uint64_t)r->info.num_views * ((uint64_t)r->cloudPoints * 20ull + 4ull);
-}
-
-// the output of one renderer on one device: the three tensors, the counts of a split view's parts, the first run of
-// the stage.  Frame and far crop are in the renderer already (mrx_cloud_create).
-static int cloudCreateOne(mrx_renderer *r, uint32_t N)
-{
-    MRX_HIP(hipSetDevice(r->device));
-    const uint64_t views = r->info.num_views, slots = views * N;
-    const uint64_t pxPerView = (uint64_t)r->info.storage_fast * r->info.storage_slow;
-    // (a failure leaves the renderer without the output: cloudPoints is cleared again)
-    auto undo = [&](hipError_t e) {
-        r->cloudPoints = 0;
-        r->cloudOut.release(); r->cloudPixel.release(); r->cloudCount.release(); r->cloudScratch.release();
-        return fail(MRX_E_HIP, std::string("point cloud: ") + hipGetErrorString(e));
-    };
-    r->cloudForcedParts = 0;
-    if (const char *dbg = std::getenv("MRX_CLOUD_PARTS"))       // tests: the split at tiny sizes
-        r->cloudForcedParts = (uint32_t)std::max(0, std::atoi(dbg));
-    const uint64_t parts = mrx::cloudParts(r->info.num_views, pxPerView, r->params.numCUs, r->cloudForcedParts);
-    hipError_t e = r->cloudOut.alloc((size_t)slots * 4u);
-    if (e == hipSuccess) e = r->cloudPixel.alloc((size_t)slots);
-    if (e == hipSuccess) e = r->cloudCount.alloc((size_t)views);
-    if (e == hipSuccess) e = r->cloudScratch.alloc((size_t)(views * parts));
-    // the empty cloud: zero points, pixel -1 (all bytes 0xFF), count 0
-    if (e == hipSuccess) e = hipMemsetAsync(r->cloudOut.ptr, 0, (size_t)slots * 16u, r->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(r->cloudPixel.ptr, 0xFF, (size_t)slots * 4u, r->stream);
-    if (e == hipSuccess) e = hipMemsetAsync(r->cloudCount.ptr, 0, (size_t)views * 4u, r->stream);
-    if (e != hipSuccess)
-        return undo(e);
-    r->cloudPoints = N;
-    e = r->launchCloud();
-    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-    if (e != hipSuccess)
-        return undo(e);
-    r->info.bytes_per_step += cloudBytes(r);
-    return MRX_OK;
-}
-
-// takes the output off a shard again (mrx_cloud_create failed on a later one)
-static void cloudDestroyOne(mrx_renderer *r)
-{
-    (void)hipSetDevice(r->device);
-    (void)hipStreamSynchronize(r->stream);
-    r->info.bytes_per_step -= cloudBytes(r);
-    r->cloudPoints = 0;
-    r->cloudOut.release(); r->cloudPixel.release(); r->cloudCount.release(); r->cloudScratch.release();
-}
-
 int mrx_cloud_create(mrx_renderer *r, uint32_t points_per_view, int frame, float max_depth)
 {
-    if (const int src = settle(r))
-        return src;
-    if (!r)
-        return fail(MRX_E_INVALID, "null renderer");
-    if (r->parent)
-        return fail(MRX_E_INVALID, "mrx_cloud_create on a shard: attach the output to the renderer it belongs to");
-    if (r->cloudPoints)
-        return fail(MRX_E_INVALID, "this renderer already has the point-cloud output");
+    AttachTexts t { "mrx_cloud_create on a shard: attach the output to the renderer it belongs to",
+                    "this renderer already has the point-cloud output" };
     if (points_per_view < 1 || points_per_view > mrx::kCloudMaxPoints)
-        return fail(MRX_E_INVALID, "points_per_view " + std::to_string(points_per_view) + " is not in 1 ... 65536");
-    if (frame != 1 && frame != 2)
-        return fail(MRX_E_INVALID, "point cloud: frame " + std::to_string(frame) + " is neither 1 (world space) nor 2 (view space)");
-    if (!(max_depth == 0.0f || (std::isfinite(max_depth) && max_depth > 0.0f)))
-        return fail(MRX_E_INVALID, "point cloud: max_depth is 0 (none) or finite and positive");
-    const mrx_renderer *first = r->shards.empty() ? r : r->shards[0];
-    if (!first->depth.ptr)
-        return fail(MRX_E_INVALID, "the point cloud needs depth: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)");
-    mrx_info_t whole {};
-    if (infoFull(r, &whole) != MRX_OK)
-        return MRX_E_INVALID;
+        t.badArgument = "points_per_view " + std::to_string(points_per_view) + " is not in 1 ... 65536";
+    else if (frame != 1 && frame != 2)
+        t.badArgument = "point cloud: frame " + std::to_string(frame) + " is neither 1 (world space) nor 2 (view space)";
+    else if (!(max_depth == 0.0f || (std::isfinite(max_depth) && max_depth > 0.0f)))
+        t.badArgument = "point cloud: max_depth is 0 (none) or finite and positive";
+    t.needDepth = "the point cloud needs depth: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)";
+    mrx_info_t whole;
+    if (const int rc = attachPrologue(r, kStageCloud, t, whole))
+        return rc;
     if ((uint64_t)whole.num_views * points_per_view >= (1ull << 31))
         return fail(MRX_E_INVALID, "point cloud: views * points_per_view reaches 2^31");
     if ((uint64_t)whole.storage_fast * whole.storage_slow > mrx::kCloudMaxViewPixels ||
-        (uint64_t)whole.num_views * whole.storage_fast * whole.storage_slow > mrx::kCloudMaxPixels)
+        nativePixels(whole) > mrx::kCloudMaxPixels)
         return fail(MRX_E_INVALID, "point cloud: more than 2^32 - 1 native pixels, or more than 2^31 - 1 in a view");
-    const auto store = [&](mrx_renderer &sh) {
+    onAll(r, [&](mrx_renderer &sh) {
         sh.cloudFrame = (uint32_t)frame;
         sh.cloudMaxDepth = max_depth;
-    };
-    store(*r);
-    for (mrx_renderer *sh : r->shards)
-        store(*sh);
-    const int rc = attachAll(r, points_per_view, cloudCreateOne, cloudDestroyOne);
-    if (rc == MRX_OK)
-        r->cloudPoints = points_per_view;           // (of a renderer of several devices: the parent's, too)
-    return rc;
+    });
+    return attachAll(r, points_per_view, kCloud);
 }
 
 int mrx_cloud(mrx_renderer *r)
@@ -816,92 +849,29 @@ int mrx_cloud(mrx_renderer *r)
     return r ? (int)r->cloudPoints : fail(MRX_E_INVALID, "null renderer");
 }
 
-// what the shadow stage reads and writes per step: 4 bytes of depth and the mask's byte per native pixel (what the
-// applying form touches on top depends on the image: no fixed term)
-static uint64_t shadowBytes(const mrx_renderer *r)
-{
-    return (uint64_t)r->info.num_views * r->info.storage_fast * r->info.storage_slow * 5ull;
-}
-
-// the stage of one renderer on one device: the mask, the first run in the mask-only form.  Bias and reach are in the
-// renderer already (mrx_shadow_create); `mode` is 1 or 2.
-static int shadowCreateOne(mrx_renderer *r, uint32_t mode)
-{
-    MRX_HIP(hipSetDevice(r->device));
-    const uint64_t px = (uint64_t)r->info.num_views * r->info.storage_fast * r->info.storage_slow;
-    // (a failure leaves the renderer without the stage: shadows is cleared again)
-    auto undo = [&](hipError_t e) {
-        r->shadows = 0;
-        r->shadowMask.release();
-        return fail(MRX_E_HIP, std::string("shadows: ") + hipGetErrorString(e));
-    };
-    const char *brute = std::getenv("MRX_SHADOW_BRUTE");
-    r->shadowBrute = brute && std::atoi(brute) != 0;
-    r->shadowPassRows = 0;
-    if (const char *dbg = std::getenv("MRX_SHADOW_PASS_ROWS"))  // tests: several staging passes at tiny sizes
-        r->shadowPassRows = (uint32_t)std::max(0, std::atoi(dbg));
-    hipError_t e = r->shadowMask.alloc((size_t)px);
-    if (e == hipSuccess) e = mrx::prepareShadow();
-    if (e == hipSuccess) e = hipMemsetAsync(r->shadowMask.ptr, 0xFF, (size_t)px, r->stream);
-    if (e != hipSuccess)
-        return undo(e);
-    r->shadows = mode;
-    e = r->launchShadow(false);
-    if (e == hipSuccess) e = hipStreamSynchronize(r->stream);
-    if (e != hipSuccess)
-        return undo(e);
-    r->info.bytes_per_step += shadowBytes(r);
-    return MRX_OK;
-}
-
-// takes the stage off a shard again (mrx_shadow_create failed on a later one)
-static void shadowDestroyOne(mrx_renderer *r)
-{
-    (void)hipSetDevice(r->device);
-    (void)hipStreamSynchronize(r->stream);
-    r->info.bytes_per_step -= shadowBytes(r);
-    r->shadows = 0;
-    r->shadowMask.release();
-}
-
 int mrx_shadow_create(mrx_renderer *r, int apply, float bias, float max_distance)
 {
-    if (const int src = settle(r))
-        return src;
-    if (!r)
-        return fail(MRX_E_INVALID, "null renderer");
-    if (r->parent)
-        return fail(MRX_E_INVALID, "mrx_shadow_create on a shard: attach the stage to the renderer it belongs to");
-    if (r->shadows)
-        return fail(MRX_E_INVALID, "this renderer already casts shadows");
+    AttachTexts t { "mrx_shadow_create on a shard: attach the stage to the renderer it belongs to",
+                    "this renderer already casts shadows" };
     if (!(std::isfinite(bias) && bias >= 0.0f))
-        return fail(MRX_E_INVALID, "shadows: bias is finite and >= 0");
-    if (!(std::isfinite(max_distance) && max_distance > 0.0f))
-        return fail(MRX_E_INVALID, "shadows: max_distance is FLT_MAX (none) or finite and > 0");
-    const mrx_renderer *first = r->shards.empty() ? r : r->shards[0];
-    if (!first->depth.ptr)
-        return fail(MRX_E_INVALID, "shadows need depth: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)");
-    if (apply && !first->rgb.ptr)
-        return fail(MRX_E_INVALID, "shadows with apply need rgb: this renderer was created depth-only (MRX_FLAG_NO_RGB)");
-    if (apply && !first->normal.ptr)
-        return fail(MRX_E_INVALID, "shadows with apply need the normal tensor: create the renderer with MRX_FLAG_NORMALS");
-    mrx_info_t whole {};
-    if (infoFull(r, &whole) != MRX_OK)
-        return MRX_E_INVALID;
-    if ((uint64_t)whole.num_views * whole.storage_fast * whole.storage_slow > mrx::kShadowMaxPixels)
+        t.badArgument = "shadows: bias is finite and >= 0";
+    else if (!(std::isfinite(max_distance) && max_distance > 0.0f))
+        t.badArgument = "shadows: max_distance is FLT_MAX (none) or finite and > 0";
+    t.needDepth = "shadows need depth: this renderer was created rgb-only (MRX_FLAG_NO_DEPTH)";
+    if (apply) {
+        t.needRgb = "shadows with apply need rgb: this renderer was created depth-only (MRX_FLAG_NO_RGB)";
+        t.needNormal = "shadows with apply need the normal tensor: create the renderer with MRX_FLAG_NORMALS";
+    }
+    mrx_info_t whole;
+    if (const int rc = attachPrologue(r, kStageShadow, t, whole))
+        return rc;
+    if (nativePixels(whole) > mrx::kShadowMaxPixels)
         return fail(MRX_E_INVALID, "shadows: more than 2^32 - 1 native pixels");
-    const auto store = [&](mrx_renderer &sh) {
+    onAll(r, [&](mrx_renderer &sh) {
         sh.shadowBias = bias;
         sh.shadowMaxDistance = max_distance;
-    };
-    store(*r);
-    for (mrx_renderer *sh : r->shards)
-        store(*sh);
-    const uint32_t mode = apply ? 2u : 1u;
-    const int rc = attachAll(r, mode, shadowCreateOne, shadowDestroyOne);
-    if (rc == MRX_OK)
-        r->shadows = mode;                          // (of a renderer of several devices: the parent's, too)
-    return rc;
+    });
+    return attachAll(r, apply ? 2u : 1u, kShadow);
 }
 
 int mrx_shadows(mrx_renderer *r)
@@ -932,18 +902,14 @@ int mrx_set_observation_depth_range(mrx_renderer *r, float lo, float hi)
     // S15: a float32 subtract and a float32 divide
     const float span = hi - lo;
     const float inv = unset ? 0.0f : 1.0f / span;
-    const auto store = [&](mrx_renderer &sh) {
+    onAll(r, [&](mrx_renderer &sh) {
         sh.obsLo = unset ? 0.0f : lo;
         sh.obsHi = unset ? 0.0f : hi;
         sh.obsInv = inv;
-    };
-    store(*r);
+    });
     // frames packed under another range are meaningless: every stack restarts from the frame packed now
-    if (!r->shards.empty()) {
-        for (mrx_renderer *sh : r->shards)
-            store(*sh);
+    if (!r->shards.empty())
         return shardsRun(r, kCmdObserveRestart);
-    }
     MRX_HIP(hipSetDevice(r->device));
     MRX_HIP(r->markObservationsReset());
     MRX_HIP(r->launchObserve());

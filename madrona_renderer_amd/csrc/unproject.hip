@@ -20,6 +20,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include "stage_core.hpp"
 #include "unproject.hpp"
 
 namespace mrx {
@@ -67,29 +68,16 @@ template <bool WORLD>
 __device__ __forceinline__ float4 unprojectPixel(const ViewVals &v, const UnprojectArgs &a, uint32_t x, uint32_t y,
                                                  float d)
 {
-    // the index of the sample the pixel's depth was taken from, as the render kernels form px: S5's ox / oz carry the
-    // half pixel that makes it the sample's centre
-    const float px = (float)(a.s * x + a.half);
-    const float py = (float)(a.s * y + a.half);
-    const float rx = px * v.sx + v.ox;
-    const float rz = py * v.sz + v.oz;
-    const float vx = d * rx, vy = d, vz = d * rz;
-    float ox = vx, oy = vy, oz = vz;
+    const ViewPoint p = viewPoint(v.sx, v.ox, v.sz, v.oz, a.s, a.half, x, y, d);
+    float o[3] = { p.v[0], p.v[1], p.v[2] };
     if constexpr (WORLD) {
-        // S1, the quaternion used as given
-        const float x2 = v.qx + v.qx, y2 = v.qy + v.qy, z2 = v.qz + v.qz;
-        const float xx = v.qx * x2, yy = v.qy * y2, zz = v.qz * z2;
-        const float xy = v.qx * y2, xz = v.qx * z2, yz = v.qy * z2;
-        const float wx = v.qw * x2, wy = v.qw * y2, wz = v.qw * z2;
-        const float r00 = 1.0f - (yy + zz), r01 = xy - wz, r02 = xz + wy;
-        const float r10 = xy + wz, r11 = 1.0f - (xx + zz), r12 = yz - wx;
-        const float r20 = xz - wy, r21 = yz + wx, r22 = 1.0f - (xx + yy);
-        ox = ((r00 * vx + r01 * vy) + r02 * vz) + v.cx;
-        oy = ((r10 * vx + r11 * vy) + r12 * vz) + v.cy;
-        oz = ((r20 * vx + r21 * vy) + r22 * vz) + v.cz;
+        const float q[4] = { v.qw, v.qx, v.qy, v.qz }, c[3] = { v.cx, v.cy, v.cz };
+        float R[9];
+        quatRotation(q, R);
+        rotateAdd(R, p.v, c, o);
     }
     const bool hit = !(d == 0.0f);
-    return make_float4(hit ? ox : 0.0f, hit ? oy : 0.0f, hit ? oz : 0.0f, hit ? 1.0f : 0.0f);
+    return make_float4(hit ? o[0] : 0.0f, hit ? o[1] : 0.0f, hit ? o[2] : 0.0f, hit ? 1.0f : 0.0f);
 }
 
 template <bool WORLD, bool TRANSPOSED>

@@ -11,9 +11,7 @@ Pure Python over ``load_capi()``: no rendering code, no fallback.  The tensor is
 handed to torch as a DLPack capsule built with ctypes; it keeps the renderer alive.
 """
 import ctypes
-import math
 
-from . import load_capi
 from . import _dlpack
 
 __all__ = ["attach", "Shadows", "DEFAULT_BIAS"]
@@ -28,41 +26,14 @@ def _check_arguments(apply, bias, max_distance):
     them)"""
     if not isinstance(apply, bool):
         raise ValueError("apply must be True or False, not %r" % (apply,))
-    if isinstance(bias, bool) or not isinstance(bias, (int, float)) or not math.isfinite(bias) or not bias >= 0:
-        raise ValueError("bias must be a finite number >= 0, not %r" % (bias,))
-    # (the C-ABI takes a float32: a number that is finite only in double precision is not finite there)
-    if not math.isfinite(ctypes.c_float(bias).value):
-        raise ValueError("bias must be a finite number >= 0 in single precision, not %r" % (bias,))
-    if max_distance is None:
-        return int(apply), float(bias), _FLT_MAX
-    if isinstance(max_distance, bool) or not isinstance(max_distance, (int, float)) or not math.isfinite(max_distance) \
-            or not max_distance > 0:
-        raise ValueError("max_distance must be None or a finite positive number, not %r" % (max_distance,))
-    as_f32 = ctypes.c_float(max_distance).value
-    if not math.isfinite(as_f32) or not as_f32 > 0:
-        raise ValueError("max_distance must be None or a finite positive number in single precision, not %r"
-                         % (max_distance,))
-    return int(apply), float(bias), float(max_distance)
-
-
-_LIB = None
+    b = _dlpack.float32_argument("bias", bias, "a finite number >= 0", lambda v: v >= 0)
+    return int(apply), b, _dlpack.positive_or_none("max_distance", max_distance) or _FLT_MAX
 
 
 def _capi():
-    """The library load_capi() mapped, through a handle of this module's own: the prototypes set here are not imposed
-    on other users of the shared handle."""
-    global _LIB
-    if _LIB is not None:
-        return _LIB
-    lib = ctypes.CDLL(load_capi()._name)
-    lib.mrx_shadow_create.restype = ctypes.c_int
-    lib.mrx_shadow_create.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float]
-    for name in ("mrx_shadow", "mrx_shadows"):
-        getattr(lib, name).restype = ctypes.c_int
-        getattr(lib, name).argtypes = [ctypes.c_void_p]
-    _dlpack.declare_buffers(lib)
-    _LIB = lib
-    return lib
+    return _dlpack.private_capi(__name__, {
+        "mrx_shadow_create": [ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_float],
+        "mrx_shadow": [ctypes.c_void_p], "mrx_shadows": [ctypes.c_void_p]})
 
 
 class Shadows:

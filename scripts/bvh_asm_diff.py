@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Do two versions of a device source compile to the same kernels?  Each is compiled to assembly with the product's
+"""Do two versions of the device sources compile to the same kernels?  Each is compiled to assembly with the product's
 flags (build.py hip_command) plus --cuda-device-only -S, and every kernel's instruction stream is compared after
 normalising what a source reorganisation may legitimately move: label numbers, the __hip_cuid symbol and the order
 of the two source operands of commutative scalar instructions.  No GPU needed.
@@ -7,11 +7,12 @@ of the two source operands of commutative scalar instructions.  No GPU needed.
   python scripts/bvh_asm_diff.py HEAD~1 HEAD            # two revisions of madrona_renderer_amd/csrc/bvh.hip
   python scripts/bvh_asm_diff.py HEAD WORK              # WORK = the working tree
   python scripts/bvh_asm_diff.py a.s b.s                # two assembly files made that way
-  python scripts/bvh_asm_diff.py --source madrona_renderer_amd/csrc/raster.hip HEAD WORK
+  python scripts/bvh_asm_diff.py --source rays.hip --source shadow.hip HEAD WORK      # names inside csrc/, or paths
 
-A revision is compiled inside csrc/ of the working tree (its headers are the working tree's, unless the revision's
-differ: then check the revision out and pass the .s files).  Prints the identical / different counts, and for every
-kernel that differs its code length, resource lines and mnemonic counts on both sides.
+A revision is compiled against its own headers: csrc/ and include/ of it are unpacked (git archive) into a temporary
+directory, which also takes the assembly; nothing is written into the tree.  Prints one summary line per source with
+the identical / different counts, and for every kernel that differs its code length, resource lines and mnemonic
+counts on both sides.
 """
 import collections
 import os
@@ -34,22 +35,25 @@ def device_flags():
     return [a for a in cmd[1:cmd.index(os.path.join(build.CSRC, build.HIP_SOURCES[0]))] if a != "-shared"]
 
 
-def assembly(what, source):
-    """Path of the assembly of `what`: an .s file as it is, WORK = the working tree's source, else a git revision."""
+def tree(what, tmp):
+    """The root of `what`'s sources: the working tree for WORK, else csrc/ and include/ of the revision, unpacked."""
+    if what == "WORK":
+        return ROOT
+    root = os.path.join(tmp, re.sub(r"\W", "_", what))
+    if not os.path.isdir(root):
+        os.makedirs(root)
+        tar = subprocess.check_output(["git", "-C", ROOT, "archive", what, "madrona_renderer_amd/csrc", "include"])
+        subprocess.run(["tar", "-x", "-C", root], input=tar, check=True)
+    return root
+
+
+def assembly(what, source, tmp):
+    """Path of the assembly of `source` in `what`: an .s file as it is, else compiled inside what's tree."""
     if what.endswith(".s"):
         return what
-    out = tempfile.mktemp(suffix=".s", prefix="asm_%s_" % re.sub(r"\W", "_", what))
-    src = os.path.join(ROOT, source)
-    if what != "WORK":
-        text = subprocess.check_output(["git", "-C", ROOT, "show", "%s:%s" % (what, source)])
-        src = os.path.join(os.path.dirname(src), ".asmdiff_%d_%s" % (os.getpid(), os.path.basename(source)))
-        with open(src, "wb") as f:
-            f.write(text)
-    try:
-        subprocess.check_call([build.hipcc()] + device_flags() + ["--cuda-device-only", "-S", "-x", "hip", src, "-o", out])
-    finally:
-        if what != "WORK":
-            os.unlink(src)
+    out = os.path.join(tmp, "%s_%s.s" % (re.sub(r"\W", "_", what), re.sub(r"\W", "_", source)))
+    src = os.path.join(tree(what, tmp), source)
+    subprocess.check_call([build.hipcc()] + device_flags() + ["--cuda-device-only", "-S", "-x", "hip", src, "-o", out])
     return out
 
 
@@ -95,13 +99,23 @@ def demangle(name):
 
 
 def main(argv):
-    source = "madrona_renderer_amd/csrc/bvh.hip"
-    if argv[:1] == ["--source"]:
-        source, argv = argv[1], argv[2:]
+    sources = []
+    while argv[:1] == ["--source"]:
+        sources.append(argv[1] if "/" in argv[1] else "madrona_renderer_amd/csrc/" + argv[1])
+        argv = argv[2:]
     if len(argv) != 2:
         raise SystemExit(__doc__)
-    with ThreadPoolExecutor(2) as ex:
-        a, b = ex.map(lambda w: kernels(assembly(w, source)), argv)
+    with tempfile.TemporaryDirectory(prefix="asmdiff_") as tmp:
+        for what in argv:
+            if not what.endswith(".s"):
+                tree(what, tmp)
+        jobs = [(what, source) for source in sources or ["madrona_renderer_amd/csrc/bvh.hip"] for what in argv]
+        with ThreadPoolExecutor(min(8, os.cpu_count() or 1)) as ex:
+            parsed = list(ex.map(lambda j: kernels(assembly(j[0], j[1], tmp)), jobs))
+    return max(compare(jobs[i][1], parsed[i], parsed[i + 1]) for i in range(0, len(jobs), 2))
+
+
+def compare(source, a, b):
     same, differ = 0, []
     for name in sorted(set(a) | set(b)):
         if name in a and name in b and a[name][0] == b[name][0]:
@@ -110,7 +124,8 @@ def main(argv):
                 print("resources differ though the instructions do not:", demangle(name), a[name][1], b[name][1])
         else:
             differ.append(name)
-    print("%d functions on the left, %d on the right: %d identical, %d different" % (len(a), len(b), same, len(differ)))
+    print("%s: %d functions on the left, %d on the right: %d identical, %d different"
+          % (os.path.basename(source), len(a), len(b), same, len(differ)))
     for name in differ:
         print("--", demangle(name))
         for side, k in (("left ", a.get(name)), ("right", b.get(name))):
