@@ -821,6 +821,42 @@ uint32_t mrx_group_fill(uint32_t num_cus);
  *    compute unit in the batch (BASELINE configs[4]); 1 / 0. */
 int mrx_dispatch_flat(int raytracer, uint32_t num_views, uint32_t width, uint32_t height, uint32_t max_world_triangles,
                       uint32_t max_world_instances, uint32_t num_cus);
+/*    The launch plan of the raster group kernel (host arithmetic, for tests; it touches no device): what the launcher
+ *    works out for a batch of `views` views of nslow rows of nfast pixels (64x64 tiles) over worlds of at most
+ *    max_world_triangles triangles on num_cus compute units (0 = 256).  uni_instances != 0 describes uniform worlds
+ *    (that many instances, at most 4, uni_cams_per_world cameras, the triangle prefix sums and first pool triangles
+ *    of the instances); has_blocks: the pose and geometry blocks exist; diagnostics: MRX_DEBUG_SKIP / MRX_DEBUG_STAMPS
+ *    is on (any non-zero value; 2 = the stamps alone, bit 1 of any other value adds them to a MRX_DEBUG_SKIP switch);
+ *    group_views / group_tiles / debug_slots: MRX_GROUP_VIEWS / MRX_GROUP_TILES / MRX_DEBUG_SLOTS (0 = automatic);
+ *    xcd_skew / xcd_rotate: MRX_XCD_SKEW / MRX_XCD_ROTATE (-1 = automatic); fast_allowed: MRX_GROUP_FAST; xcd_phase:
+ *    the XCD workgroup 0 last reported; has_report: a report word exists.  Returns the entry (MRX_ENTRY_GROUP_FAST or
+ *    MRX_ENTRY_GROUP), 0 for a batch of no pixels (nothing is launched, *out is zeroed), MRX_E_INVALID for a null
+ *    pointer, worlds of more than 256 triangles (the group kernel does not render them), more than 4 uniform
+ *    instances, a negative group_views / group_tiles / debug_slots, or an xcd_skew / xcd_rotate below -1.  shape,
+ *    prefix, first01 and first23 are the packed words of the FAST entry's argument header (0 for MRX_ENTRY_GROUP). */
+typedef struct {
+    uint32_t views, nfast, nslow, max_world_triangles;
+    int32_t textured;
+    uint32_t num_cus;
+    uint32_t uni_instances, uni_cams_per_world, uni_prefix[5], uni_first_tri[4];
+    int32_t has_blocks, diagnostics;
+    int32_t group_views, group_tiles, xcd_skew, xcd_rotate, debug_slots;
+    int32_t fast_allowed;
+    uint32_t xcd_phase;
+    int32_t has_report;
+} mrx_group_plan_in;
+typedef struct {
+    int32_t slots;             /* triangle slots per view: 16 ... 256 */
+    uint32_t group_views;      /* whole views per workgroup (groups_per_view = 1) */
+    uint32_t chunk_tiles;      /* tiles of one view per workgroup (groups_per_view > 1) */
+    uint32_t groups_per_view;
+    uint32_t workgroups, threads;
+    uint32_t xcd_skew, xcd_rotate;
+    int32_t xmode;             /* bit 0: the workgroups of a pair trade places, bit 1: workgroup 0 reports its XCD */
+    int32_t fast;
+    uint32_t shape, prefix, first01, first23;
+} mrx_group_plan_t;
+int mrx_group_plan(const mrx_group_plan_in *in, mrx_group_plan_t *out);
 
 /* -- per-view projection.  View indices are the whole job's (a renderer of several shards splits the range).
  *    mrx_set_view_projection sets views [first_view, first_view + count) and is stream-ordered: renders enqueued

@@ -305,6 +305,62 @@ int mrx_dispatch_flat(int raytracer, uint32_t num_views, uint32_t width, uint32_
                                 max_world_instances, num_cus) ? 1 : 0;
 }
 
+int mrx_group_plan(const mrx_group_plan_in *in, mrx_group_plan_t *out)
+{
+    if (!in || !out)
+        return fail(MRX_E_INVALID, "null argument");
+    if (in->max_world_triangles > 256u)
+        return fail(MRX_E_INVALID, "the group kernel renders worlds of at most 256 triangles");
+    if (in->uni_instances > 4u)
+        return fail(MRX_E_INVALID, "uniform worlds have at most 4 instances");
+    if (in->group_views < 0 || in->group_tiles < 0 || in->debug_slots < 0 || in->xcd_skew < -1 || in->xcd_rotate < -1)
+        return fail(MRX_E_INVALID, "override out of range");
+    // (never dereferenced: groupPlan looks at the pointers' values only)
+    static const char block = 0;
+    static uint32_t word = 0;
+    static unsigned long long stamp = 0;
+    mrx::RasterParams p {};
+    p.numViews = in->views; p.nfast = in->nfast; p.nslow = in->nslow;
+    p.tilesFast = (in->nfast + 63u) / 64u;
+    p.tilesSlow = (in->nslow + 63u) / 64u;
+    p.anyTextured = in->textured != 0;
+    p.numCUs = in->num_cus;
+    p.uniInstances = in->uni_instances;
+    p.uniCamsPerWorld = in->uni_cams_per_world;
+    std::memcpy(p.uniPrefix, in->uni_prefix, sizeof p.uniPrefix);
+    std::memcpy(p.uniFirstTri, in->uni_first_tri, sizeof p.uniFirstTri);
+    p.poseBlock = p.geomBlock = in->has_blocks ? &block : nullptr;
+    // (any non-zero value is "on": 2 the stamps alone, every other value a MRX_DEBUG_SKIP switch, with bit 1 the stamps too)
+    p.debugSkip = (in->diagnostics & ~2) ? 1u : 0u;
+    p.debugStamps = (in->diagnostics & 2) ? &stamp : nullptr;
+    p.grpViewsWanted = in->group_views;
+    p.grpTilesWanted = in->group_tiles;
+    p.xcdSkewWanted = in->xcd_skew;
+    p.xcdRotateWanted = in->xcd_rotate;
+    p.debugSlots = in->debug_slots;
+    p.xcdPhase = in->xcd_phase;
+    p.xccReport = in->has_report ? &word : nullptr;
+    *out = mrx_group_plan_t {};
+    if ((uint64_t)p.numViews * p.tilesFast * p.tilesSlow == 0)
+        return MRX_ENTRY_NONE;
+    const mrx::GroupPlan plan = mrx::groupPlan(p, in->max_world_triangles, in->fast_allowed != 0);
+    out->slots = plan.slots;
+    out->group_views = plan.grpViews;
+    out->chunk_tiles = plan.grpChunkTiles;
+    out->groups_per_view = plan.grpPerView;
+    out->workgroups = plan.workgroups;
+    out->threads = plan.threads;
+    out->xcd_skew = plan.xcdSkew;
+    out->xcd_rotate = plan.xcdRotate;
+    out->xmode = plan.xmode;
+    out->fast = plan.fast ? 1 : 0;
+    out->shape = plan.header.shape;
+    out->prefix = plan.header.prefix;
+    out->first01 = plan.header.first01;
+    out->first23 = plan.header.first23;
+    return plan.fast ? MRX_ENTRY_GROUP_FAST : MRX_ENTRY_GROUP;
+}
+
 int mrx_blas_check(const float *tri_pos, uint32_t num_tris, uint32_t *num_nodes, uint32_t *depth,
                    uint32_t *num_leaves)
 {

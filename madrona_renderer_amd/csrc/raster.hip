@@ -31,7 +31,6 @@ constexpr int kWavesPerBlock = 4;
 // launch bounds of the brute and the chunked kernels, uniform and form alike (the second bound is waves per SIMD)
 constexpr int kBruteThreads = kWave * kWavesPerBlock;
 constexpr int kChunkedThreads = kWave * kWavesPerBlock, kChunkedWavesPerSimd = 3;
-constexpr int kChunk = 64;       // triangles set up per pass (one per lane)
 constexpr int kHot = 16;         // dwords: edges, depth plane, rgba, tex, seg, k
 constexpr int kBandRows = 16;    // a band is 64 x 16 pixels = 16 blocks of 8x8
 constexpr int kBlocksPerBand = 16;
@@ -130,6 +129,24 @@ __device__ __forceinline__ bool setupTriangleProj(const RasterParams &p, const V
     if (LAB)
         applyLabel(shade, p.instLabel, wt.inst);
     return valid;
+}
+
+// A TriPlanes of zeros: what an idle slot publishes.
+__device__ __forceinline__ void zeroPlanes(TriPlanes &c)
+{
+    c.A0 = c.B0 = c.C0 = c.A1 = c.B1 = c.C1 = 0.0f;
+    c.A2 = c.B2 = c.C2 = c.Dx = c.Dy = c.Dc = 0.0f;
+    c.bbX0 = c.bbX1 = c.bbY0 = c.bbY1 = 0.0f;
+}
+// The planes of a triangle as phase R reads them from LDS (loadPlanes): A0 A1 A2 Dx | B0 B1 B2 Dy | C0 C1 C2 Dc, and a
+// fourth float4 that is the kernel's own -- the bounding box in the group kernel, the region mask in the chunked one.
+__device__ __forceinline__ void publishPlanes(float (&rec)[16], const TriPlanes &c, float4 fourth)
+{
+    float4 *dst = reinterpret_cast<float4 *>(rec);
+    dst[0] = make_float4(c.A0, c.A1, c.A2, c.Dx);
+    dst[1] = make_float4(c.B0, c.B1, c.B2, c.Dy);
+    dst[2] = make_float4(c.C0, c.C1, c.C2, c.Dc);
+    dst[3] = fourth;
 }
 
 // S for one chunk of up to 64 world-triangles; returns the valid-lane mask.
@@ -566,9 +583,7 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
             const int rec = wave * kWave + lane;
             const uint32_t k = pass + (uint32_t)rec;
             TriPlanes c;
-            c.A0 = c.B0 = c.C0 = c.A1 = c.B1 = c.C1 = 0.0f;
-            c.A2 = c.B2 = c.C2 = c.Dx = c.Dy = c.Dc = 0.0f;
-            c.bbX0 = c.bbX1 = c.bbY0 = c.bbY1 = 0.0f;
+            zeroPlanes(c);
             uint32_t mask = 0;
             // whole waves past the end of the list skip the setup code
             if (pass + (uint32_t)(wave * kWave) < t.numTris) {
@@ -589,11 +604,7 @@ __device__ __forceinline__ void chunkedKernelBody(const RasterParams p)
                 if (valid && !(p.debugSkip & 4u))
                     mask = classifyRegions(c, t, invNear, invFar);
             }
-            float4 *dst = reinterpret_cast<float4 *>(lds.planes[rec]);
-            dst[0] = make_float4(c.A0, c.A1, c.A2, c.Dx);
-            dst[1] = make_float4(c.B0, c.B1, c.B2, c.Dy);
-            dst[2] = make_float4(c.C0, c.C1, c.C2, c.Dc);
-            dst[3] = make_float4(__uint_as_float(mask), 0.f, 0.f, 0.f);
+            publishPlanes(lds.planes[rec], c, make_float4(__uint_as_float(mask), 0.f, 0.f, 0.f));   // the fourth: the mask
         }
         __syncthreads();
 
@@ -671,14 +682,7 @@ void rasterChunkedFormKernel(const RasterParams p)
 //   R+O all waves pull (tile, strip) items off an LDS counter, rasterise the
 //       strip's two regions and store them.
 // ---------------------------------------------------------------------------
-// A group is up to 16 tiles drawn from one or more views whose triangles fit
-// the records together (setup is per view, shared by the view's tiles).  Up to
-// 64 slots per view the group holds kChunk records (with the XCD-aware split
-// a workgroup on a fast XCD carries one 16-slot view more); views of 128 / 256
-// slots are one view per group.
-constexpr int kGroupTilesMax = 16;
-constexpr int kGroupSlotsMax = 256;
-constexpr int groupTilesMax(int slots) { return slots <= 128 ? kGroupTilesMax : 8; }
+// (the group's limits -- kGroupTilesMax, kGroupSlotsMax, groupTilesMax -- and groupWaves: raster.hpp, beside the launch plan)
 
 template <int SLOTS, bool PV = false>
 struct GroupLds {
@@ -853,11 +857,6 @@ __device__ __forceinline__ uint32_t classifyPair(const LDS &L, int j, int k, int
     return m;
 }
 
-// Waves per workgroup of the group kernel: eight for untextured scenes (more
-// waves in flight absorb the stalls of a saturated store path), four for the
-// textured variant (its texel loads cost registers and vmcnt drains).
-constexpr int groupWaves(bool tex) { return tex ? 4 : 8; }
-
 // XMODE (16-slot instantiations only): bit 0 = the workgroups of every pair trade places
 // (XCD phase, below), bit 1 = workgroup 0 reports the XCD it runs on.  Separate
 // instantiations, chosen per launch by the host, because any extra state in this kernel's
@@ -885,12 +884,42 @@ constexpr int groupWaves(bool tex) { return tex ? 4 : 8; }
 // the record's label slot.  Everything optional is taken as the normals form takes it: the colour and material columns
 // behind null tests, the XCD trade and report at run time, so one form per family and normals setting covers every
 // renderer with the column (which always launches with the per-view tables filled).
-template <bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT, bool PV = false, bool LT = false, bool COL = false,
-          bool MAT = false, bool NRM = false, bool LAB = false>
+// What an instantiation of the body is: the settings above by name.  GroupKindOf makes a type of one (C++17 has no
+// class-type template arguments) from the parameters the entries have themselves; the form's flags come from formFlags.
+struct GroupKind {
+    bool ids;
+    int slots;
+    bool tex;
+    int xmode;
+    bool fast;
+    int out;
+    FormFlags form;
+};
+template <KernelForm F, bool IDS, int SLOTS, bool TEX, int XMODE, bool FAST, int OUT>
+struct GroupKindOf {
+    static constexpr GroupKind value()
+    {
+        GroupKind k {};
+        k.ids = IDS;
+        k.slots = SLOTS;
+        k.tex = TEX;
+        k.xmode = XMODE;
+        k.fast = FAST;
+        k.out = OUT;
+        k.form = formFlags(F);
+        return k;
+    }
+};
+
+template <typename KIND>
 __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *hGeom, uint32_t hViews, uint32_t hInstances,
                                                 uint32_t hPool, uint32_t hShape, uint32_t hGroups, uint32_t hPrefix,
                                                 uint32_t hFirst01, uint32_t hFirst23, const RasterParams p)
 {
+    constexpr GroupKind K = KIND::value();
+    constexpr bool IDS = K.ids, TEX = K.tex, FAST = K.fast;
+    constexpr int SLOTS = K.slots, XMODE = K.xmode, OUT = K.out;
+    constexpr bool PV = K.form.pv, LT = K.form.lt, COL = K.form.col, MAT = K.form.mat, NRM = K.form.nrm, LAB = K.form.lab;
     __shared__ GroupLds<SLOTS, PV> lds;
     constexpr int kBackground = GroupLds<SLOTS, PV>::kBackground;
     __shared__ uint32_t nrmLds[NRM ? GroupLds<SLOTS, PV>::kRecs + 1 : 1];   // [record], the background's last
@@ -902,15 +931,15 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     // the other waves touch it for the whole CU, whose scalar cache they share)
     if (!FAST || wave >= 2)
         touchKernelArguments<(FAST ? 48 : 0) + sizeof(RasterParams)>();
-    // what the prologue reads of the arguments: from the preloaded header (FAST) or from `p`
+    // ==== arguments ====  what the prologue reads: from the preloaded header (FAST) or from `p`
     const uint32_t aNumViews = FAST ? hViews : p.numViews;
-    const uint32_t aGrpViews = FAST ? (hShape & 255u) : p.grpViews;
-    const uint32_t aXcdSkew = FAST ? ((hShape >> 8) & 15u) : p.xcdSkew;
-    const uint32_t aXcdRotate = FAST ? ((hShape >> 12) & 1u) : p.xcdRotate;
+    const uint32_t aGrpViews = FAST ? hdrGrpViews(hShape) : p.grpViews;
+    const uint32_t aXcdSkew = FAST ? hdrXcdSkew(hShape) : p.xcdSkew;
+    const uint32_t aXcdRotate = FAST ? hdrXcdRotate(hShape) : p.xcdRotate;
     const uint32_t aGrpPerView = FAST ? 1u : p.grpPerView;
     const uint32_t aGrid = FAST ? hGroups : gridDim.x;
-    const uint32_t aUniInstances = FAST ? ((hShape >> 13) & 7u) : p.uniInstances;
-    const uint32_t aUniCams = FAST ? ((hShape >> 16) & 255u) : p.uniCamsPerWorld;
+    const uint32_t aUniInstances = FAST ? hdrUniInstances(hShape) : p.uniInstances;
+    const uint32_t aUniCams = FAST ? hdrUniCams(hShape) : p.uniCamsPerWorld;
     const uint32_t dskip = FAST ? 0u : p.debugSkip;           // (the host never picks FAST with diagnostics on)
     const PoseLayout lay = poseLayout(hViews, hInstances);
     const float *aCamRot = FAST ? reinterpret_cast<const float *>(hPose + lay.camRot) : p.camRot;
@@ -930,7 +959,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     // The plain entry and the textured kernels keep the per-tile masks: measured slower with the items
     //  -- the plain entry carries both loops, the textured one lost its register budget.
     constexpr bool readyItems = FAST && !TEX;
-    // ---- which views / tiles this workgroup owns (launchRaster):
+    // ==== ownership ====  which views / tiles this workgroup owns (groupPlan, raster.hpp):
     //  A  grpPerView == 1: grpViews whole views (all their tiles);
     //  B  otherwise: grpChunkTiles tiles of one view.
     uint32_t firstView, groupViews, firstTile, groupTiles;
@@ -966,7 +995,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
         firstTile = (bid - firstView * aGrpPerView) * p.grpChunkTiles;
         groupTiles = min(p.grpChunkTiles, tilesPerView - firstTile);
     }
-    // XCD-aware split (see launchRaster; one-tile views, four per group):
+    // XCD-aware split (see groupPlan; one-tile views, four per group):
     // consecutive workgroups run on consecutive XCDs and the odd XCD of each pair
     // drains its stores more slowly.  Workgroups 2m and 2m+1 (after the trade above:
     // even = on an even XCD) share the view between their two runs of four: the odd
@@ -999,7 +1028,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
         for (int i = threadIdx.x; i < numPairs; i += groupWaves(TEX) * kWave)
             lds.masks[i] = 0u;
 
-    // ---- S1: one lane per (view vi of the group, triangle slot k): setup.
+    // ==== S1: tile notes and item order (the last wave) ====
+    //      S1 is one lane per (view vi of the group, triangle slot k): setup.
     //      Wave 0 covers the first 64 records, wave 1 a fifth 16-slot view or
     //      the next 64 slots of a large view, ...  Meanwhile the last wave
     //      notes where each tile of the group lies.
@@ -1043,6 +1073,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             base += (uint32_t)__builtin_popcountll(m);
         }
     }
+    // ==== S1: set-up per record ====
     if (wave * kWave < groupRecs) {
         const int rec = wave * kWave + lane;
         const int vi = rec / SLOTS, k = rec % SLOTS;
@@ -1057,10 +1088,10 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
         if (aUniInstances) {
             const uint32_t kk = (uint32_t)k;
             // (FAST: the table rides in the header, eight / sixteen bits per entry)
-            const uint32_t pre1 = FAST ? (hPrefix & 255u) : p.uniPrefix[1], pre2 = FAST ? ((hPrefix >> 8) & 255u) : p.uniPrefix[2];
-            const uint32_t pre3 = FAST ? ((hPrefix >> 16) & 255u) : p.uniPrefix[3], pre4 = FAST ? (hPrefix >> 24) : p.uniPrefix[4];
-            const uint32_t ft0 = FAST ? (hFirst01 & 0xFFFFu) : p.uniFirstTri[0], ft1 = FAST ? (hFirst01 >> 16) : p.uniFirstTri[1];
-            const uint32_t ft2 = FAST ? (hFirst23 & 0xFFFFu) : p.uniFirstTri[2], ft3 = FAST ? (hFirst23 >> 16) : p.uniFirstTri[3];
+            const uint32_t pre1 = FAST ? hdrPrefix(hPrefix, 1) : p.uniPrefix[1], pre2 = FAST ? hdrPrefix(hPrefix, 2) : p.uniPrefix[2];
+            const uint32_t pre3 = FAST ? hdrPrefix(hPrefix, 3) : p.uniPrefix[3], pre4 = FAST ? hdrPrefix(hPrefix, 4) : p.uniPrefix[4];
+            const uint32_t ft0 = FAST ? hdrFirst(hFirst01, 0) : p.uniFirstTri[0], ft1 = FAST ? hdrFirst(hFirst01, 1) : p.uniFirstTri[1];
+            const uint32_t ft2 = FAST ? hdrFirst(hFirst23, 2) : p.uniFirstTri[2], ft3 = FAST ? hdrFirst(hFirst23, 3) : p.uniFirstTri[3];
             const uint32_t li = (kk >= pre1 ? 1u : 0u) + (kk >= pre2 ? 1u : 0u) + (kk >= pre3 ? 1u : 0u);
             const uint32_t pre = li == 0 ? 0u : li == 1 ? pre1 : li == 2 ? pre2 : pre3;
             const uint32_t first = li == 0 ? ft0 : li == 1 ? ft1 : li == 2 ? ft2 : ft3;
@@ -1095,9 +1126,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
             }
         }
         TriPlanes c;
-        c.A0 = c.B0 = c.C0 = c.A1 = c.B1 = c.C1 = 0.0f;
-        c.A2 = c.B2 = c.C2 = c.Dx = c.Dy = c.Dc = 0.0f;
-        c.bbX0 = c.bbX1 = c.bbY0 = c.bbY1 = 0.0f;
+        zeroPlanes(c);
         bool valid = false;
         MRX_STAMP(1);
         if (recOk) {
@@ -1114,32 +1143,24 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                     pr.sx, pr.ox, pr.sz, pr.oz, pr.s6bPad, lt.ambient, lt.diffuse, p.transposed };
                 InstXform x;
                 instanceTransform(sa, vc, wt.inst, x);
-                if (BYPTR) {
-                    const MatOverride mo = { aInstMat ? aInstMat[wt.inst] : -1, p.numMaterials, p.matTable };
+                // one dispatch: the by-pointer forms (NRM, LAB) take every column behind a null test and set everything up,
+                // the others what their parameters name; NRM: the packed normal goes to the array beside the records
+                const MatOverride mo = { BYPTR ? (aInstMat ? aInstMat[wt.inst] : -1) : MAT ? aInstMat[wt.inst] : -1,
+                                         p.numMaterials, p.matTable };
+                const auto nrmOut = [&] {
                     if constexpr (NRM)
-                        valid = setupTriangleCore<true, true, true, true>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
-                                                                          lds.shade[rec], lds.cold[rec],
-                                                                          aInstColor ? aInstColor[wt.inst] : 0u, mo,
-                                                                          NormalOut { nrmLds + rec });
+                        return NormalOut { nrmLds + rec };
                     else
-                        valid = setupTriangleCore<true, true, true, true>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
-                                                                          lds.shade[rec], lds.cold[rec],
-                                                                          aInstColor ? aInstColor[wt.inst] : 0u, mo);
-                    if (LAB)
-                        applyLabel(lds.shade[rec], p.instLabel, wt.inst);
-                } else {
-                const MatOverride mo = { MAT ? aInstMat[wt.inst] : -1, p.numMaterials, p.matTable };
-                valid = setupTriangleCore<true, OUT != kOutDepth, COL, MAT>(sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c,
-                                                                            lds.shade[rec], lds.cold[rec],
-                                                                            COL ? aInstColor[wt.inst] : 0u, mo);
-                }
+                        return NoNormalOut {};
+                }();
+                valid = setupTriangleCore<true, BYPTR || OUT != kOutDepth, BYPTR || COL, BYPTR || MAT>(
+                    sa, vc.lv, x, wt.tri, aInstObj[wt.inst], k, c, lds.shade[rec], lds.cold[rec],
+                    BYPTR ? (aInstColor ? aInstColor[wt.inst] : 0u) : COL ? aInstColor[wt.inst] : 0u, mo, nrmOut);
+                if (LAB)
+                    applyLabel(lds.shade[rec], p.instLabel, wt.inst);
             }
             MRX_STAMP(2);
-            float4 *dst = reinterpret_cast<float4 *>(lds.planes[rec]);
-            dst[0] = make_float4(c.A0, c.A1, c.A2, c.Dx);
-            dst[1] = make_float4(c.B0, c.B1, c.B2, c.Dy);
-            dst[2] = make_float4(c.C0, c.C1, c.C2, c.Dc);
-            dst[3] = make_float4(c.bbX0, c.bbX1, c.bbY0, c.bbY1);
+            publishPlanes(lds.planes[rec], c, make_float4(c.bbX0, c.bbX1, c.bbY0, c.bbY1));       // the fourth: the box
             lds.live[rec] = (valid && !(dskip & 4u)) ? 1u : 0u;
         }
         if (rec == 0) {
@@ -1155,7 +1176,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     __syncthreads();
     MRX_STAMP(3);
 
-    // ---- S2: classification of every (tile, triangle slot) pair against the
+    // ==== S2: ready items | masks ====
+    //      classification of every (tile, triangle slot) pair against the
     //      tile's sixteen 32x8 regions.  Wave w takes strips 2(w&3), 2(w&3)+1
     //      (four regions) of the pairs (w>>2)*64 + lane, + 64 * (waves / 4), ...;
     //      results are OR-ed in LDS: bits 0..15 regions, bits 16..19
@@ -1206,7 +1228,8 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
     __syncthreads();
     MRX_STAMP(4);
 
-    // ---- R + O: the four waves pull (tile, strip) work items off an LDS
+    // ==== R + O: item fetch (ready items | tile masks), then the strip's two regions ====
+    //      the four waves pull (tile, strip) work items off an LDS
     //      counter -- strips differ a lot in cost (sky vs. ground vs. objects),
     //      a static split leaves waves idle
     // lane -> four consecutive pixels of one row of a 32x8 region (a 64x4
@@ -1304,6 +1327,7 @@ __device__ __forceinline__ void groupKernelBody(const char *hPose, const char *h
                         pxTile[hf][b] = (float)(tileX0 + hf * 32 + 4 * lx + b);
             }
         }
+        // ==== R + O: the regions of the item ====
         const uint32_t fy = tileY0 + strip * 8 + ly;
         const float py = (float)fy;
 #pragma unroll
@@ -1392,7 +1416,7 @@ template <bool IDS, int SLOTS, bool TEX, int XMODE = 0, int OUT = kOutRGBD>
 __global__ __launch_bounds__(groupThreads(TEX), groupWavesPerSimd(KernelForm::Uniform, SLOTS, TEX))
 void rasterGroupKernel(const RasterParams p)
 {
-    groupKernelBody<IDS, SLOTS, TEX, XMODE, false, OUT>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
+    groupKernelBody<GroupKindOf<KernelForm::Uniform, IDS, SLOTS, TEX, XMODE, false, OUT>>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
 }
 
 // OUT: output selection (raster.hpp OutSel: kOutRGBD, kOutDepth or kOutRGB), fixed per instantiation
@@ -1402,8 +1426,8 @@ void rasterGroupKernelFast(const char *hPose, const char *hGeom, uint32_t hViews
                            uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
                            const RasterParams p)
 {
-    groupKernelBody<IDS, 16, TEX, XMODE, true, OUT>(hPose, hGeom, hViews, hInstances, hPool, hShape, hGroups, hPrefix, hFirst01,
-                                               hFirst23, p);
+    groupKernelBody<GroupKindOf<KernelForm::Uniform, IDS, 16, TEX, XMODE, true, OUT>>(hPose, hGeom, hViews, hInstances, hPool, hShape,
+                                                                                   hGroups, hPrefix, hFirst01, hFirst23, p);
 }
 
 // The form kernels of both entry points (raster.hpp KernelForm, formFlags): XMODE 0 (the XCD phase
@@ -1427,10 +1451,8 @@ template <KernelForm F, bool IDS, int SLOTS, bool TEX>
 __global__ __launch_bounds__(groupThreads(TEX), groupWavesPerSimd(F, SLOTS, TEX))
 void rasterGroupFormKernel(const RasterParams p)
 {
-    constexpr FormFlags f = formFlags(F);
-    static_assert(F != KernelForm::Uniform && F != KernelForm::PVM && (IDS || !f.lab), "the forms of this family");
-    groupKernelBody<IDS, SLOTS, TEX, 0, false, kOutByPointer, f.pv, f.lt, f.col, f.mat, f.nrm, f.lab>(
-        nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
+    static_assert(F != KernelForm::Uniform && F != KernelForm::PVM && (IDS || !formFlags(F).lab), "the forms of this family");
+    groupKernelBody<GroupKindOf<F, IDS, SLOTS, TEX, 0, false, kOutByPointer>>(nullptr, nullptr, 0u, 0u, 0u, 0u, 0u, 0u, 0u, 0u, p);
 }
 
 // (the argument list is the FAST entry's: ten header words, then RasterParams -- the body relies on their preload)
@@ -1440,10 +1462,9 @@ void rasterGroupFormKernelFast(const char *hPose, const char *hGeom, uint32_t hV
                                uint32_t hShape, uint32_t hGroups, uint32_t hPrefix, uint32_t hFirst01, uint32_t hFirst23,
                                const RasterParams p)
 {
-    constexpr FormFlags f = formFlags(F);
-    static_assert(F != KernelForm::Uniform && F != KernelForm::PVM && (IDS || !f.lab), "the forms of this family");
-    groupKernelBody<IDS, 16, TEX, 0, true, kOutByPointer, f.pv, f.lt, f.col, f.mat, f.nrm, f.lab>(
-        hPose, hGeom, hViews, hInstances, hPool, hShape, hGroups, hPrefix, hFirst01, hFirst23, p);
+    static_assert(F != KernelForm::Uniform && F != KernelForm::PVM && (IDS || !formFlags(F).lab), "the forms of this family");
+    groupKernelBody<GroupKindOf<F, IDS, 16, TEX, 0, true, kOutByPointer>>(hPose, hGeom, hViews, hInstances, hPool, hShape, hGroups, hPrefix,
+                                                                      hFirst01, hFirst23, p);
 }
 
 // ---- which form a launch takes (host; first match wins) ---------------------------------------------------------------
@@ -1477,6 +1498,119 @@ KernelForm groupForm(const RasterParams &p)
     return KernelForm::Uniform;
 }
 
+// ---- the three launchers behind launchRaster -------------------------------------------------------------------------
+// v1 reference: one wave per tile, every triangle at every pixel
+void launchBrute(const RasterParams &p, uint32_t items, bool multi, hipStream_t stream, LaunchForm *took)
+{
+    const dim3 block(kWave * kWavesPerBlock);
+    const bool ids = p.ids != nullptr;
+    const dim3 grid((items + kWavesPerBlock - 1) / kWavesPerBlock);
+    const KernelForm form = tileForm(p);
+    if (took) *took = LaunchForm { (int32_t)form, 0 };
+    const OutSel out = outSelOf(p.rgb, p.depth);
+    const auto byIdsMulti = [&](auto f) {
+        withBool(ids, [&](auto IDS) { withBool(multi, [&](auto MULTI) { f(IDS, MULTI); }); });
+    };
+    if (form != KernelForm::Uniform)
+        withValue<KernelForm, KernelForm::NPV, KernelForm::N, KernelForm::PV>(form, [&](auto F) {
+            byIdsMulti([&](auto IDS, auto MULTI) {
+                rasterBruteFormKernel<decltype(F)::value, decltype(IDS)::value, decltype(MULTI)::value><<<grid, block, 0, stream>>>(p);
+            });
+        });
+    else
+        withValue<int, kOutDepth, kOutRGB, kOutRGBD>(out, [&](auto O) {
+            byIdsMulti([&](auto IDS, auto MULTI) {
+                rasterBruteKernel<decltype(IDS)::value, decltype(MULTI)::value, decltype(O)::value><<<grid, block, 0, stream>>>(p);
+            });
+        });
+}
+
+// more triangles per world than the group kernel holds: one workgroup per tile
+void launchChunked(const RasterParams &p, uint32_t items, hipStream_t stream, LaunchForm *took)
+{
+    const dim3 block(kWave * kWavesPerBlock);
+    const bool ids = p.ids != nullptr;
+    const KernelForm form = tileForm(p);
+    if (took) *took = LaunchForm { (int32_t)form, 0 };
+    withBool(ids, [&](auto IDS) {
+        constexpr bool kIds = decltype(IDS)::value;
+        if (form != KernelForm::Uniform)
+            withValue<KernelForm, KernelForm::PV, KernelForm::N, KernelForm::NPV>(form, [&](auto F) {
+                rasterChunkedFormKernel<decltype(F)::value, kIds><<<dim3(items), block, 0, stream>>>(p);
+            });
+        else
+            rasterChunkedKernel<kIds><<<dim3(items), block, 0, stream>>>(p);
+    });
+}
+
+// the group kernel in the shape `plan` gives it (raster.hpp groupPlan)
+void launchGroup(const RasterParams &p, const GroupPlan &plan, hipStream_t stream, LaunchForm *took)
+{
+    RasterParams q = p;
+    q.grpViews = plan.grpViews;
+    q.grpChunkTiles = plan.grpChunkTiles;
+    q.grpPerView = plan.grpPerView;
+    q.xcdSkew = plan.xcdSkew;
+    q.xcdRotate = plan.xcdRotate;
+    const dim3 grid(plan.workgroups);
+    const dim3 gblock(plan.threads);
+    const GroupHeader &h = plan.header;
+    const int slots = plan.slots, xmode = plan.xmode;
+    const bool fast = plan.fast, ids = p.ids != nullptr;
+    // Instantiation choice: the form (groupForm), then slots x ids x textured; the uniform kernels by XMODE and OUT
+    // too.  FAST and XMODE 1..3 exist with 16 slots only, the label forms with ids only.
+    const KernelForm form = groupForm(p);
+    if (took) *took = LaunchForm { (int32_t)form, slots };
+    const bool tex = p.anyTextured != 0;
+    // output selection: one instantiation per setting (kOutRGBD = the kernels as they always were)
+    const OutSel out = outSelOf(p.rgb, p.depth);
+    const auto byTexIds = [&](auto f) {
+        withBool(tex, [&](auto TEX) { withBool(ids, [&](auto IDS) { f(IDS, TEX); }); });
+    };
+    const auto launchFast = [&](auto kernel) {        // the FAST entry: the header in front
+        kernel<<<grid, gblock, 0, stream>>>(h.pose, h.geom, h.views, h.instances, h.poolTris, h.shape, h.groups, h.prefix,
+                                            h.first01, h.first23, q);
+    };
+    const auto launchPlain = [&](auto kernel) { kernel<<<grid, gblock, 0, stream>>>(q); };
+    withValue<int, 16, 32, 64, 128, 256>(slots, [&](auto S) {
+        constexpr int kSlots = decltype(S)::value;
+        if (form != KernelForm::Uniform) {
+            withValue<KernelForm, KernelForm::PV, KernelForm::PVL, KernelForm::C, KernelForm::PVLC, KernelForm::M,
+                      KernelForm::PVLM, KernelForm::N, KernelForm::NPV, KernelForm::L, KernelForm::LN>(form, [&](auto F) {
+                constexpr KernelForm kForm = decltype(F)::value;
+                byTexIds([&](auto IDS, auto TEX) {
+                    constexpr bool kIds = decltype(IDS)::value, kTex = decltype(TEX)::value;
+                    if constexpr (kIds || !formFlags(kForm).lab) {   // (groupForm: labels with ids only)
+                        if constexpr (kSlots == 16) {
+                            if (fast)
+                                return launchFast(rasterGroupFormKernelFast<kForm, kIds, kTex>);
+                        }
+                        launchPlain(rasterGroupFormKernel<kForm, kIds, kSlots, kTex>);
+                    }
+                });
+            });
+            return;
+        }
+        withValue<int, 0, 1, 2, 3>(xmode, [&](auto X) {
+            constexpr int kX = decltype(X)::value;
+            if constexpr (kX == 0 || kSlots == 16)
+                withValue<int, kOutDepth, kOutRGB, kOutRGBD>(out, [&](auto O) {
+                    // rgb only: the FAST entry has its fixed instantiation, the plain one selects by pointer
+                    constexpr int kO = decltype(O)::value, kOP = kO == kOutRGB ? kOutByPointer : kO;
+                    if constexpr (kSlots == 16) {
+                        if (fast)
+                            return byTexIds([&](auto IDS, auto TEX) {
+                                launchFast(rasterGroupKernelFast<decltype(IDS)::value, decltype(TEX)::value, kX, kO>);
+                            });
+                    }
+                    byTexIds([&](auto IDS, auto TEX) {
+                        launchPlain(rasterGroupKernel<decltype(IDS)::value, kSlots, decltype(TEX)::value, kX, kOP>);
+                    });
+                });
+        });
+    });
+}
+
 }  // namespace
 
 hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
@@ -1485,189 +1619,19 @@ hipError_t launchRaster(const RasterParams &p, uint32_t maxWorldTris,
     const uint32_t items = p.numViews * p.tilesFast * p.tilesSlow;
     if (items == 0)
         return hipSuccess;
-    const dim3 block(kWave * kWavesPerBlock);
-    const bool ids = p.ids != nullptr;
-    const bool multi = maxWorldTris > (uint32_t)kChunk;       // brute variant: chunk loop
-    const bool large = maxWorldTris > (uint32_t)kGroupSlotsMax;
     if (variant == kVariantBrute) {
-        // v1 reference: one wave per tile, every triangle at every pixel
         if (entry) *entry = kEntryBrute;
-        const dim3 grid((items + kWavesPerBlock - 1) / kWavesPerBlock);
-        const KernelForm form = tileForm(p);
-        if (took) *took = LaunchForm { (int32_t)form, 0 };
-        const OutSel out = outSelOf(p.rgb, p.depth);
-        const auto byIdsMulti = [&](auto f) {
-            withBool(ids, [&](auto IDS) { withBool(multi, [&](auto MULTI) { f(IDS, MULTI); }); });
-        };
-        if (form != KernelForm::Uniform)
-            withValue<KernelForm, KernelForm::NPV, KernelForm::N, KernelForm::PV>(form, [&](auto F) {
-                byIdsMulti([&](auto IDS, auto MULTI) {
-                    rasterBruteFormKernel<decltype(F)::value, decltype(IDS)::value, decltype(MULTI)::value><<<grid, block, 0, stream>>>(p);
-                });
-            });
-        else
-            withValue<int, kOutDepth, kOutRGB, kOutRGBD>(out, [&](auto O) {
-                byIdsMulti([&](auto IDS, auto MULTI) {
-                    rasterBruteKernel<decltype(IDS)::value, decltype(MULTI)::value, decltype(O)::value><<<grid, block, 0, stream>>>(p);
-                });
-            });
-    } else if (large) {
-        // more triangles per world than the group kernel holds: one workgroup per tile
+        launchBrute(p, items, maxWorldTris > (uint32_t)kChunk, stream, took);     // (above a chunk: the chunk loop)
+    } else if (maxWorldTris > (uint32_t)kGroupSlotsMax) {
         if (entry) *entry = kEntryChunked;
-        const KernelForm form = tileForm(p);
-        if (took) *took = LaunchForm { (int32_t)form, 0 };
-        withBool(ids, [&](auto IDS) {
-            constexpr bool kIds = decltype(IDS)::value;
-            if (form != KernelForm::Uniform)
-                withValue<KernelForm, KernelForm::PV, KernelForm::N, KernelForm::NPV>(form, [&](auto F) {
-                    rasterChunkedFormKernel<decltype(F)::value, kIds><<<dim3(items), block, 0, stream>>>(p);
-                });
-            else
-                rasterChunkedKernel<kIds><<<dim3(items), block, 0, stream>>>(p);
-        });
+        launchChunked(p, items, stream, took);
     } else {
-        // triangle slots per view: the smallest of 16 ... 256 that holds a world
-        int slots = 16;
-        while ((uint32_t)slots < maxWorldTris)
-            slots *= 2;
-        if (p.debugSlots >= slots && p.debugSlots <= kGroupSlotsMax && (p.debugSlots & (p.debugSlots - 1)) == 0)
-            slots = p.debugSlots;                 // tuning / test aid (MRX_DEBUG_SLOTS)
-        // Workgroup shape.  Setup is per view and the view's tiles share it, so
-        // a workgroup takes as many whole views as fit 64 records and 16 tiles
-        // (8 for views of 256 slots); a view of more tiles is cut into chunks.
-        // Small batches shrink the workgroups again until there are ~4 per CU.
-        const uint32_t tpv = p.tilesFast * p.tilesSlow;
-        const uint32_t maxTiles = (uint32_t)groupTilesMax(slots);
-        const uint32_t kFill = groupFill(p.numCUs);    // 4 resident workgroups per CU: 1024 on 256 CUs
-        RasterParams q = p;
-        uint32_t vg = 1, ct = tpv, gpv = 1;
-        if (tpv == 1) {
-            // one-tile views: as many as fit 64 records, all workgroups resident
-            // (textured: two -- its workgroups have four waves and longer tiles)
-            vg = std::max<uint32_t>(1u, (uint32_t)(kChunk / slots));
-            if (p.anyTextured)
-                vg = std::min<uint32_t>(vg, 2u);
-            // ... until ~4 workgroups per CU remain; two views per workgroup are kept
-            // down to 2 per CU (1024 worlds: 9.9 -> 9.3 us)
-            while (vg > 1 && (p.numViews + vg - 1) / vg < (vg == 2 ? kFill / 2 : kFill))
-                vg /= 2;
-        } else if (p.anyTextured) {
-            // textured, several tiles per view: a quarter of a view per workgroup, at most four
-            // tiles (4 waves per workgroup and per-pixel texturing make a tile long enough for
-            // its own setup; measured on 128^2 and 256^2: profiles/r01_group_shapes.txt)
-            ct = std::max<uint32_t>(1u, std::min<uint32_t>(4u, tpv / 4u));
-        } else {
-            // untextured, several tiles per view: one view per workgroup, at most eight tiles
-            ct = std::min<uint32_t>(tpv, std::min<uint32_t>(maxTiles, 8u));
-        }
-        if (tpv != 1)
-            while (ct > 1 && (uint64_t)p.numViews * ((tpv + ct - 1) / ct) < kFill)
-                ct = (ct + 1) / 2;
-        if (p.grpViewsWanted > 0 && tpv * (uint32_t)p.grpViewsWanted <= maxTiles &&
-            p.grpViewsWanted * slots <= kChunk) {
-            vg = (uint32_t)p.grpViewsWanted;
-            ct = tpv;
-        }
-        if (p.grpTilesWanted > 0 && (uint32_t)p.grpTilesWanted <= maxTiles) {
-            vg = 1;
-            ct = std::min<uint32_t>((uint32_t)p.grpTilesWanted, tpv);
-        }
-        gpv = (tpv + ct - 1) / ct;
-        q.grpViews = vg;
-        q.grpChunkTiles = ct;
-        q.grpPerView = gpv;
-        const uint32_t numGroups = gpv == 1 ? (p.numViews + vg - 1) / vg : p.numViews * gpv;
-        // XCD-aware split.  Workgroups go round-robin to the eight XCDs and the
-        // odd XCD of every pair drains its stores ~15 % more slowly (measured,
-        // profiles/r01_xcd.txt): once the batch fills the chip, xcdSkew strips
-        // (eighths of a tile) per workgroup pair move from the odd to the even
-        // XCD (see the kernel prologue).
-        const bool skewable = slots == 16 && tpv == 1 && (vg == 4 || vg == 2);
-        q.xcdSkew = (skewable && numGroups >= kFill) ? (vg == 4 ? 3u : 1u) : 0u;
-        if (p.xcdSkewWanted >= 0)
-            q.xcdSkew = skewable ? (uint32_t)(p.xcdSkewWanted < 8 ? p.xcdSkewWanted : 7) : 0u;
-        q.xcdRotate = (tpv == 1 && numGroups >= kFill) ? 1u : 0u;
-        if (p.xcdRotateWanted >= 0)
-            q.xcdRotate = p.xcdRotateWanted ? 1u : 0u;
-        const dim3 grid(numGroups);
-        const dim3 gblock(kWave * groupWaves(p.anyTextured != 0));
-        // The argument header (GroupHeader, raster.hpp) goes along with every launch; the FAST instantiations --
-        // 16 slots, one-tile views, uniform worlds whose table fits the header, no diagnostics -- read nothing else
-        // ahead of their pose loads.
-        GroupHeader h {};
-        h.pose = p.poseBlock;
-        h.geom = p.geomBlock;
-        h.views = p.numViews;
-        h.instances = p.numInstances;
-        h.poolTris = p.poolTris;
-        h.groups = numGroups;
-        bool fast = slots == 16 && tpv == 1 && gpv == 1 && p.uniInstances != 0 && p.uniCamsPerWorld < 256 && vg < 256 &&
-                    p.poseBlock && p.geomBlock && p.debugSkip == 0 && p.debugStamps == nullptr && p.uniPrefix[4] < 256;
-        for (int i = 0; i < 4 && fast; ++i)
-            fast = p.uniFirstTri[i] < 65536u;
+        bool fastAllowed = true;
         if (const char *dbg = std::getenv("MRX_GROUP_FAST"))      // 0: never (A/B and tests)
-            fast = fast && std::atoi(dbg) != 0;
-        if (entry) *entry = fast ? kEntryGroupFast : kEntryGroup;
-        if (fast) {
-            h.shape = vg | (q.xcdSkew << 8) | (q.xcdRotate << 12) | (p.uniInstances << 13) | (p.uniCamsPerWorld << 16) | (1u << 31);
-            h.prefix = p.uniPrefix[1] | (p.uniPrefix[2] << 8) | (p.uniPrefix[3] << 16) | (p.uniPrefix[4] << 24);
-            h.first01 = p.uniFirstTri[0] | (p.uniFirstTri[1] << 16);
-            h.first23 = p.uniFirstTri[2] | (p.uniFirstTri[3] << 16);
-        }
-        // Instantiation choice: the form (groupForm), then slots x ids x textured; the uniform kernels by XMODE and OUT
-        // too.  FAST and XMODE 1..3 exist with 16 slots only, the label forms with ids only.
-        const KernelForm form = groupForm(p);
-        if (took) *took = LaunchForm { (int32_t)form, slots };
-        const bool tex = p.anyTextured != 0;
-        // output selection: one instantiation per setting (kOutRGBD = the kernels as they always were)
-        const OutSel out = outSelOf(p.rgb, p.depth);
-        // XCD phase: trade places within the pairs on an odd start, ask for a report now and then
-        const int xmode = slots != 16 ? 0 : ((q.xcdSkew && (p.xcdPhase & 1u)) ? 1 : 0) | (p.xccReport ? 2 : 0);
-        const auto byTexIds = [&](auto f) {
-            withBool(tex, [&](auto TEX) { withBool(ids, [&](auto IDS) { f(IDS, TEX); }); });
-        };
-        const auto launchFast = [&](auto kernel) {        // the FAST entry: the header in front
-            kernel<<<grid, gblock, 0, stream>>>(h.pose, h.geom, h.views, h.instances, h.poolTris, h.shape, h.groups, h.prefix,
-                                                h.first01, h.first23, q);
-        };
-        const auto launchPlain = [&](auto kernel) { kernel<<<grid, gblock, 0, stream>>>(q); };
-        withValue<int, 16, 32, 64, 128, 256>(slots, [&](auto S) {
-            constexpr int kSlots = decltype(S)::value;
-            if (form != KernelForm::Uniform) {
-                withValue<KernelForm, KernelForm::PV, KernelForm::PVL, KernelForm::C, KernelForm::PVLC, KernelForm::M,
-                          KernelForm::PVLM, KernelForm::N, KernelForm::NPV, KernelForm::L, KernelForm::LN>(form, [&](auto F) {
-                    constexpr KernelForm kForm = decltype(F)::value;
-                    byTexIds([&](auto IDS, auto TEX) {
-                        constexpr bool kIds = decltype(IDS)::value, kTex = decltype(TEX)::value;
-                        if constexpr (kIds || !formFlags(kForm).lab) {   // (groupForm: labels with ids only)
-                            if constexpr (kSlots == 16) {
-                                if (fast)
-                                    return launchFast(rasterGroupFormKernelFast<kForm, kIds, kTex>);
-                            }
-                            launchPlain(rasterGroupFormKernel<kForm, kIds, kSlots, kTex>);
-                        }
-                    });
-                });
-                return;
-            }
-            withValue<int, 0, 1, 2, 3>(xmode, [&](auto X) {
-                constexpr int kX = decltype(X)::value;
-                if constexpr (kX == 0 || kSlots == 16)
-                    withValue<int, kOutDepth, kOutRGB, kOutRGBD>(out, [&](auto O) {
-                        // rgb only: the FAST entry has its fixed instantiation, the plain one selects by pointer
-                        constexpr int kO = decltype(O)::value, kOP = kO == kOutRGB ? kOutByPointer : kO;
-                        if constexpr (kSlots == 16) {
-                            if (fast)
-                                return byTexIds([&](auto IDS, auto TEX) {
-                                    launchFast(rasterGroupKernelFast<decltype(IDS)::value, decltype(TEX)::value, kX, kO>);
-                                });
-                        }
-                        byTexIds([&](auto IDS, auto TEX) {
-                            launchPlain(rasterGroupKernel<decltype(IDS)::value, kSlots, decltype(TEX)::value, kX, kOP>);
-                        });
-                    });
-            });
-        });
+            fastAllowed = std::atoi(dbg) != 0;
+        const GroupPlan plan = groupPlan(p, maxWorldTris, fastAllowed);
+        if (entry) *entry = plan.fast ? kEntryGroupFast : kEntryGroup;
+        launchGroup(p, plan, stream, took);
     }
     return hipGetLastError();
 }

@@ -2,6 +2,7 @@
 // host launcher.  Layouts are described in DESIGN.md section 4.
 #pragma once
 
+#include <algorithm>
 #include <cstdint>
 #include <type_traits>
 #include <hip/hip_runtime_api.h>
@@ -293,6 +294,40 @@ struct GroupHeader {
     uint32_t prefix;         // uniPrefix[1..4], eight bits each
     uint32_t first01, first23;   // uniFirstTri[0..3], sixteen bits each
 };
+// The layout of the four packed words, defined once: the host packs with these functions (groupPlan below), the
+// kernel's prologue unpacks with them (raster.hip), and what a field cannot hold keeps a launch off the FAST entry
+// (hdrFits).  A field is (first bit, width) within its word.
+struct HdrField {
+    uint32_t shift, bits;
+};
+constexpr HdrField kHdrGrpViews = { 0, 8 }, kHdrXcdSkew = { 8, 4 }, kHdrXcdRotate = { 12, 1 }, kHdrUniInstances = { 13, 3 },
+                   kHdrUniCams = { 16, 8 }, kHdrValid = { 31, 1 };
+constexpr uint32_t kHdrPrefixBits = 8;    // prefix: uniPrefix[i] at 8 (i - 1), i = 1..4
+constexpr uint32_t kHdrFirstBits = 16;    // first01 / first23: uniFirstTri[i] at 16 (i & 1)
+MRX_HD inline bool hdrFits(uint32_t value, uint32_t bits) { return value < (1u << bits); }
+MRX_HD inline uint32_t hdrPackShape(uint32_t grpViews, uint32_t xcdSkew, uint32_t xcdRotate, uint32_t uniInstances,
+                                    uint32_t uniCams)
+{
+    return (grpViews << kHdrGrpViews.shift) | (xcdSkew << kHdrXcdSkew.shift) | (xcdRotate << kHdrXcdRotate.shift) |
+           (uniInstances << kHdrUniInstances.shift) | (uniCams << kHdrUniCams.shift) | (1u << kHdrValid.shift);
+}
+MRX_HD inline uint32_t hdrPackPrefix(const uint32_t (&uniPrefix)[5])
+{
+    return uniPrefix[1] | (uniPrefix[2] << kHdrPrefixBits) | (uniPrefix[3] << 2 * kHdrPrefixBits) |
+           (uniPrefix[4] << 3 * kHdrPrefixBits);
+}
+MRX_HD inline uint32_t hdrPackFirst(uint32_t even, uint32_t odd) { return even | (odd << kHdrFirstBits); }
+// the fields of the shape word, each with its shift and mask as constants where the expression is written
+constexpr uint32_t hdrMask(HdrField f) { return (1u << f.bits) - 1u; }
+static_assert(kHdrGrpViews.shift == 0, "the first field");
+MRX_HD inline uint32_t hdrGrpViews(uint32_t shape) { constexpr uint32_t m = hdrMask(kHdrGrpViews); return shape & m; }
+MRX_HD inline uint32_t hdrXcdSkew(uint32_t shape) { constexpr uint32_t s = kHdrXcdSkew.shift, m = hdrMask(kHdrXcdSkew); return (shape >> s) & m; }
+MRX_HD inline uint32_t hdrXcdRotate(uint32_t shape) { constexpr uint32_t s = kHdrXcdRotate.shift, m = hdrMask(kHdrXcdRotate); return (shape >> s) & m; }
+MRX_HD inline uint32_t hdrUniInstances(uint32_t shape) { constexpr uint32_t s = kHdrUniInstances.shift, m = hdrMask(kHdrUniInstances); return (shape >> s) & m; }
+MRX_HD inline uint32_t hdrUniCams(uint32_t shape) { constexpr uint32_t s = kHdrUniCams.shift, m = hdrMask(kHdrUniCams); return (shape >> s) & m; }
+// uniPrefix[i], i = 1..4, of the prefix word; uniFirstTri[i] of the word that holds it (first01 for 0 and 1, first23)
+MRX_HD inline uint32_t hdrPrefix(uint32_t word, uint32_t i) { return (word >> kHdrPrefixBits * (i - 1u)) & ((1u << kHdrPrefixBits) - 1u); }
+MRX_HD inline uint32_t hdrFirst(uint32_t word, uint32_t i) { return (word >> kHdrFirstBits * (i & 1u)) & ((1u << kHdrFirstBits) - 1u); }
 
 // Default dispatch: worlds of this many triangles and more take the BVH path
 // (measured crossover, profiles/r02_bvh_crossover.txt; MRX_BVH_MIN_TRIS overrides; small batches of 64x64 views
@@ -381,6 +416,134 @@ enum KernelVariant : int32_t {
 // Workgroups of the group kernel a launch needs before the chip counts as full: a CU holds 2048 threads = four
 // workgroups of 512 (the untextured kernel; the textured one has 256 threads and longer tiles -- same target).
 inline uint32_t groupFill(uint32_t numCUs) { return 4u * (numCUs ? numCUs : 256u); }
+
+// ---- the group kernel's launch plan (raster.hip rasterGroupKernel) --------------------------------
+// (kWave and kChunk are the device sources' names for the wave size and the set-up pass; they stand here, in namespace mrx,
+// because the plan below is the launcher's text -- no other source of the library defines either name)
+constexpr int kWave = 64;
+constexpr int kChunk = 64;       // triangles set up per pass (one per lane)
+// A group is up to 16 tiles drawn from one or more views whose triangles fit
+// the records together (setup is per view, shared by the view's tiles).  Up to
+// 64 slots per view the group holds kChunk records (with the XCD-aware split
+// a workgroup on a fast XCD carries one 16-slot view more); views of 128 / 256
+// slots are one view per group.
+constexpr int kGroupTilesMax = 16;
+constexpr int kGroupSlotsMax = 256;
+constexpr int groupTilesMax(int slots) { return slots <= 128 ? kGroupTilesMax : 8; }
+// Waves per workgroup of the group kernel: eight for untextured scenes (more
+// waves in flight absorb the stalls of a saturated store path), four for the
+// textured variant (its texel loads cost registers and vmcnt drains).
+constexpr int groupWaves(bool tex) { return tex ? 4 : 8; }
+
+// What launchRaster launches for a batch of worlds of at most kGroupSlotsMax triangles: the shape of the workgroups,
+// the XCD split, the entry and the header that goes with the launch.  All of it decides speed only -- every shape
+// renders the same pixels -- so it is host arithmetic a test can read (mrx_group_plan) where no parity test would
+// notice a slip.
+struct GroupPlan {
+    int slots;                   // triangle slots per view: 16 ... 256
+    uint32_t grpViews, grpChunkTiles, grpPerView;   // RasterParams' members of these names
+    uint32_t workgroups, threads;
+    uint32_t xcdSkew, xcdRotate; // RasterParams' members of these names
+    int xmode;                   // the XMODE instantiation (raster.hip): bit 0 trade places, bit 1 report
+    bool fast;                   // the FAST entry
+    GroupHeader header;          // shape, prefix, first01 and first23 are filled in for the FAST entry only
+};
+// `fastAllowed`: MRX_GROUP_FAST as launchRaster reads it (false: never the FAST entry).  No HIP call, no environment.
+inline GroupPlan groupPlan(const RasterParams &p, uint32_t maxWorldTris, bool fastAllowed)
+{
+    GroupPlan plan {};
+    // triangle slots per view: the smallest of 16 ... 256 that holds a world
+    int slots = 16;
+    while ((uint32_t)slots < maxWorldTris)
+        slots *= 2;
+    if (p.debugSlots >= slots && p.debugSlots <= kGroupSlotsMax && (p.debugSlots & (p.debugSlots - 1)) == 0)
+        slots = p.debugSlots;                 // tuning / test aid (MRX_DEBUG_SLOTS)
+    // Workgroup shape.  Setup is per view and the view's tiles share it, so
+    // a workgroup takes as many whole views as fit 64 records and 16 tiles
+    // (8 for views of 256 slots); a view of more tiles is cut into chunks.
+    // Small batches shrink the workgroups again until there are ~4 per CU.
+    const uint32_t tpv = p.tilesFast * p.tilesSlow;
+    const uint32_t maxTiles = (uint32_t)groupTilesMax(slots);
+    const uint32_t kFill = groupFill(p.numCUs);    // 4 resident workgroups per CU: 1024 on 256 CUs
+    uint32_t vg = 1, ct = tpv, gpv = 1;
+    if (tpv == 1) {
+        // one-tile views: as many as fit 64 records, all workgroups resident
+        // (textured: two -- its workgroups have four waves and longer tiles)
+        vg = std::max<uint32_t>(1u, (uint32_t)(kChunk / slots));
+        if (p.anyTextured)
+            vg = std::min<uint32_t>(vg, 2u);
+        // ... until ~4 workgroups per CU remain; two views per workgroup are kept
+        // down to 2 per CU (1024 worlds: 9.9 -> 9.3 us)
+        while (vg > 1 && (p.numViews + vg - 1) / vg < (vg == 2 ? kFill / 2 : kFill))
+            vg /= 2;
+    } else if (p.anyTextured) {
+        // textured, several tiles per view: a quarter of a view per workgroup, at most four
+        // tiles (4 waves per workgroup and per-pixel texturing make a tile long enough for
+        // its own setup; measured on 128^2 and 256^2: profiles/r01_group_shapes.txt)
+        ct = std::max<uint32_t>(1u, std::min<uint32_t>(4u, tpv / 4u));
+    } else {
+        // untextured, several tiles per view: one view per workgroup, at most eight tiles
+        ct = std::min<uint32_t>(tpv, std::min<uint32_t>(maxTiles, 8u));
+    }
+    if (tpv != 1)
+        while (ct > 1 && (uint64_t)p.numViews * ((tpv + ct - 1) / ct) < kFill)
+            ct = (ct + 1) / 2;
+    if (p.grpViewsWanted > 0 && tpv * (uint32_t)p.grpViewsWanted <= maxTiles &&
+        p.grpViewsWanted * slots <= kChunk) {
+        vg = (uint32_t)p.grpViewsWanted;
+        ct = tpv;
+    }
+    if (p.grpTilesWanted > 0 && (uint32_t)p.grpTilesWanted <= maxTiles) {
+        vg = 1;
+        ct = std::min<uint32_t>((uint32_t)p.grpTilesWanted, tpv);
+    }
+    gpv = (tpv + ct - 1) / ct;
+    plan.slots = slots;
+    plan.grpViews = vg;
+    plan.grpChunkTiles = ct;
+    plan.grpPerView = gpv;
+    const uint32_t numGroups = gpv == 1 ? (p.numViews + vg - 1) / vg : p.numViews * gpv;
+    // XCD-aware split.  Workgroups go round-robin to the eight XCDs and the
+    // odd XCD of every pair drains its stores ~15 % more slowly (measured,
+    // profiles/r01_xcd.txt): once the batch fills the chip, xcdSkew strips
+    // (eighths of a tile) per workgroup pair move from the odd to the even
+    // XCD (see the kernel prologue).
+    const bool skewable = slots == 16 && tpv == 1 && (vg == 4 || vg == 2);
+    plan.xcdSkew = (skewable && numGroups >= kFill) ? (vg == 4 ? 3u : 1u) : 0u;
+    if (p.xcdSkewWanted >= 0)
+        plan.xcdSkew = skewable ? (uint32_t)(p.xcdSkewWanted < 8 ? p.xcdSkewWanted : 7) : 0u;
+    plan.xcdRotate = (tpv == 1 && numGroups >= kFill) ? 1u : 0u;
+    if (p.xcdRotateWanted >= 0)
+        plan.xcdRotate = p.xcdRotateWanted ? 1u : 0u;
+    plan.workgroups = numGroups;
+    plan.threads = (uint32_t)(kWave * groupWaves(p.anyTextured != 0));
+    // The argument header (GroupHeader) goes along with every launch; the FAST instantiations --
+    // 16 slots, one-tile views, uniform worlds whose table fits the header, no diagnostics -- read nothing else
+    // ahead of their pose loads.
+    GroupHeader &h = plan.header;
+    h.pose = p.poseBlock;
+    h.geom = p.geomBlock;
+    h.views = p.numViews;
+    h.instances = p.numInstances;
+    h.poolTris = p.poolTris;
+    h.groups = numGroups;
+    bool fast = slots == 16 && tpv == 1 && gpv == 1 && p.uniInstances != 0 && hdrFits(p.uniCamsPerWorld, kHdrUniCams.bits) &&
+                hdrFits(vg, kHdrGrpViews.bits) && p.poseBlock && p.geomBlock && p.debugSkip == 0 && p.debugStamps == nullptr &&
+                hdrFits(p.uniPrefix[4], kHdrPrefixBits);
+    for (int i = 0; i < 4 && fast; ++i)
+        fast = hdrFits(p.uniFirstTri[i], kHdrFirstBits);
+    fast = fast && fastAllowed;
+    plan.fast = fast;
+    if (fast) {
+        h.shape = hdrPackShape(vg, plan.xcdSkew, plan.xcdRotate, p.uniInstances, p.uniCamsPerWorld);
+        h.prefix = hdrPackPrefix(p.uniPrefix);
+        h.first01 = hdrPackFirst(p.uniFirstTri[0], p.uniFirstTri[1]);
+        h.first23 = hdrPackFirst(p.uniFirstTri[2], p.uniFirstTri[3]);
+    }
+    // XCD phase: trade places within the pairs on an odd start, ask for a report now and then
+    plan.xmode = slots != 16 ? 0 : ((plan.xcdSkew && (p.xcdPhase & 1u)) ? 1 : 0) | (p.xccReport ? 2 : 0);
+    return plan;
+}
 // Triangles per world from which the default dispatch takes the BVH path (mrx_api.cpp bindGeometry).  `base` is the
 // general threshold (kBvhMinTris or MRX_BVH_MIN_TRIS).  Small batches of one-tile views cross earlier, because up to two
 // workgroups per CU the BVH kernel's launch costs what its slowest workgroup costs while the raster kernels' 128-slot

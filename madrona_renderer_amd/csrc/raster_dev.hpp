@@ -13,7 +13,6 @@
 namespace mrx {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kCold = 12;        // dwords: u/v planes, lit colour
 constexpr int kRegionBlocks = 4; // a lane owns 4 consecutive pixels of a 32x8 region
 
