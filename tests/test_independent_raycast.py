@@ -30,14 +30,16 @@ def quat_to_mat(q):
                      [2 * (x * z - w * y), 2 * (y * z + w * x), 1 - 2 * (x * x + y * y)]])
 
 
-def raycast_view(fs, v):
+def raycast_view(fs, v, vfov=90.0, znear=None):
     """(tri [H,W] or -1, depth [H,W], margin [H,W]): nearest hit per pixel in
-    float64 and how unambiguous it is (>= 0; small = too close to call)."""
+    float64 and how unambiguous it is (>= 0; small = too close to call).
+    vfov (degrees) and znear are the view's projection; the defaults are the
+    build's (90 degrees; the mode's near plane)."""
     W, H = fs.width, fs.height
     w = int(fs.view_world[v])
     Rc = quat_to_mat(fs.cam_rot[v])
     c = fs.cam_pos[v].astype(np.float64)
-    th = math.tan(math.radians(45.0))
+    th = math.tan(math.radians(vfov / 2.0))
     asp = W / H
     px = (np.arange(W) + 0.5) / W * 2 - 1
     py = 1 - (np.arange(H) + 0.5) / H * 2
@@ -46,6 +48,8 @@ def raycast_view(fs, v):
     fwd = Rc[:, 1]
     rt = fs.raytracer
     near, far = (0.1, 1000.0) if rt else (0.001, np.inf)
+    if znear is not None:
+        near = float(znear)
     best = np.full((H, W), np.inf)
     second = np.full((H, W), np.inf)
     tri = np.full((H, W), -1, np.int64)
@@ -172,16 +176,17 @@ def test_meshes_with_hierarchies_agree_with_float64_moeller_trumbore(oracle_mod)
     assert checked > 0.8 * hits > 0, f"only {checked} of {hits} covered pixels were decisive"
 
 
-def raycast_colour(fs, v):
+def raycast_colour(fs, v, vfov=90.0, znear=None):
     """(rgb [H,W,3] float64 prediction in 0..255 before rounding, decisive [H,W] bool, tri, margin): the
     colour of the nearest hit per pixel from first principles in float64 -- world-space normal turned
     towards the eye, one directional light travelling along (1, -1, -0.05), 0.25 ambient + 0.75
-    diffuse, material colour, nearest texel of the perspective-correct (barycentric) uv with v up."""
+    diffuse, material colour, nearest texel of the perspective-correct (barycentric) uv with v up.
+    vfov and znear as in raycast_view."""
     W, H = fs.width, fs.height
     w = int(fs.view_world[v])
     Rc = quat_to_mat(fs.cam_rot[v])
     c = fs.cam_pos[v].astype(np.float64)
-    th = math.tan(math.radians(45.0))
+    th = math.tan(math.radians(vfov / 2.0))
     asp = W / H
     px = (np.arange(W) + 0.5) / W * 2 - 1
     py = 1 - (np.arange(H) + 0.5) / H * 2
@@ -191,6 +196,8 @@ def raycast_colour(fs, v):
     to_light /= np.linalg.norm(to_light)
     rt = fs.raytracer
     near, far = (0.1, 1000.0) if rt else (0.001, np.inf)
+    if znear is not None:
+        near = float(znear)
     best = np.full((H, W), np.inf)
     rgb = np.zeros((H, W, 3))
     sure_tex = np.ones((H, W), bool)
